@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """bench.py -- SCF-step wall time, Numerov sweeps/s and Poisson V-cycles/s for Radon (Z=86) at 131073 grid points on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--atoms B] [--lsda] [--levels 17] [--no-cpu] [--no-extras]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--atoms B] [--lsda] [--levels 17] [--dump-outputs DIR]
+                    [--full [--no-cpu] [--no-extras]]
+
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds everything that takes runs of its own: the
+measured copy / triad bandwidth next to the roofline, the extra workloads, the periodic table, the per-call surface and the CPU
+baseline.  --dump-outputs DIR writes what the last timed step computed (dump_outputs) as DIR/<name>.npy.
 
 Workload of the headline line (BASELINE.json configs[1]): Rn Z=86 LDA, 17 multigrid levels (131073 nodes), delta = 1e-4,
 Rmax = 50, mixing 0.5 (README.md:54 of the reference); one "step" = one SCF iteration of the atom batch, state resident in
@@ -16,15 +21,16 @@ integrating; `sweeps_reference_executed` leaves those out) divided by the elapse
 the same quantity the CPU baseline reports.
 
 The ONE line on stdout is compact (< 7 KB: the driver keeps the last 8 KB of stdout; compact_line()); the complete result with every
-kernel object and its notes goes to profiles/bench_full_last.json (and gpurun_out/bench_full_last.json).  On the line:
+kernel object and its notes goes to profiles/bench_full_last.json (and a second copy: write_full()).  On the line:
   roofline       the DOMINANT kernel of the timed region (by HIP-event time): the persistent multigrid kernel or the sweep
                  kernel; achieved = algorithmic bytes / its HIP-event time, against 8 TB/s; traffic,
                  hbm_GBps_counters, frac_counters = rocprofv3 FETCH/WRITE bytes of the committed profile of this workload
   kernels        both hot kernels, flat: frac (reference's bisection path), frac_issued (every speculative trial), counters
-  extra          (N = 1 only) one flat object per further workload: tolerance mode, Rn LSDA (configs[2]), a 256-atom batch,
-                 1 048 577 nodes x 1 and x 16 atoms (configs[4]); --all-extras: LSDA tolerance, 1024 atoms, dense-K sweeps
-  cpu_baseline   the oracle on the host: 1 core (how the reference runs) + scalars for the table variant, 15 level threads and
-                 one replica per physical core
+  extra          (--full, N = 1 only) one flat object per further workload: tolerance mode, Rn LSDA (configs[2]), a 256-atom batch,
+                 1 048 577 nodes x 1 and x 16 atoms (configs[4]); --all-extras: LSDA tolerance, 1024 atoms, dense-K sweeps;
+                 (--full, any N) the periodic table (configs[3])
+  cpu_baseline   (--full) the oracle on the host: 1 core (how the reference runs) + scalars for the table variant, 15 level threads
+                 and one replica per physical core
 
 N > 1 (launched by torch.distributed.run): atoms are independent, so every rank advances its own replica of the batch (weak
 scaling, no data-path collective); the per-atom result records are all_gathered over RCCL once after the last step, inside
@@ -418,6 +424,52 @@ def run_workload(D, ctx, grid, levels, atoms, lsda, steps, warmup, tree_depth, b
     return scf, tot
 
 
+DUMP_LIMIT = 64 << 20          # bytes of all files of --dump-outputs together
+
+
+def dump_outputs(D, scf, torch, path):
+    """--dump-outputs: what a caller of the timed path holds after its last step, as float64 arrays in path/<name>.npy.  Every atom's
+    energies (the nine fields of dfta_energies), finished flag, level eigenvalues (atom x spin x level, NaN-padded) and 64-double record;
+    the radial arrays of dfta_scf_get_array (density, potential, Hartree U; LSDA: also both spin densities and potentials) of every atom,
+    or, where they would pass the size limit, of a fixed seeded sample of atoms (radial_atoms.npy) and, past one atom, of grid points
+    (radial_points.npy)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    n, N = scf.natoms, scf.grid.N
+    out = {}
+    en, fin = scf.energies()
+    out["energies"] = np.array([[getattr(e, k) for k, _ in D.Energies._fields_] for e in en])
+    out["finished"] = fin.astype(np.float64)
+    spins = 2 if scf.lsda else 1
+    lv = [[scf.levels(a, s)["E"] for s in range(spins)] for a in range(n)]
+    nlev = max(len(E) for row in lv for E in row)
+    out["eigenvalues"] = np.full((n, spins, nlev), np.nan)
+    for a in range(n):
+        for s in range(spins):
+            out["eigenvalues"][a, s, :len(lv[a][s])] = lv[a][s]
+    rec = torch.zeros((n, D.RECORD_DOUBLES), dtype=torch.float64, device="cuda")
+    scf.records_into(rec.data_ptr())
+    out["records"] = rec.cpu().numpy()
+    radial = ({"density": 0, "density_A": 1, "density_B": 2, "potential_A": 3, "potential_B": 4, "hartree_U": 5} if scf.lsda else
+              {"density": 0, "potential": 3, "hartree_U": 5})
+    budget = DUMP_LIMIT - sum(a.nbytes for a in out.values()) - (1 << 20)     # headroom for the sample indices and .npy headers
+    rng = np.random.default_rng(0)
+    per_atom = len(radial) * N * 8
+    atoms = np.arange(n) if n * per_atom <= budget else np.sort(rng.choice(n, max(1, budget // per_atom), replace=False))
+    points = None if per_atom <= budget else np.sort(rng.choice(N, budget // ((len(radial) + 1) * 8), replace=False))   # + the index file
+    for name, which in radial.items():
+        a2 = np.stack([scf.array(which, int(a)) for a in atoms])
+        out[name] = a2 if points is None else a2[:, points]
+    if len(atoms) < n:
+        out["radial_atoms"] = atoms.astype(np.float64)
+    if points is not None:
+        out["radial_points"] = points.astype(np.float64)
+    assert sum(a.nbytes for a in out.values()) <= DUMP_LIMIT - (1 << 16)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+    return sorted(out)
+
+
 def kernel_figures(tot, levels, N, atoms, workload=None):
     """per-kernel roofline figures of a workload (HIP-event times measured inside the library on the launch stream).
     `algorithmic_*` = SURVEY 8d bytes / time: a yardstick, NOT a bandwidth (levels resident in LDS / L2 and trials sharing a table row
@@ -619,12 +671,15 @@ def main():
     ap.add_argument("--adaptive", action="store_true", help="DFTA_POISSON_ADAPTIVE for the headline workload: the tolerance kernels, V-cycles stop on the round-off floor (6-8 instead of the reference's 100)")
     ap.add_argument("--scan-sweeps", action="store_true", help="the sweeps' opt-in tolerance mode (DFTA_SWEEPS_TOLERANCE: transfer-matrix scans) for the headline workload")
     ap.add_argument("--tree-depth", type=int, default=0)
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
-    ap.add_argument("--no-extras", action="store_true", help="skip the extra workloads (256-atom batch, LSDA, 1 048 577 nodes)")
-    ap.add_argument("--all-extras", action="store_true", help="also: LSDA in tolerance mode, a 1024-atom batch, the dense-K sweep benchmark")
-    ap.add_argument("--no-cpu-all-cores", action="store_true", help="CPU baseline: skip the one-replica-per-physical-core leg")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last one computed as DIR/<name>.npy (dump_outputs)")
+    ap.add_argument("--full", action="store_true", help="also measure what takes runs of its own: the HBM copy / triad bandwidth, the extra "
+                                                        "workloads, the periodic table, the per-call surface and the CPU baseline")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU baseline leg")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip the extra workloads (256-atom batch, LSDA, 1 048 577 nodes)")
+    ap.add_argument("--all-extras", action="store_true", help="--full: also LSDA in tolerance mode, a 1024-atom batch, the dense-K sweep benchmark")
+    ap.add_argument("--no-cpu-all-cores", action="store_true", help="--full, CPU baseline: skip the one-replica-per-physical-core leg")
     ap.add_argument("--cpu-steps", type=int, default=3)
-    ap.add_argument("--no-periodic-table", action="store_true", help="skip BASELINE config 4 (Z = 1..86, sharded by atom over the ranks) after the timed steps")
+    ap.add_argument("--no-periodic-table", action="store_true", help="--full: skip BASELINE config 4 (Z = 1..86, sharded by atom over the ranks) after the timed steps")
     ap.add_argument("--pt-zmax", type=int, default=86, help="last atom of the periodic-table sweep (tests shorten it)")
     args = ap.parse_args()
 
@@ -674,7 +729,7 @@ def main():
     stream = torch.cuda.current_stream().cuda_stream
     ctx = D.Context(dev_index, stream)
     grid = D.Grid(ctx, args.levels, delta, rmax)
-    if rank == 0:
+    if rank == 0 and args.full:
         try:
             HBM_MEASURED["copy"], HBM_MEASURED["triad"] = ctx.measure_hbm(1 << 27, 5)      # 3 x 1 GiB arrays, a few ms
         except Exception:
@@ -708,9 +763,12 @@ def main():
         ref_all, issued_all, vc_all, exe_all = (float(x) for x in w.tolist())
     else:
         ref_all, issued_all, vc_all, exe_all = (float(tot[k]) for k in ("sweeps_reference", "sweeps_issued", "vcycles", "sweeps_reference_executed"))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(D, scf, torch, args.dump_outputs)
     scf.close()
+    extras = args.full and not args.no_extras
     pt_extra = None
-    if not args.no_periodic_table and not args.no_extras and args.atoms == 1 and not args.lsda and not args.tolerance and not args.scan_sweeps and not args.adaptive:
+    if not args.no_periodic_table and extras and args.atoms == 1 and not args.lsda and not args.tolerance and not args.scan_sweeps and not args.adaptive:
         t_w = time.time()
         pt_extra = periodic_table(D, ctx, grid, args.levels, world, rank, dist, torch, shared, args.pt_zmax)
         if rank == 0:
@@ -776,12 +834,12 @@ def main():
             "parity_gates": parity_gates(pmode, "tolerance" if args.scan_sweeps else "exact"),
         }
         cpu_job = None
-        want_cpu = world == 1 and not args.no_cpu      # rank 0 at N = 1 only: the other ranks of a larger job would sit at the final barrier
+        want_cpu = args.full and world == 1 and not args.no_cpu      # rank 0 at N = 1 only: the other ranks of a larger job would sit at the final barrier
         # The CPU legs run in child processes on the host cores NEXT TO the long extras (batches, 2^20+1 nodes) -- but start only after the
         # short single-atom extras: three Python children importing numpy while a 16 ms step is being timed cost it 3-5 ms of host jitter
-        if want_cpu and args.no_extras:
+        if want_cpu and not extras:
             cpu_job = cpu_baseline_start(args.levels, args.lsda, args.cpu_steps)
-        if world == 1 and not args.no_extras:
+        if world == 1 and extras:
             # further measured workloads with the same per-kernel figures (>= 10 timed steps after >= 5 warm-up steps wherever a step
             # is short enough): the opt-in tolerance mode of the multigrid smoother, LSDA (BASELINE config 3), a machine-filling
             # batch of Rn atoms, and the 1 048 577-node stress of config 5 (one atom and a batch of 16, SCF steps 6.. : from the seventh step
@@ -846,7 +904,7 @@ def main():
             cpu_job = cpu_baseline_start(args.levels, args.lsda, args.cpu_steps)
         if pt_extra is not None:
             out.setdefault("extra", {})["periodic_table"] = pt_extra
-        if world == 1 and not args.no_extras:
+        if world == 1 and extras:
             pcs = per_call_surface()
             if pcs is not None:
                 out.setdefault("extra", {})["per_call_surface"] = pcs

@@ -137,7 +137,7 @@ def test_bench_two_ranks_control_flow():
         port = s.getsockname()[1]
     env = dict(os.environ, DFTA_BENCH_SHARED_GPU="1")
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-                          "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--pt-zmax", "7"],
+                          "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full", "--pt-zmax", "7"],
                          env=env, capture_output=True, text=True, timeout=600, cwd=root)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -174,6 +174,34 @@ def test_bench_gpus_flag_starts_the_ranks_itself():
         bad = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0"],
                              env=env, capture_output=True, text=True, timeout=600, cwd=root)
         assert bad.returncode != 0 and "only" in bad.stderr and not [ln for ln in bad.stdout.splitlines() if ln.startswith("{")]
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_times_the_steps_and_dumps_the_last_one(tmp_path):
+    """`bench.py --steps K --warmup W` without --full: the headline line alone (no extras, no CPU baseline), K timed steps, and with
+    --dump-outputs the arrays of the last timed step as float64 .npy files within 64 MB -- here a 24-atom batch whose radial arrays
+    (3 MB per atom) pass the limit, so a seeded sample of atoms is written"""
+    import json
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    dump = tmp_path / "out"
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--atoms", "24",
+                          "--dump-outputs", str(dump)], capture_output=True, text=True, timeout=600, cwd=root)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, out.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["value"] > 0 and d["dtype"] == "f64"
+    assert d["unit"] == "sweeps/s" and d["higher_is_better"] is True and "extra" not in d and "cpu_baseline" not in d
+    files = {p.stem: np.load(p) for p in dump.glob("*.npy")}
+    assert sum(p.stat().st_size for p in dump.glob("*.npy")) <= 64 << 20
+    assert all(a.dtype == np.float64 for a in files.values())
+    assert files["energies"].shape == (24, 9) and files["energies"][0, 0] == d["etotal_last_step"]
+    assert files["records"].shape == (24, 64) and files["eigenvalues"].shape == (24, 1, 15) and files["finished"].shape == (24,)
+    picked = files["radial_atoms"]
+    assert 1 <= len(picked) < 24 and np.all(np.diff(picked) > 0) and "radial_points" not in files
+    for name in ("density", "potential", "hartree_U"):
+        assert files[name].shape == (len(picked), 131073) and np.all(np.isfinite(files[name]))
 
 
 @pytest.mark.gpu
