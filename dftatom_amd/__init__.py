@@ -22,11 +22,11 @@ BOUNDARY_DEVICE, BOUNDARY_HOST = 0, 1
 LEVELS_CHAINED, LEVELS_BATCHED = 0, 1
 LEVELS_SCAN_SWEEPS = 0x10          # OR-ed into the mode of solve_levels: tolerance mode of the sweeps (transfer-matrix scan)
 SWEEPS_EXACT, SWEEPS_TOLERANCE = 0, 1
-ABI_VERSION = 6
+ABI_VERSION = 7
 LEVEL_CONVERGED, LEVEL_ITERATION_CAP, LEVEL_FIXED_POINT, LEVEL_U0_NONFINITE = 1, 2, 4, 8
 POISSON_DEFAULT, POISSON_EXACT, POISSON_TOLERANCE, POISSON_ADAPTIVE = -1, 0, 1, 2    # dfta_poisson_create_ex / dfta_scf_options::poisson_mode
 INT_TRAPEZOID, INT_SIMPSON13, INT_SIMPSON38, INT_BOOLE, INT_ROMBERG = range(5)
-XC_VWN, XC_CHACHIYO, XC_CHACHIYO_IMPROVED = range(3)
+XC_VWN, XC_CHACHIYO, XC_CHACHIYO_IMPROVED, XC_PW92, XC_PBE = range(5)
 AUFBAU_REFERENCE, AUFBAU_TRANSITION_METALS = range(2)
 RECORD_DOUBLES = 64
 
@@ -131,6 +131,8 @@ SIGNATURES = {
     "dfta_get_subshells_ex": (C.c_int, [C.c_int, C.c_int, c_ip, c_ip, c_ip, C.c_int]),
     "dfta_split_spin_ex": (C.c_int, [C.c_int, C.c_int, c_ip, c_ip, c_ip, c_ip, c_ip, c_ip, c_ip, c_ip, C.c_int]),
     "dfta_chachiyo_lda": (C.c_int, [vp, C.c_int, c_dp, C.c_size_t, c_dp, c_dp]),
+    "dfta_xc_pointwise": (C.c_int, [vp, C.c_int, C.c_size_t, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp]),
+    "dfta_xc_radial": (C.c_int, [vp, vp, C.c_int, C.c_int, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp]),
     "dfta_split_spin": (C.c_int, [C.c_int, c_ip, c_ip, c_ip, c_ip, c_ip, c_ip, c_ip, c_ip, C.c_int]),
     "dfta_ctx_measure_hbm": (C.c_int, [vp, C.c_size_t, C.c_int, c_dp, c_dp]),
     "dfta_poisson_create_ex": (C.c_int, [vp, vp, C.c_int, C.c_int, C.POINTER(vp)]),
@@ -469,6 +471,41 @@ def vwn_lsda(ctx, na, nb):
     r, va, vb, e = (np.zeros_like(na) for _ in range(4))
     ctx.check(ctx.lib.dfta_vwn_lsda(ctx.h, _dp(na), _dp(nb), na.size, _dp(r), _dp(va), _dp(vb), _dp(e)))
     return r, va, vb, e
+
+
+def xc_pointwise(ctx, functional, na, nb=None, saa=None, sab=None, sbb=None):
+    """e (per volume) and its partial derivatives for XC_PW92 / XC_PBE at independent points.  nb None: unpolarised
+    (n = na, sigma = saa): returns dict(e, dn, dsigma); else dict(e, dna, dnb, dsaa, dsab, dsbb)."""
+    na = _f64(na).ravel()
+    sz = na.size
+    arr = lambda a: None if a is None else _f64(np.broadcast_to(np.asarray(a, dtype=np.float64), na.shape)).ravel()
+    nb, saa, sab, sbb = arr(nb), arr(saa), arr(sab), arr(sbb)
+    p = lambda a: None if a is None else _dp(a)
+    out = [np.zeros(sz) for _ in range(6)]
+    pol = nb is not None
+    ctx.check(ctx.lib.dfta_xc_pointwise(ctx.h, int(functional), sz, _dp(na), p(nb), p(saa), p(sab), p(sbb), _dp(out[0]), _dp(out[1]),
+                                        _dp(out[2]) if pol else None, _dp(out[3]), _dp(out[4]) if pol else None,
+                                        _dp(out[5]) if pol else None))
+    if not pol:
+        return {"e": out[0], "dn": out[1], "dsigma": out[3]}
+    return dict(zip(("e", "dna", "dnb", "dsaa", "dsab", "dsbb"), out))
+
+
+def xc_radial(ctx, grid, functional, na, nb=None):
+    """The SCF's XC_PW92 / XC_PBE evaluation on `grid` for densities na (and nb: LSDA) of shape (natoms, N) or (N,).
+    LDA: returns (Vexc, eexc); LSDA: (res, va, vb, eexc) -- the outputs k_tail consumes (include/dftatom_hip.h)."""
+    na = _f64(na)
+    shape = na.shape
+    na = na.reshape(-1, grid.N)
+    natoms = na.shape[0]
+    res, eexc = np.zeros_like(na), np.zeros_like(na)
+    if nb is None:
+        ctx.check(ctx.lib.dfta_xc_radial(ctx.h, grid.h, int(functional), natoms, _dp(na), None, _dp(res), None, None, _dp(eexc)))
+        return res.reshape(shape), eexc.reshape(shape)
+    nb = _f64(nb).reshape(natoms, grid.N)
+    va, vb = np.zeros_like(na), np.zeros_like(na)
+    ctx.check(ctx.lib.dfta_xc_radial(ctx.h, grid.h, int(functional), natoms, _dp(na), _dp(nb), _dp(res), _dp(va), _dp(vb), _dp(eexc)))
+    return res.reshape(shape), va.reshape(shape), vb.reshape(shape), eexc.reshape(shape)
 
 
 class Scf:

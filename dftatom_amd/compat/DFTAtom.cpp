@@ -14,6 +14,7 @@ const char DFTAtom::orb[] = {'s', 'p', 'd', 'f'};
 int DFTAtom::levelsMode = DFTA_LEVELS_BATCHED;
 int DFTAtom::integrator = DFTA_INT_SIMPSON38;
 int DFTAtom::sweepMode = DFTA_SWEEPS_EXACT;
+int DFTAtom::functional = DFTA_XC_VWN;
 int DFTAtom::poissonMode = -1;      // as dfta_poisson_create: exact unless $DFTA_DEBUG POISSON_MODE (--poisson= overrides)
 std::ostream* DFTAtom::jsonOut = nullptr;
 
@@ -73,7 +74,7 @@ void DFTAtom::Run(bool lsda, bool uniform, int Z, int MultigridLevels, double al
     dfta_scf* scf = nullptr;
     dfta_scf_options opt = {};                    // zero = what the reference runs
     opt.struct_size = (int)sizeof(opt);
-    opt.integrator = integrator; opt.functional = DFTA_XC_VWN; opt.aufbau = DFTA_AUFBAU_REFERENCE;
+    opt.integrator = integrator; opt.functional = functional; opt.aufbau = DFTA_AUFBAU_REFERENCE;
     opt.poisson_mode = poissonMode; opt.sweep_mode = sweepMode;
     dfta_compat::check(dfta_scf_create_ex(rt.ctx(), grid, lsda ? 1 : 0, 1, &Z, alpha, levelsMode, 0, &opt, &scf), rt.ctx(), "dfta_scf_create");
     const int maxSteps = lsda ? 150 : 100;                                  // DFTAtom.cpp:396 / 908

@@ -1,6 +1,6 @@
 // dftatom_cli.cpp -- headless stand-in for the wxWidgets front end (DFTAtomFrame.cpp:174-199 + Options.h:48-54).
 //
-//   dftatom_cli Z MultigridLevels alpha MaxR deltaGrid method [chained] [--integrator=NAME]
+//   dftatom_cli Z MultigridLevels alpha MaxR deltaGrid method [chained] [--integrator=NAME] [--xc=NAME]
 //   dftatom_cli --ini DFTAtom.ini [chained] [--integrator=NAME] [--uniform]
 //
 // method: 0 = LDA, 1 = LSDA (the two the GUI reaches, DFTAtomFrame.cpp:190-195); 2 / 3 = the uniform-grid entry points
@@ -13,6 +13,7 @@
 // --json[=FILE]: one JSON line per SCF step (17-digit energies and eigenvalues, per-level status bits and sweep counts, rounds, V-cycles,
 //                phase times) to FILE, or to stderr -- the console protocol on stdout stays the reference's.
 // --sweeps=exact|tolerance, --poisson=exact|tolerance|adaptive: the opt-in tolerance modes of the device path (include/dftatom_hip.h).
+// --xc=vwn (default, what the reference runs) | chachiyo | chachiyo-improved (LDA only) | pw92 | pbe (logarithmic grid only).
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
@@ -65,7 +66,7 @@ const char* validate(const Options& o, bool uniform)
 int main(int argc, char** argv)
 {
     Options o;
-    bool uniform = false, have = false;
+    bool uniform = false, have = false, bad = false;
     int pos = 0;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
@@ -85,6 +86,13 @@ int main(int argc, char** argv)
             DFT::DFTAtom::sweepMode = a == "--sweeps=tolerance" ? DFTA_SWEEPS_TOLERANCE : DFTA_SWEEPS_EXACT;
         } else if (a == "--poisson=tolerance" || a == "--poisson=adaptive" || a == "--poisson=exact") {
             DFT::DFTAtom::poissonMode = a == "--poisson=tolerance" ? DFTA_POISSON_TOLERANCE : (a == "--poisson=adaptive" ? DFTA_POISSON_ADAPTIVE : DFTA_POISSON_EXACT);
+        } else if (a.rfind("--xc=", 0) == 0) {
+            const std::string n = a.substr(5);
+            const char* names[] = {"vwn", "chachiyo", "chachiyo-improved", "pw92", "pbe"};      // DFTA_XC_VWN .. DFTA_XC_PBE
+            int f = -1;
+            for (int k = 0; k < 5; ++k) if (n == names[k]) f = k;
+            if (f < 0) { std::cerr << "unknown functional " << n << std::endl; bad = true; }
+            else DFT::DFTAtom::functional = f;
         } else if (a.rfind("--integrator=", 0) == 0) {
             const std::string n = a.substr(13);
             const char* names[] = {"trapezoid", "simpson13", "simpson38", "boole", "romberg"};
@@ -104,9 +112,10 @@ int main(int argc, char** argv)
             }
         }
     }
-    if (!have) {
-        std::cerr << "usage: " << argv[0] << " Z MultigridLevels alpha MaxR deltaGrid method(0 LDA, 1 LSDA, 2 uniform LDA, 3 uniform LSDA) [chained] [--integrator=NAME]\n"
-                  << "       " << argv[0] << " --ini DFTAtom.ini [--uniform] [chained] [--integrator=NAME]\n";
+    if (!have || bad) {
+        std::cerr << "usage: " << argv[0] << " Z MultigridLevels alpha MaxR deltaGrid method(0 LDA, 1 LSDA, 2 uniform LDA, 3 uniform LSDA) [chained] [--integrator=NAME] [--xc=NAME]\n"
+                  << "       " << argv[0] << " --ini DFTAtom.ini [--uniform] [chained] [--integrator=NAME] [--xc=NAME]\n"
+                  << "       --xc=vwn (default) | chachiyo | chachiyo-improved | pw92 | pbe\n";
         return 2;
     }
     if (o.method == 2 || o.method == 3) { uniform = true; o.method -= 2; }

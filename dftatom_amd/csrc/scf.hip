@@ -257,6 +257,13 @@ struct dfta_scf {
 static int scf_xc(dfta_scf* s)
 {
     const size_t sz = (size_t)s->natoms * s->g->N;
+    // PBE: one fused stencil + pointwise + divergence launch (gga.hip), frozen atoms skipped; PW92: pointwise, as VWN
+    if (s->functional == DFTA_XC_PBE)
+        return dfta_launch_pbe_radial(s->ctx, s->g, s->natoms, s->lsda ? s->d_dA : s->d_density, s->lsda ? s->d_dB : nullptr, s->d_Vexc,
+                                      s->d_va, s->d_vb, s->d_eexc, s->d_fin);
+    if (s->functional == DFTA_XC_PW92)
+        return s->lsda ? dfta_launch_pw92_lsda(s->ctx, s->d_dA, s->d_dB, sz, s->d_Vexc, s->d_va, s->d_vb, s->d_eexc)
+                       : dfta_launch_pw92_lda(s->ctx, s->d_density, sz, s->d_Vexc, s->d_eexc);
     if (!s->lsda && s->functional != DFTA_XC_VWN)
         return dfta_launch_chachiyo_lda(s->ctx, s->functional == DFTA_XC_CHACHIYO_IMPROVED, s->d_density, sz, s->d_Vexc, s->d_eexc);
     if (!s->lsda) return dfta_launch_vwn_lda(s->ctx, s->d_density, sz, s->d_Vexc, s->d_eexc);
@@ -306,8 +313,9 @@ int dfta_scf_create_ex(dfta_ctx* ctx, const dfta_grid* g, int lsda, int natoms, 
     }
     DFTA_REQUIRE(ctx, opt.poisson_mode >= -1 && opt.poisson_mode <= DFTA_POISSON_ADAPTIVE, "poisson mode");
     DFTA_REQUIRE(ctx, dfta_integral_shape_ok(opt.integrator, g->N), "integration rule / grid size");
-    DFTA_REQUIRE(ctx, opt.functional >= DFTA_XC_VWN && opt.functional <= DFTA_XC_CHACHIYO_IMPROVED, "functional");
-    DFTA_REQUIRE(ctx, opt.functional == DFTA_XC_VWN || !lsda, "the Chachiyo functional is LDA only (ExcCor.h)");
+    DFTA_REQUIRE(ctx, opt.functional >= DFTA_XC_VWN && opt.functional <= DFTA_XC_PBE, "functional (DFTA_XC_VWN .. DFTA_XC_PBE)");
+    DFTA_REQUIRE(ctx, (opt.functional != DFTA_XC_CHACHIYO && opt.functional != DFTA_XC_CHACHIYO_IMPROVED) || !lsda, "the Chachiyo functional is LDA only (ExcCor.h)");
+    DFTA_REQUIRE(ctx, opt.functional != DFTA_XC_PBE || !g->uniform, "the PBE functional needs a logarithmic grid (no GGA on the uniform grid)");
     DFTA_REQUIRE(ctx, opt.aufbau == DFTA_AUFBAU_REFERENCE || opt.aufbau == DFTA_AUFBAU_TRANSITION_METALS, "aufbau");
     DFTA_REQUIRE(ctx, opt.sweep_mode == DFTA_SWEEPS_EXACT || opt.sweep_mode == DFTA_SWEEPS_TOLERANCE, "sweep mode");
     DFTA_REQUIRE(ctx, opt.sweep_mode == DFTA_SWEEPS_EXACT || dfta_scan_supported(g), "the tolerance mode of the sweeps needs a logarithmic grid of 12 .. 20 multigrid levels");

@@ -1,4 +1,4 @@
-// xc.h -- device-pointer launchers of the VWN kernels (xc.hip) and of the Poisson solve (poisson.hip)
+// xc.h -- device-pointer launchers of the exchange-correlation kernels (xc.hip, gga.hip) and of the Poisson solve (poisson.hip)
 #pragma once
 #include "common.h"
 
@@ -6,6 +6,14 @@ int dfta_launch_vwn_lda(dfta_ctx* ctx, const double* dN, size_t sz, double* dVex
 int dfta_launch_vwn_lsda(dfta_ctx* ctx, const double* dNa, const double* dNb, size_t sz, double* dRes, double* dVa, double* dVb,
                          double* dEexc);
 int dfta_launch_chachiyo_lda(dfta_ctx* ctx, int improved, const double* dN, size_t sz, double* dVexc, double* dEexc);
+// Slater exchange + PW92 correlation (xc.hip), same outputs as the VWN launchers
+int dfta_launch_pw92_lda(dfta_ctx* ctx, const double* dN, size_t sz, double* dVexc, double* dEexc);
+int dfta_launch_pw92_lsda(dfta_ctx* ctx, const double* dNa, const double* dNb, size_t sz, double* dRes, double* dVa, double* dVb,
+                          double* dEexc);
+// gga.hip: PBE on the logarithmic grid for natoms x N densities in one fused launch; dNb == nullptr: LDA (dRes = Vexc, dVa / dVb unused);
+// dFin: per atom, non-zero = frozen, leave its outputs alone (may be null)
+int dfta_launch_pbe_radial(dfta_ctx* ctx, const dfta_grid* g, int natoms, const double* dNa, const double* dNb, double* dRes,
+                           double* dVa, double* dVb, double* dEexc, const int* dFin);
 // poisson.hip: launch (asynchronous) / finish (synchronises, inspects the group barriers' abort flag and repeats the solve with
 // one workgroup per atom if it was raised).  dSkip: per atom, non-zero = leave this atom alone (may be null).
 int dfta_poisson_solve_launch(dfta_poisson* p, const int* dZ, const double* dDensity, double* dU, int* dVcycles, double* dErr,

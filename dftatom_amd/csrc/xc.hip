@@ -1,4 +1,4 @@
-// xc.hip -- Vosko-Wilk-Nusair exchange-correlation, LDA and LSDA, as coalesced pointwise kernels.
+// xc.hip -- Vosko-Wilk-Nusair exchange-correlation, LDA and LSDA, as coalesced pointwise kernels (and the PW92 / Chachiyo alternatives).
 //
 // Replaces VWNExchCor::Vexc / eexcDif (VWNExcCor.h:73-128, LDA) and the spin-polarised pair
 // (VWNExcCor.h:134-312, LSDA) with ExcCorBase::f / df (ExcCorBase.h:14-26).  Expressions are written in the
@@ -10,6 +10,7 @@
 #include <algorithm>
 #include <cmath>
 
+#include "gga.h"
 #include "internal.h"
 #include "xc.h"
 
@@ -133,6 +134,35 @@ __global__ void k_chachiyo_lda(const double* __restrict__ n, size_t sz, double* 
     }
 }
 
+// Slater exchange + Perdew-Wang 1992 correlation (gga.h, the same G(rs) as the PBE kernel).  Outputs as k_vwn_lda / k_vwn_lsda:
+// LDA Vexc = v, eexc = eps_xc - v; LSDA res = (v_a rho_a + v_b rho_b) / rho, v_a, v_b, eexc = eps_xc - res.
+__global__ void k_pw92_lda(const double* __restrict__ n, size_t sz, double* __restrict__ vexc, double* __restrict__ eexc)
+{
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < sz; i += (size_t)gridDim.x * blockDim.x) {
+        const double rho = n[i];
+        const dfta_gga::XcPoint p = dfta_gga::xc_point<false, false>(rho, 0., 0., 0., 0.);
+        const bool on = !(rho < dfta_gga::kThreshold) && rho == rho;
+        if (vexc) vexc[i] = p.da;
+        if (eexc) eexc[i] = on ? p.e / rho - p.da : 0.;
+    }
+}
+
+__global__ void k_pw92_lsda(const double* __restrict__ na, const double* __restrict__ nb, size_t sz, double* __restrict__ res,
+                            double* __restrict__ va, double* __restrict__ vb, double* __restrict__ eexc)
+{
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < sz; i += (size_t)gridDim.x * blockDim.x) {
+        const double up = na[i], dn = nb[i];
+        const double tot = up + dn;
+        const dfta_gga::XcPoint p = dfta_gga::xc_point<true, false>(up, dn, 0., 0., 0.);
+        const bool on = !(tot < dfta_gga::kThreshold) && tot == tot;
+        const double mean = on ? (p.da * up + p.db * dn) / tot : 0.;
+        if (res) res[i] = mean;
+        if (va) va[i] = p.da;
+        if (vb) vb[i] = p.db;
+        if (eexc) eexc[i] = on ? p.e / tot - mean : 0.;
+    }
+}
+
 }  // namespace
 
 // the two irrational constants are evaluated once on the host with libm, as the reference does (VWNExcCor.h:75,139-140)
@@ -162,6 +192,23 @@ int dfta_launch_vwn_lsda(dfta_ctx* ctx, const double* dNa, const double* dNb, si
 {
     const int blocks = (int)std::min<size_t>((sz + 255) / 256, 2048);
     hipLaunchKernelGGL(k_vwn_lsda, dim3(blocks), dim3(256), 0, ctx->stream, dNa, dNb, sz, dRes, dVa, dVb, dEexc, host_X1(), host_X2());
+    DFTA_CHECK_LAUNCH(ctx);
+    return DFTA_OK;
+}
+
+int dfta_launch_pw92_lda(dfta_ctx* ctx, const double* dN, size_t sz, double* dVexc, double* dEexc)
+{
+    const int blocks = (int)std::min<size_t>((sz + 255) / 256, 2048);
+    hipLaunchKernelGGL(k_pw92_lda, dim3(blocks), dim3(256), 0, ctx->stream, dN, sz, dVexc, dEexc);
+    DFTA_CHECK_LAUNCH(ctx);
+    return DFTA_OK;
+}
+
+int dfta_launch_pw92_lsda(dfta_ctx* ctx, const double* dNa, const double* dNb, size_t sz, double* dRes, double* dVa, double* dVb,
+                          double* dEexc)
+{
+    const int blocks = (int)std::min<size_t>((sz + 255) / 256, 2048);
+    hipLaunchKernelGGL(k_pw92_lsda, dim3(blocks), dim3(256), 0, ctx->stream, dNa, dNb, sz, dRes, dVa, dVb, dEexc);
     DFTA_CHECK_LAUNCH(ctx);
     return DFTA_OK;
 }

@@ -30,6 +30,8 @@ def main():
     ap.add_argument("--out", default="")
     ap.add_argument("--partition", choices=("model", "work"), default="model",
                     help="model: balance the predicted shard times (critical path + work, dftatom_amd.sweep); work: LPT on subshells x steps")
+    ap.add_argument("--xc", choices=("vwn", "pw92", "pbe"), default="vwn",
+                    help="exchange-correlation functional: VWN (the reference's), Slater + PW92, or the PBE GGA (logarithmic grid)")
     ap.add_argument("--sweeps", choices=("exact", "tolerance"), default="exact", help="tolerance: the scan sweeps (DFTA_SWEEPS_TOLERANCE)")
     ap.add_argument("--poisson", choices=("exact", "tolerance", "adaptive"), default="exact",
                     help="tolerance: the multigrid's tolerance mode; adaptive: that, and the V-cycles stop at the round-off floor")
@@ -63,7 +65,8 @@ def main():
     Zs = list(range(args.zmin, args.zmax + 1))
     cost = sweep.atom_cost if args.partition == "work" else None
     modes = dict(sweep_mode=D.SWEEPS_TOLERANCE if args.sweeps == "tolerance" else D.SWEEPS_EXACT,
-                 poisson_mode={"tolerance": D.POISSON_TOLERANCE, "adaptive": D.POISSON_ADAPTIVE}.get(args.poisson, D.POISSON_EXACT))
+                 poisson_mode={"tolerance": D.POISSON_TOLERANCE, "adaptive": D.POISSON_ADAPTIVE}.get(args.poisson, D.POISSON_EXACT),
+                 functional={"vwn": D.XC_VWN, "pw92": D.XC_PW92, "pbe": D.XC_PBE}[args.xc])
     model = "tolerance" if args.sweeps == "tolerance" else "exact"
     if cost is None and model != "exact":
         cost_model = model

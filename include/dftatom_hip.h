@@ -271,6 +271,24 @@ int dfta_vwn_lsda(dfta_ctx* ctx, const double* na, const double* nb, size_t sz,
  * call site commented out (DFTAtom.cpp:383,412,421). */
 int dfta_chachiyo_lda(dfta_ctx* ctx, int improved, const double* n, size_t sz, double* vexc, double* eexcdif);
 
+/* ---- PW92 and PBE (beyond the reference, which has LDA only) ------------------------------------------------
+ * DFTA_XC_PW92: Slater exchange + Perdew-Wang 1992 correlation (constants of the PBE reference code, libxc lda_c_pw_mod).
+ * DFTA_XC_PBE: Perdew-Burke-Ernzerhof 1996 exchange and correlation on top of PW92; the spin-polarised exchange follows the
+ * spin-scaling relation E_x[a, b] = (E_x[2a] + E_x[2b]) / 2.  Densities per volume, sigma_xy = grad rho_x . grad rho_y.  A total
+ * density below 1e-18 (the VWN threshold, VWNExcCor.h:82) gives zeros; a spin channel below it has no exchange and pins zeta to +-1.
+ * Host pointers; both record the kernel time for dfta_ctx_last_kernel_ms. */
+/* pointwise e (per volume) and its partial derivatives; nb == NULL: unpolarised (n = na, sigma = saa; dnb, dsab, dsbb not written);
+   functional: DFTA_XC_PW92 (sigma ignored, d/dsigma = 0) or DFTA_XC_PBE */
+int dfta_xc_pointwise(dfta_ctx* ctx, int functional, size_t sz, const double* na, const double* nb,
+                      const double* saa, const double* sab, const double* sbb,
+                      double* e, double* dna, double* dnb, double* dsaa, double* dsab, double* dsbb);
+/* the SCF's evaluation on a grid for natoms x N densities (atom-major); nb == NULL: LDA outputs (res = Vexc, va / vb not written).
+ * PBE: rho' by 5-point central differences in the grid index over dr/di (second-order one-sided at nodes 0, 1, N-2, N-1),
+ * v = de/drho - (dF/dr + 2F/r) with the flux F_a = 2 e_saa rho_a' + e_sab rho_b'; node 0 is 0.  Logarithmic grids only for PBE.
+ * Outputs as the VWN pair: LDA Vexc = v, eexc = e/rho - v; LSDA res = (v_a rho_a + v_b rho_b)/rho, va, vb, eexc = e/rho - res. */
+int dfta_xc_radial(dfta_ctx* ctx, const dfta_grid* g, int functional, int natoms, const double* na, const double* nb,
+                   double* res, double* va, double* vb, double* eexc);
+
 /* ---- quadrature --------------------------------------------------------------------------------------------
  * Integral::{Trapezoid,SimpsonOneThird,Simpson38,Boole,Romberg} (Integral.h:11-155); values: host. */
 #define DFTA_INT_TRAPEZOID 0
@@ -320,6 +338,8 @@ int  dfta_scf_create(dfta_ctx* ctx, const dfta_grid* g, int lsda, int natoms, co
 #define DFTA_XC_VWN               0   /* VWNExchCor (live in the reference)                                  */
 #define DFTA_XC_CHACHIYO          1   /* ChachiyoExchCor<ChachiyoExchCorParam>, LDA only (ExcCor.h)           */
 #define DFTA_XC_CHACHIYO_IMPROVED 2   /* ChachiyoExchCor<ChachiyoExchCorImprovedParam> (DFTAtom.cpp:383)      */
+#define DFTA_XC_PW92              3   /* Slater exchange + PW92 correlation, LDA and LSDA, both grids (not in the reference) */
+#define DFTA_XC_PBE               4   /* PBE GGA, LDA and LSDA, logarithmic grid only (not in the reference)  */
 typedef struct dfta_scf_options {
     int struct_size;  /* sizeof(dfta_scf_options) of the CALLER's header: members beyond it keep their defaults, a value that is no valid
                          size of this struct (0, or what an older header had in this place) is rejected with DFTA_ERR_INVALID          */
@@ -332,7 +352,7 @@ typedef struct dfta_scf_options {
 /* The option and statistics structs start with struct_size (since version 6) and grow at the END between versions of this header:
  * zero-initialise them, set struct_size = sizeof(...) -- every other member's 0 is the reference's behaviour -- and the library reads /
  * writes no more than the caller's struct holds.  dfta_abi_version() returns the DFTA_ABI_VERSION the library was built with. */
-#define DFTA_ABI_VERSION 6
+#define DFTA_ABI_VERSION 7
 int  dfta_abi_version(void);
 int  dfta_scf_create_ex(dfta_ctx* ctx, const dfta_grid* g, int lsda, int natoms, const int* Z, double alpha, int levels_mode,
                         int tree_depth, const dfta_scf_options* options, dfta_scf** out);
