@@ -137,6 +137,12 @@ SIGNATURES = {
     "dfta_ctx_measure_hbm": (C.c_int, [vp, C.c_size_t, C.c_int, c_dp, c_dp]),
     "dfta_poisson_create_ex": (C.c_int, [vp, vp, C.c_int, C.c_int, C.POINTER(vp)]),
     "dfta_poisson_mode": (C.c_int, [vp]),
+    "dfta_config_parse": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_int, c_ip, c_ip, c_ip, c_ip, c_dp, c_ip, c_ip, c_dp]),
+    "dfta_ion_config": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_ip, c_ip, c_ip, c_ip, c_dp, c_ip, c_ip, c_dp]),
+    "dfta_config_last_error": (C.c_char_p, []),
+    "dfta_scf_create_config": (C.c_int, [vp, vp, C.c_int, C.c_int, c_ip, c_ip, c_ip, c_ip, c_dp, C.c_double, C.c_int, C.c_int, vp,
+                                         C.POINTER(vp)]),
+    "dfta_scf_get_occupations": (C.c_int, [vp, C.c_int, C.c_int, c_dp]),
 }
 
 _lib = None
@@ -176,6 +182,39 @@ def _i32(a):
 
 def _f64(a):
     return np.ascontiguousarray(a, dtype=np.float64)
+
+
+_CONFIG_CAP = 32
+
+
+def _config_call(fn, *head):
+    nA, nB = C.c_int(), C.c_int()
+    an, al, bn, bl = (np.zeros(_CONFIG_CAP, np.int32) for _ in range(4))
+    ao, bo = np.zeros(_CONFIG_CAP), np.zeros(_CONFIG_CAP)
+    rc = fn(*head, _CONFIG_CAP, C.byref(nA), C.byref(nB), _ip(an), _ip(al), _dp(ao), _ip(bn), _ip(bl), _dp(bo))
+    if rc != OK:
+        raise DftaError("invalid electron configuration: %s" % load().dfta_config_last_error().decode())
+    return {"alpha": [(int(an[k]), int(al[k]), float(ao[k])) for k in range(nA.value)],
+            "beta": [(int(bn[k]), int(bl[k]), float(bo[k])) for k in range(nB.value)]}
+
+
+def parse_config(Z, text, lsda=False, aufbau=AUFBAU_REFERENCE):
+    """dfta_config_parse: '[Ne] 3s2 3p5.5', '1s2 2s1 2p3/1' (LSDA split) ... -> {"alpha": [(n, l, occ), ...], "beta": [...]}
+    (LDA: every level under "alpha"), sorted by (n, l); n as get_subshells counts it (principal quantum number - 1).  Raises DftaError with the reason on an invalid configuration."""
+    lib = load()
+    return _config_call(lib.dfta_config_parse, int(Z), int(bool(lsda)), int(aufbau), text.encode())
+
+
+def ion_config(Z, charge, lsda=False, aufbau=AUFBAU_REFERENCE):
+    """dfta_ion_config: the Aufbau configuration of Z with `charge` electrons removed from the outermost subshell(s)
+    (highest n, then highest l: Fe+ = 3d6 4s1), split by spin as the default path splits it."""
+    lib = load()
+    return _config_call(lib.dfta_ion_config, int(Z), int(charge), int(bool(lsda)), int(aufbau))
+
+
+def config_electrons(cfg):
+    """electron count of a configuration returned by parse_config / ion_config"""
+    return sum(o for _, _, o in cfg["alpha"]) + sum(o for _, _, o in cfg["beta"])
 
 
 class Context:
@@ -512,15 +551,45 @@ class Scf:
     """Device-resident SCF state of a batch of atoms (dfta_scf): the body of CalculateNonUniformLDA/LSDA."""
 
     def __init__(self, ctx, grid, Z, lsda=False, alpha=0.5, levels_mode=LEVELS_BATCHED, tree_depth=0, integrator=INT_SIMPSON38,
-                 functional=XC_VWN, aufbau=AUFBAU_REFERENCE, poisson_mode=POISSON_DEFAULT, sweep_mode=SWEEPS_EXACT):
+                 functional=XC_VWN, aufbau=AUFBAU_REFERENCE, poisson_mode=POISSON_DEFAULT, sweep_mode=SWEEPS_EXACT, config=None,
+                 charge=None):
+        """config: an electron configuration (parse_config's text, or its result) for every atom, or a list of them, one per atom;
+        charge: an int for every atom, or a list of ints (ion_config: cations).  Neither: the Aufbau configuration of each Z.
+        The nuclear charge stays Z; the electron count sets the start density and the Poisson boundary U(Rmax)."""
         self.ctx, self.grid = ctx, grid
         self.Z = _i32(np.atleast_1d(Z))
         self.natoms = len(self.Z)
         self.lsda = bool(lsda)
         h = vp()
         opt = ScfOptions(C.sizeof(ScfOptions), integrator, functional, aufbau, poisson_mode, sweep_mode)
-        ctx.check(ctx.lib.dfta_scf_create_ex(ctx.h, grid.h, int(self.lsda), self.natoms, _ip(self.Z), alpha, levels_mode,
-                                             tree_depth, C.cast(C.byref(opt), vp), C.byref(h)))
+        if config is not None and charge is not None:
+            raise ValueError("give config or charge, not both")
+        self.configs = None
+        if config is not None or charge is not None:
+            per = config if config is not None else charge
+            if isinstance(per, (str, dict)) or np.ndim(per) == 0:
+                per = [per] * self.natoms
+            if len(per) != self.natoms:
+                raise ValueError("%d configurations for %d atoms" % (len(per), self.natoms))
+            cfgs = []
+            for z, c in zip(self.Z, per):
+                if isinstance(c, dict):
+                    cfgs.append(c)
+                elif config is not None:
+                    cfgs.append(parse_config(int(z), c, self.lsda, aufbau))
+                else:
+                    cfgs.append(ion_config(int(z), int(c), self.lsda, aufbau))
+            self.configs = cfgs
+            nlev = _i32([[len(c["alpha"]), len(c["beta"])] for c in cfgs]).reshape(-1)
+            flat = [lv for c in cfgs for lv in c["alpha"] + c["beta"]]
+            n = _i32([lv[0] for lv in flat])
+            l = _i32([lv[1] for lv in flat])
+            occ = _f64([lv[2] for lv in flat])
+            ctx.check(ctx.lib.dfta_scf_create_config(ctx.h, grid.h, int(self.lsda), self.natoms, _ip(self.Z), _ip(nlev), _ip(n), _ip(l),
+                                                     _dp(occ), alpha, levels_mode, tree_depth, C.cast(C.byref(opt), vp), C.byref(h)))
+        else:
+            ctx.check(ctx.lib.dfta_scf_create_ex(ctx.h, grid.h, int(self.lsda), self.natoms, _ip(self.Z), alpha, levels_mode,
+                                                 tree_depth, C.cast(C.byref(opt), vp), C.byref(h)))
         self.h = h
         d, nj, tr = C.c_int(), C.c_int(), C.c_long()
         ctx.check(ctx.lib.dfta_scf_info(h, C.byref(d), C.byref(nj), C.byref(tr)))
@@ -541,14 +610,19 @@ class Scf:
     def levels(self, atom=0, spin=0):
         cnt = self.ctx.lib.dfta_scf_num_levels(self.h, atom, spin)
         n, l, occ, conv = (np.zeros(max(cnt, 1), np.int32) for _ in range(4))
-        E = np.zeros(max(cnt, 1))
+        E, occupation = np.zeros(max(cnt, 1)), np.zeros(max(cnt, 1))
         if cnt > 0:
-            self.ctx.check(self.ctx.lib.dfta_scf_get_levels(self.h, atom, spin, _ip(n), _ip(l), _ip(occ), _dp(E), _ip(conv)))
+            self.ctx.check(self.ctx.lib.dfta_scf_get_occupations(self.h, atom, spin, _dp(occupation)))
+            integral = bool(np.all(occupation[:cnt] == np.floor(occupation[:cnt])))
+            self.ctx.check(self.ctx.lib.dfta_scf_get_levels(self.h, atom, spin, _ip(n), _ip(l), _ip(occ) if integral else None, _dp(E),
+                                                            _ip(conv)))
+            if not integral:
+                occ = None              # a fractional occupation: the int getter has no value for it, see "occupation"
         status, nc, nz = (np.zeros(max(cnt, 1), np.int32) for _ in range(3))
         if cnt > 0:
             self.ctx.check(self.ctx.lib.dfta_scf_get_level_status(self.h, atom, spin, _ip(status), _ip(nc), _ip(nz)))
-        return {"n": n[:cnt], "l": l[:cnt], "occ": occ[:cnt], "E": E[:cnt], "converged": conv[:cnt], "status": status[:cnt],
-                "n_count": nc[:cnt], "n_zero": nz[:cnt]}
+        return {"n": n[:cnt], "l": l[:cnt], "occ": None if occ is None else occ[:cnt], "occupation": occupation[:cnt], "E": E[:cnt],
+                "converged": conv[:cnt], "status": status[:cnt], "n_count": nc[:cnt], "n_zero": nz[:cnt]}
 
     def array(self, which, atom=0):
         out = np.zeros(self.grid.N)

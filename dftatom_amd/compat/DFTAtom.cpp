@@ -15,21 +15,47 @@ int DFTAtom::levelsMode = DFTA_LEVELS_BATCHED;
 int DFTAtom::integrator = DFTA_INT_SIMPSON38;
 int DFTAtom::sweepMode = DFTA_SWEEPS_EXACT;
 int DFTAtom::functional = DFTA_XC_VWN;
+int DFTAtom::charge = 0;
+std::string DFTAtom::config;
 int DFTAtom::poissonMode = -1;      // as dfta_poisson_create: exact unless $DFTA_DEBUG POISSON_MODE (--poisson= overrides)
 std::ostream* DFTAtom::jsonOut = nullptr;
 
 namespace {
-struct LevelLine { int n, l, occ; double E; int status, n_count, n_zero; };
+struct LevelLine { int n, l; double occ, E; int status, n_count, n_zero; };
+
+// DFTAtom::charge / config as the flat arrays of dfta_scf_create_config (one atom)
+int build_configuration(int Z, bool lsda, std::vector<int>& nlev, std::vector<int>& n, std::vector<int>& l, std::vector<double>& occ)
+{
+    const int cap = 32;
+    int nA = 0, nB = 0, an[cap], al[cap], bn[cap], bl[cap];
+    double ao[cap], bo[cap];
+    const int rc = DFTAtom::config.empty()
+                       ? dfta_ion_config(Z, DFTAtom::charge, lsda ? 1 : 0, DFTA_AUFBAU_REFERENCE, cap, &nA, &nB, an, al, ao, bn, bl, bo)
+                       : dfta_config_parse(Z, lsda ? 1 : 0, DFTA_AUFBAU_REFERENCE, DFTAtom::config.c_str(), cap, &nA, &nB, an, al, ao, bn, bl, bo);
+    if (rc != DFTA_OK) return rc;
+    nlev = {nA, nB};
+    n.assign(an, an + nA); l.assign(al, al + nA); occ.assign(ao, ao + nA);
+    n.insert(n.end(), bn, bn + nB); l.insert(l.end(), bl, bl + nB); occ.insert(occ.end(), bo, bo + nB);
+    return DFTA_OK;
+}
+
+// an occupation as the reference prints its integers; a fractional one with its decimals
+void print_occupation(std::ostream& os, double occ)
+{
+    if (occ == static_cast<double>(static_cast<long>(occ))) os << static_cast<long>(occ);
+    else os << std::defaultfloat << std::setprecision(6) << occ << std::fixed;
+}
 
 std::vector<LevelLine> fetch_levels(dfta_scf* scf, int spin)
 {
     const int cnt = dfta_scf_num_levels(scf, 0, spin);
-    std::vector<int> n(cnt), l(cnt), occ(cnt), conv(cnt);
-    std::vector<double> E(cnt);
+    std::vector<int> n(cnt), l(cnt), conv(cnt);
+    std::vector<double> E(cnt), occ(cnt);
     std::vector<LevelLine> out;
     if (cnt <= 0) return out;
     std::vector<int> st(cnt), nc(cnt), nz(cnt);
-    if (dfta_scf_get_levels(scf, 0, spin, n.data(), l.data(), occ.data(), E.data(), conv.data()) != DFTA_OK) throw std::runtime_error("dfta_scf_get_levels");
+    if (dfta_scf_get_levels(scf, 0, spin, n.data(), l.data(), nullptr, E.data(), conv.data()) != DFTA_OK) throw std::runtime_error("dfta_scf_get_levels");
+    if (dfta_scf_get_occupations(scf, 0, spin, occ.data()) != DFTA_OK) throw std::runtime_error("dfta_scf_get_occupations");
     if (dfta_scf_get_level_status(scf, 0, spin, st.data(), nc.data(), nz.data()) != DFTA_OK) throw std::runtime_error("dfta_scf_get_level_status");
     for (int i = 0; i < cnt; ++i) out.push_back({n[i], l[i], occ[i], E[i], st[i], nc[i], nz[i]});
     return out;
@@ -58,7 +84,11 @@ void print_configuration(std::vector<LevelLine> levels)
 {
     // levels sorted by energy for the final configuration line (DFTAtom.cpp:487-490)
     std::sort(levels.begin(), levels.end(), [](const LevelLine& a, const LevelLine& b) { return a.E < b.E; });
-    for (const auto& lv : levels) std::cout << lv.n + 1 << DFTAtom::orb[lv.l] << lv.occ << " ";
+    for (const auto& lv : levels) {
+        std::cout << lv.n + 1 << DFTAtom::orb[lv.l];
+        print_occupation(std::cout, lv.occ);
+        std::cout << " ";
+    }
 }
 }  // namespace
 
@@ -76,7 +106,16 @@ void DFTAtom::Run(bool lsda, bool uniform, int Z, int MultigridLevels, double al
     opt.struct_size = (int)sizeof(opt);
     opt.integrator = integrator; opt.functional = functional; opt.aufbau = DFTA_AUFBAU_REFERENCE;
     opt.poisson_mode = poissonMode; opt.sweep_mode = sweepMode;
-    dfta_compat::check(dfta_scf_create_ex(rt.ctx(), grid, lsda ? 1 : 0, 1, &Z, alpha, levelsMode, 0, &opt, &scf), rt.ctx(), "dfta_scf_create");
+    if (charge == 0 && config.empty()) {
+        dfta_compat::check(dfta_scf_create_ex(rt.ctx(), grid, lsda ? 1 : 0, 1, &Z, alpha, levelsMode, 0, &opt, &scf), rt.ctx(), "dfta_scf_create");
+    } else {
+        std::vector<int> nlev, n, l;
+        std::vector<double> occ;
+        if (build_configuration(Z, lsda, nlev, n, l, occ) != DFTA_OK)
+            throw std::invalid_argument(std::string("electron configuration: ") + dfta_config_last_error());
+        dfta_compat::check(dfta_scf_create_config(rt.ctx(), grid, lsda ? 1 : 0, 1, &Z, nlev.data(), n.data(), l.data(), occ.data(), alpha, levelsMode, 0,
+                                                  &opt, &scf), rt.ctx(), "dfta_scf_create_config");
+    }
     const int maxSteps = lsda ? 150 : 100;                                  // DFTAtom.cpp:396 / 908
     for (int sp = 0; sp < maxSteps; ++sp) {
         std::cout << "Step: " << sp << std::endl;
@@ -110,6 +149,14 @@ void DFTAtom::Run(bool lsda, bool uniform, int Z, int MultigridLevels, double al
         print_configuration(fetch_levels(scf, 1));
     }
     dfta_scf_destroy(scf);
+}
+
+const char* DFTAtom::CheckConfiguration(int Z, bool lsda)
+{
+    if (charge == 0 && config.empty()) return nullptr;
+    std::vector<int> nlev, n, l;
+    std::vector<double> occ;
+    return build_configuration(Z, lsda, nlev, n, l, occ) == DFTA_OK ? nullptr : dfta_config_last_error();
 }
 
 void DFTAtom::CalculateNonUniformLDA(int Z, int MultigridLevels, double alpha, double MaxR, double deltaGrid) { Run(false, false, Z, MultigridLevels, alpha, MaxR, deltaGrid); }

@@ -10,6 +10,7 @@
 #pragma once
 
 #include <iosfwd>
+#include <string>
 #include <vector>
 
 #include "AufbauPrinciple.h"
@@ -32,6 +33,12 @@ public:
     static int sweepMode;       // DFTA_SWEEPS_EXACT (default) / DFTA_SWEEPS_TOLERANCE (transfer-matrix scans; logarithmic grids of 12 .. 20 levels)
     static int poissonMode;     // -1 (default): as dfta_poisson_create, i.e. exact unless $DFTA_DEBUG POISSON_MODE says otherwise; DFTA_POISSON_EXACT / _TOLERANCE / _ADAPTIVE
     static int functional;      // DFTA_XC_VWN (default: what the reference runs), _CHACHIYO, _CHACHIYO_IMPROVED (LDA only), _PW92, _PBE (logarithmic grid)
+    // electron configuration (not in the reference, which runs the neutral Aufbau atom): charge q > 0 runs the cation of dfta_ion_config,
+    // a non-empty config the text of dfta_config_parse ("[Ne] 3s2 3p5.5", "2p3/1" LSDA splits); both unset (default): the Aufbau atom
+    static int charge;
+    static std::string config;
+    // nullptr if charge / config describe a valid configuration of Z (LDA or LSDA), else the reason (dfta_config_last_error)
+    static const char* CheckConfiguration(int Z, bool lsda);
     // per-step machine-readable output (metrics): when set, every SCF step appends ONE JSON line with 17-digit
     // energies and eigenvalues, per-level status bits (DFTA_LEVEL_*) and sweep counts, rounds, V-cycles and the phases' HIP-event times
     static std::ostream* jsonOut;

@@ -14,6 +14,9 @@
 //                phase times) to FILE, or to stderr -- the console protocol on stdout stays the reference's.
 // --sweeps=exact|tolerance, --poisson=exact|tolerance|adaptive: the opt-in tolerance modes of the device path (include/dftatom_hip.h).
 // --xc=vwn (default, what the reference runs) | chachiyo | chachiyo-improved (LDA only) | pw92 | pbe (logarithmic grid only).
+// --charge=q: the cation X^q+ (electrons leave the subshell of highest n, then highest l: Fe+ = [Ar] 3d6 4s1);
+// --config="[Ne] 3s2 3p5.5": an explicit, possibly fractional configuration ("2p3/1": LSDA alpha / beta split).  An invalid
+// configuration exits with code 2 before anything runs.
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
@@ -93,6 +96,14 @@ int main(int argc, char** argv)
             for (int k = 0; k < 5; ++k) if (n == names[k]) f = k;
             if (f < 0) { std::cerr << "unknown functional " << n << std::endl; bad = true; }
             else DFT::DFTAtom::functional = f;
+        } else if (a.rfind("--charge=", 0) == 0) {
+            char* end = nullptr;
+            const long q = std::strtol(a.c_str() + 9, &end, 10);
+            if (end == a.c_str() + 9 || *end) { std::cerr << "bad charge " << a.substr(9) << std::endl; return 2; }
+            DFT::DFTAtom::charge = static_cast<int>(q);
+        } else if (a.rfind("--config=", 0) == 0) {
+            DFT::DFTAtom::config = a.substr(9);
+            if (DFT::DFTAtom::config.empty()) { std::cerr << "empty --config" << std::endl; return 2; }
         } else if (a.rfind("--integrator=", 0) == 0) {
             const std::string n = a.substr(13);
             const char* names[] = {"trapezoid", "simpson13", "simpson38", "boole", "romberg"};
@@ -114,12 +125,16 @@ int main(int argc, char** argv)
     }
     if (!have || bad) {
         std::cerr << "usage: " << argv[0] << " Z MultigridLevels alpha MaxR deltaGrid method(0 LDA, 1 LSDA, 2 uniform LDA, 3 uniform LSDA) [chained] [--integrator=NAME] [--xc=NAME]\n"
-                  << "       " << argv[0] << " --ini DFTAtom.ini [--uniform] [chained] [--integrator=NAME] [--xc=NAME]\n"
-                  << "       --xc=vwn (default) | chachiyo | chachiyo-improved | pw92 | pbe\n";
+                  << "           [--charge=q | --config=\"[Ne] 3s2 3p5.5\"]\n"
+                  << "       " << argv[0] << " --ini DFTAtom.ini [--uniform] [chained] [--integrator=NAME] [--xc=NAME] [--charge=q | --config=TEXT]\n"
+                  << "       --xc=vwn (default) | chachiyo | chachiyo-improved | pw92 | pbe\n"
+                  << "       --charge=q: the cation (q > 0); --config: an electron configuration, fractional occupations allowed\n";
         return 2;
     }
     if (o.method == 2 || o.method == 3) { uniform = true; o.method -= 2; }
     if (const char* msg = validate(o, uniform)) { std::cerr << "error: " << msg << std::endl; return 2; }
+    if (DFT::DFTAtom::charge != 0 && !DFT::DFTAtom::config.empty()) { std::cerr << "error: give --charge or --config, not both" << std::endl; return 2; }
+    if (const char* msg = DFT::DFTAtom::CheckConfiguration(o.Z, o.method != 0)) { std::cerr << "error: electron configuration: " << msg << std::endl; return 2; }
     try {
         if (uniform) {
             if (o.method) DFT::DFTAtom::CalculateUniformLSDA(o.Z, o.MultigridLevels, o.alpha, o.MaxR);

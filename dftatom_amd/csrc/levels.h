@@ -7,7 +7,9 @@
 
 namespace dfta {
 
-struct JobSpec { int v, n, l, occ; };
+// occ: the level's integer occupation as the reference's records hold it (Job::occ); docc: the occupation the density and the
+// electronic energy are summed with -- (double)occ for an Aufbau configuration, a fractional one for dfta_scf_create_config
+struct JobSpec { int v, n, l, occ; double docc; };
 
 // state of one (potential, level) eigenvalue search; lives in device memory
 struct Job {
@@ -105,6 +107,8 @@ struct LevelSolver {
     int debug_rounds = 0;          // $DFTA_DEBUG_ROUNDS, read once in setup()
     int integ_rule = DFTA_INT_SIMPSON38;   // quadrature of the normalisation integral (the reference calls Simpson38: DFTAtom.cpp:27,51)
     Job* d_jobs = nullptr;
+    std::vector<double> h_occ;     // per job: JobSpec::docc (Job keeps its int occ: persist.inc / own.inc copy Job as 8-byte words)
+    double* d_occ = nullptr;
     int *d_chain_off = nullptr, *d_chain_off_b = nullptr, *d_v_off = nullptr, *d_slot_v = nullptr, *d_slot_l = nullptr;
     double2* d_tab = nullptr;
     double *d_E = nullptr, *d_us = nullptr, *d_us1 = nullptr, *d_u0 = nullptr, *d_phi = nullptr;

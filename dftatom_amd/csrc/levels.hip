@@ -460,8 +460,9 @@ __global__ __launch_bounds__(kNormThreads) void k_normalize(double* __restrict__
     for (int i = threadIdx.x; i < N; i += kNormThreads) P[i] *= unorm;
 }
 
-// newDensity[v][i] += occ * Psi[i] * Psi[i] for i < N-1, levels of a potential in their order (DFTAtom.cpp:558-559)
-__global__ void k_accumulate_density(const double* __restrict__ Psi, const dfta::Job* __restrict__ jobs,
+// newDensity[v][i] += occ * Psi[i] * Psi[i] for i < N-1, levels of a potential in their order (DFTAtom.cpp:558-559); occ: per job,
+// (double)Job::occ for an Aufbau configuration (the same product as the int operand converted), fractional ones beside it
+__global__ void k_accumulate_density(const double* __restrict__ Psi, const double* __restrict__ occ,
                                      const int* __restrict__ v_off, int N, double* __restrict__ newDensity)
 {
     const int v = blockIdx.y;
@@ -470,7 +471,7 @@ __global__ void k_accumulate_density(const double* __restrict__ Psi, const dfta:
         if (i < N - 1)
             for (int k = v_off[v]; k < v_off[v + 1]; ++k) {
                 const double p = Psi[(size_t)k * N + i];
-                acc += jobs[k].occ * p * p;
+                acc += occ[k] * p * p;
             }
         newDensity[(size_t)v * N + i] = acc;
     }
@@ -618,7 +619,7 @@ LevelSolver::~LevelSolver() { release(); }
 
 void LevelSolver::release()
 {
-    void* ptrs[] = {d_jobs, d_chain_off, d_chain_off_b, d_v_off, d_slot_v, d_slot_l, d_tab, d_E, d_limit, d_start, d_us, d_us1, d_count,
+    void* ptrs[] = {d_jobs, d_occ, d_chain_off, d_chain_off_b, d_v_off, d_slot_v, d_slot_l, d_tab, d_E, d_limit, d_start, d_us, d_us1, d_count,
                     d_u0, d_phi, d_istop, d_trip, d_wave_job, d_wave_kind, d_wave_slot, d_wave_first, d_wave_cnt, d_counters, d_Psi, d_Q, d_jE, d_jslot, d_jl,
                     d_jstart, d_jus, d_jus1, d_jmp, d_slot_min, d_bounds};
     for (void* p : ptrs) if (p) (void)hipFree(p);
@@ -643,7 +644,7 @@ void LevelSolver::release()
     for (void* q : {(void*)d_snapE, (void*)d_snapReady, (void*)d_jtake}) if (q) (void)hipFree(q);
     d_snapE = nullptr; d_snapReady = nullptr; d_jtake = nullptr;
     for (hipEvent_t& e : ev) if (e) { (void)hipEventDestroy(e); e = nullptr; }
-    d_jobs = nullptr; d_chain_off = nullptr; d_chain_off_b = nullptr; d_v_off = nullptr; d_slot_v = nullptr; d_slot_l = nullptr; d_tab = nullptr;
+    d_jobs = nullptr; d_occ = nullptr; d_chain_off = nullptr; d_chain_off_b = nullptr; d_v_off = nullptr; d_slot_v = nullptr; d_slot_l = nullptr; d_tab = nullptr;
     d_E = nullptr; d_limit = nullptr; d_start = nullptr; d_us = nullptr; d_us1 = nullptr; d_count = nullptr; d_u0 = nullptr; d_phi = nullptr; d_istop = nullptr; d_trip = nullptr;
     d_wave_kind = nullptr; d_wave_slot = nullptr; d_wave_first = nullptr; d_wave_cnt = nullptr; d_counters = nullptr; d_wave_job = nullptr;
     d_Psi = nullptr; d_Q = nullptr; d_jE = nullptr; d_jslot = nullptr; d_jl = nullptr; d_jstart = nullptr; d_jus = nullptr;
@@ -799,6 +800,9 @@ int LevelSolver::setup(dfta_ctx* c, const dfta_grid* grid, int mode_, int tree_d
 #define ALLOC(ptr, type, count) DFTA_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&ptr), sizeof(type) * (size_t)(count)))
 #define UPLOAD(ptr, vec) DFTA_HIP(ctx, hipMemcpyAsync(ptr, vec.data(), sizeof(vec[0]) * vec.size(), hipMemcpyHostToDevice, st))
     ALLOC(d_jobs, Job, njobs);
+    h_occ.resize(njobs);
+    for (int k = 0; k < njobs; ++k) h_occ[k] = specs[k].docc;
+    ALLOC(d_occ, double, njobs); UPLOAD(d_occ, h_occ);
     ALLOC(d_chain_off, int, chain_off.size()); UPLOAD(d_chain_off, chain_off);
     ALLOC(d_chain_off_b, int, chain_off_b.size()); UPLOAD(d_chain_off_b, chain_off_b);
     ALLOC(d_v_off, int, v_off.size()); UPLOAD(d_v_off, v_off);
@@ -1363,7 +1367,7 @@ int LevelSolver::run(const double* dV, const double* job_bottom, int run_mode, d
         DFTA_CHECK_LAUNCH(ctx);
     }
     if (dNewDensity) {
-        hipLaunchKernelGGL(k_accumulate_density, dim3(std::min(256, (N + 255) / 256), nV), dim3(256), 0, st, d_Psi, d_jobs, d_v_off,
+        hipLaunchKernelGGL(k_accumulate_density, dim3(std::min(256, (N + 255) / 256), nV), dim3(256), 0, st, d_Psi, d_occ, d_v_off,
                            N, dNewDensity);
         DFTA_CHECK_LAUNCH(ctx);
     }
@@ -1411,7 +1415,7 @@ extern "C" int dfta_solve_levels(dfta_ctx* ctx, const dfta_grid* g, int mode, in
     DFTA_REQUIRE(ctx, !scan_sweeps || dfta_scan_supported(g), "the tolerance mode of the sweeps needs a logarithmic grid of 12 .. 20 multigrid levels");
     const int N = g->N;
     std::vector<dfta::JobSpec> specs(nlevels);
-    for (int k = 0; k < nlevels; ++k) specs[k] = {vidx ? vidx[k] : 0, n[k], l[k], occ[k]};
+    for (int k = 0; k < nlevels; ++k) specs[k] = {vidx ? vidx[k] : 0, n[k], l[k], occ[k], static_cast<double>(occ[k])};
     dfta::LevelSolver solver;
     solver.sweep_mode = scan_sweeps ? DFTA_SWEEPS_TOLERANCE : DFTA_SWEEPS_EXACT;
     int rc = solver.setup(ctx, g, mode, tree_depth, nV, specs);
@@ -1440,7 +1444,7 @@ extern "C" int dfta_solve_levels(dfta_ctx* ctx, const dfta_grid* g, int mode, in
         results[k].E = j.E; results[k].top = j.top; results[k].bottom = j.bottom; results[k].n_count = j.n_count;
         results[k].n_zero = j.n_zero; results[k].converged = j.converged; results[k].matchPoint = j.matchPoint;
         results[k].status = j.status;
-        if (Eelectronic) Eelectronic[j.v] += j.occ * j.E;            // DFTAtom.cpp:561
+        if (Eelectronic) Eelectronic[j.v] += solver.h_occ[k] * j.E;  // DFTAtom.cpp:561 (h_occ[k] == (double)j.occ)
         allconv = allconv && j.converged;
     }
     if (newDensity) DFTA_HIP(ctx, hipMemcpyAsync(newDensity, dND.p, sizeof(double) * (size_t)nV * N, hipMemcpyDeviceToHost, st));

@@ -226,12 +226,13 @@ static int degrade(dfta_poisson* p)
     return DFTA_OK;
 }
 
+// dNe (device, per atom): electron count, the outer boundary U(Rmax) of the solve (DFTAtom's Z for a neutral atom)
 // dSkip (device, per atom, may be null): atoms with a non-zero entry are left untouched (frozen atoms of an SCF batch)
-int dfta_poisson_solve_launch(dfta_poisson* p, const int* dZ, const double* dDensity, double* dU, int* dVcycles, double* dErr,
+int dfta_poisson_solve_launch(dfta_poisson* p, const double* dNe, const double* dDensity, double* dU, int* dVcycles, double* dErr,
                               const int* dSkip)
 {
     dfta_ctx* ctx = p->ctx;
-    if (p->degraded) return dfta_poisson_solve_launch(p->fallback, dZ, dDensity, dU, dVcycles, dErr, dSkip);
+    if (p->degraded) return dfta_poisson_solve_launch(p->fallback, dNe, dDensity, dU, dVcycles, dErr, dSkip);
     DFTA_HIP(ctx, hipMemsetAsync(p->d_group_ctr, 0, sizeof(unsigned) * p->batch, ctx->stream));
     DFTA_HIP(ctx, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(p->d_group_part), 0x7FF8DEAD, (size_t)p->batch * group_part_doubles(p->D.G) * 2, ctx->stream));   // group_sum_fast's sentinel
     if (p->resident) {
@@ -240,13 +241,13 @@ int dfta_poisson_solve_launch(dfta_poisson* p, const int* dZ, const double* dDen
         const double *a_r = p->g->d_rsrc, *a_psrc = p->g->d_psrc;
         int fault = p->fault, src_all = p->g->uniform;
         if (p->plain_launch) {
-            hipLaunchKernelGGL(K_SOLVE_RES(p), dim3(p->batch * p->res_wg()), dim3(kThreads), 0, ctx->stream, a0, p->d_phi0, p->d_phi1, p->d_src, dZ,
+            hipLaunchKernelGGL(K_SOLVE_RES(p), dim3(p->batch * p->res_wg()), dim3(kThreads), 0, ctx->stream, a0, p->d_phi0, p->d_phi1, p->d_src, dNe,
                                dDensity, a_r, a_psrc, dU, dVcycles, dErr, p->d_total_vcycles, p->d_group_ctr, p->d_res_slots, dSkip, fault, src_all,
                                p->d_res_spill);
             DFTA_CHECK_LAUNCH(ctx);
             return DFTA_OK;
         }
-        void* args[] = {&a0, &p->d_phi0, &p->d_phi1, &p->d_src, &dZ, &dDensity, &a_r, &a_psrc, &dU, &dVcycles, &dErr, &p->d_total_vcycles,
+        void* args[] = {&a0, &p->d_phi0, &p->d_phi1, &p->d_src, &dNe, &dDensity, &a_r, &a_psrc, &dU, &dVcycles, &dErr, &p->d_total_vcycles,
                         &p->d_group_ctr, &p->d_res_slots, &dSkip, &fault, &src_all, &p->d_res_spill};
         const hipError_t e = hipLaunchCooperativeKernel(reinterpret_cast<const void*>(K_SOLVE_RES(p)), dim3(p->batch * p->res_wg()), dim3(kThreads),
                                                         args, 0, ctx->stream);
@@ -255,19 +256,19 @@ int dfta_poisson_solve_launch(dfta_poisson* p, const int* dZ, const double* dDen
             int rc = degrade(p);
             if (rc) return rc;
             ++p->aborts;
-            return dfta_poisson_solve_launch(p->fallback, dZ, dDensity, dU, dVcycles, dErr, dSkip);
+            return dfta_poisson_solve_launch(p->fallback, dNe, dDensity, dU, dVcycles, dErr, dSkip);
         }
         return DFTA_OK;
     }
     if (p->D.G == 1) {
-        hipLaunchKernelGGL(K_SOLVE(p), dim3(p->batch), dim3(kThreads), 0, ctx->stream, p->d_desc, p->d_phi0, p->d_phi1, p->d_src, dZ,
+        hipLaunchKernelGGL(K_SOLVE(p), dim3(p->batch), dim3(kThreads), 0, ctx->stream, p->d_desc, p->d_phi0, p->d_phi1, p->d_src, dNe,
                            dDensity, p->g->d_rsrc, p->g->d_psrc, dU, dVcycles, dErr, p->d_total_vcycles, p->d_group_ctr, p->d_group_part,
                            dSkip, 0, p->g->uniform);
         DFTA_CHECK_LAUNCH(ctx);
         return DFTA_OK;
     }
     if (p->plain_launch) {           // under a profiler (see poisson_create_impl): same kernel, ordinary launch
-        hipLaunchKernelGGL(K_SOLVE(p), dim3(p->batch * p->D.G), dim3(kThreads), 0, ctx->stream, p->d_desc, p->d_phi0, p->d_phi1, p->d_src, dZ,
+        hipLaunchKernelGGL(K_SOLVE(p), dim3(p->batch * p->D.G), dim3(kThreads), 0, ctx->stream, p->d_desc, p->d_phi0, p->d_phi1, p->d_src, dNe,
                            dDensity, p->g->d_rsrc, p->g->d_psrc, dU, dVcycles, dErr, p->d_total_vcycles, p->d_group_ctr, p->d_group_part,
                            dSkip, p->fault, p->g->uniform);
         DFTA_CHECK_LAUNCH(ctx);
@@ -276,7 +277,7 @@ int dfta_poisson_solve_launch(dfta_poisson* p, const int* dZ, const double* dDen
     const MgDesc* a0 = p->d_desc;
     const double *a_r = p->g->d_rsrc, *a_psrc = p->g->d_psrc;
     int fault = p->fault, src_all = p->g->uniform;
-    void* args[] = {&a0, &p->d_phi0, &p->d_phi1, &p->d_src, &dZ, &dDensity, &a_r, &a_psrc, &dU, &dVcycles, &dErr, &p->d_total_vcycles,
+    void* args[] = {&a0, &p->d_phi0, &p->d_phi1, &p->d_src, &dNe, &dDensity, &a_r, &a_psrc, &dU, &dVcycles, &dErr, &p->d_total_vcycles,
                     &p->d_group_ctr, &p->d_group_part, &dSkip, &fault, &src_all};
     const hipError_t e = hipLaunchCooperativeKernel(reinterpret_cast<const void*>(K_SOLVE(p)), dim3(p->batch * p->D.G), dim3(kThreads),
                                                     args, 0, ctx->stream);
@@ -286,7 +287,7 @@ int dfta_poisson_solve_launch(dfta_poisson* p, const int* dZ, const double* dDen
         int rc = degrade(p);
         if (rc) return rc;
         ++p->aborts;
-        return dfta_poisson_solve_launch(p->fallback, dZ, dDensity, dU, dVcycles, dErr, dSkip);
+        return dfta_poisson_solve_launch(p->fallback, dNe, dDensity, dU, dVcycles, dErr, dSkip);
     }
     return DFTA_OK;
 }
@@ -311,7 +312,7 @@ static int check_groups(dfta_poisson* p)
 
 // Completes the solve launched last (synchronises the stream).  If a group of workgroups gave up, the solve is repeated
 // with one workgroup per atom, in this process and on the same stream, and every later solve of `p` takes that path.
-int dfta_poisson_finish(dfta_poisson* p, const int* dZ, const double* dDensity, double* dU, int* dVcycles, double* dErr,
+int dfta_poisson_finish(dfta_poisson* p, const double* dNe, const double* dDensity, double* dU, int* dVcycles, double* dErr,
                         const int* dSkip)
 {
     dfta_ctx* ctx = p->ctx;
@@ -321,7 +322,7 @@ int dfta_poisson_finish(dfta_poisson* p, const int* dZ, const double* dDensity, 
     DFTA_HIP(ctx, hipMemsetAsync(p->d_total_vcycles, 0, sizeof(unsigned long long), ctx->stream));   // the aborted solve's count
     int rc = degrade(p);
     if (rc) return rc;
-    rc = dfta_poisson_solve_launch(p->fallback, dZ, dDensity, dU, dVcycles, dErr, dSkip);
+    rc = dfta_poisson_solve_launch(p->fallback, dNe, dDensity, dU, dVcycles, dErr, dSkip);
     if (rc) return rc;
     DFTA_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return DFTA_OK;
@@ -652,11 +653,12 @@ int dfta_poisson_solve(dfta_poisson* p, const int* Z, const double* density, dou
     DFTA_REQUIRE(ctx, Z && density && U, "null input");
     const int N = p->g->N, B = p->batch;
     hipStream_t st = ctx->stream;
-    DevBuf<int> dZ, dVc;
-    DevBuf<double> dRho, dU, dErr;
+    DevBuf<int> dVc;
+    DevBuf<double> dZ, dRho, dU, dErr;
+    std::vector<double> ne(Z, Z + B);                    // the outer boundary of a neutral atom: (double)Z
     DFTA_HIP(ctx, dZ.alloc(B)); DFTA_HIP(ctx, dVc.alloc(B)); DFTA_HIP(ctx, dErr.alloc(B));
     DFTA_HIP(ctx, dRho.alloc((size_t)B * N)); DFTA_HIP(ctx, dU.alloc((size_t)B * N));
-    DFTA_HIP(ctx, hipMemcpyAsync(dZ.p, Z, sizeof(int) * B, hipMemcpyHostToDevice, st));
+    DFTA_HIP(ctx, hipMemcpyAsync(dZ.p, ne.data(), sizeof(double) * B, hipMemcpyHostToDevice, st));
     DFTA_HIP(ctx, hipMemcpyAsync(dRho.p, density, sizeof(double) * (size_t)B * N, hipMemcpyHostToDevice, st));
     DFTA_HIP(ctx, hipEventRecord(ctx->ev[0], st));
     int rc = dfta_poisson_solve_launch(p, dZ.p, dRho.p, dU.p, dVc.p, dErr.p, nullptr);
@@ -672,16 +674,30 @@ int dfta_poisson_solve(dfta_poisson* p, const int* Z, const double* density, dou
     return DFTA_OK;
 }
 
+}  // extern "C"
+
+static __global__ void k_int_to_double(const int* __restrict__ in, int n, double* __restrict__ out)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = in[i];
+}
+
+extern "C" {
+
 int dfta_poisson_solve_dev(dfta_poisson* p, const int* dZ, const double* dDensity, double* dU)
 {
     if (!p) return DFTA_ERR_INVALID;
     DFTA_REQUIRE(p->ctx, dZ && dDensity && dU, "null input");
     DFTA_ENTER(p->ctx);
+    DevBuf<double> dNe;                                  // (double)Z: the outer boundary of a neutral atom
+    DFTA_HIP(p->ctx, dNe.alloc(p->batch));
+    hipLaunchKernelGGL(k_int_to_double, dim3((p->batch + 255) / 256), dim3(256), 0, p->ctx->stream, dZ, p->batch, dNe.p);
+    DFTA_CHECK_LAUNCH(p->ctx);
     // synchronises: the group barriers' abort flag is inspected after every solve (and the solve repeated with one
     // workgroup per atom if it was raised), so a DFTA_OK always means a completed solve
-    int rc = dfta_poisson_solve_launch(p, dZ, dDensity, dU, nullptr, nullptr, nullptr);
+    int rc = dfta_poisson_solve_launch(p, dNe.p, dDensity, dU, nullptr, nullptr, nullptr);
     if (rc) return rc;
-    return dfta_poisson_finish(p, dZ, dDensity, dU, nullptr, nullptr, nullptr);
+    return dfta_poisson_finish(p, dNe.p, dDensity, dU, nullptr, nullptr, nullptr);
 }
 
 int dfta_poisson_group_info(const dfta_poisson* p, int* G, int* degraded, int* aborts)

@@ -3410,7 +3410,7 @@ __device__ __forceinline__ double res_cycles(const MgDesc& D, Atom& A, Res& R, c
 
 // SolvePoissonNonUniform (PoissonSolver.h:51-81) by a resident group: kResWG blocks per atom
 __global__ __launch_bounds__(kThreads) void k_poisson_solve_res(const MgDesc* __restrict__ Dp, double* __restrict__ phi0, double* __restrict__ phi1,
-                                                                double* __restrict__ src, const int* __restrict__ Z,
+                                                                double* __restrict__ src, const double* __restrict__ Ne,
                                                                 const double* __restrict__ density, const double* __restrict__ r,
                                                                 const double* __restrict__ psrc, double* __restrict__ U,
                                                                 int* __restrict__ vcycles, double* __restrict__ errs,
@@ -3481,7 +3481,7 @@ __global__ __launch_bounds__(kThreads) void k_poisson_solve_res(const MgDesc* __
         for (int l = 0; l < R.kres; ++l) { DFTA_RES_LEVEL(R.logC0 - l, (res_init_level<LC>(D, A, R, l, rho, r, psrc, src_all))) }
         __syncthreads();
     } else {
-        res_init_coarse(D, A, R, rho, r, psrc, 0.0, (double)Z[a]);
+        res_init_coarse(D, A, R, rho, r, psrc, 0.0, Ne[a]);     // U(Rmax) = electron count (PoissonSolver.h:76 passes Z: neutral)
     }
     const double err = res_cycles(D, A, R, 100, 1E-3, 1E-14, red, c);      // FullCycle(1E-3, 1E-14), PoissonSolver.h:78
     if (R.role == 0) {
@@ -3516,7 +3516,7 @@ __global__ __launch_bounds__(kThreads) void k_poisson_solve_res(const MgDesc* __
 #ifndef DFTA_MG_RES16
 // SolvePoissonNonUniform (PoissonSolver.h:51-81): one block per atom
 __global__ __launch_bounds__(kThreads) void k_poisson_solve(const MgDesc* __restrict__ Dp, double* __restrict__ phi0, double* __restrict__ phi1,
-                                                            double* __restrict__ src, const int* __restrict__ Z,
+                                                            double* __restrict__ src, const double* __restrict__ Ne,
                                                             const double* __restrict__ density, const double* __restrict__ r,
                                                             const double* __restrict__ psrc, double* __restrict__ U,
                                                             int* __restrict__ vcycles, double* __restrict__ errs,
@@ -3568,7 +3568,7 @@ __global__ __launch_bounds__(kThreads) void k_poisson_solve(const MgDesc* __rest
     __syncthreads();
     Counters c{0, 0};
     PROF_T0();
-    initialize(D, A, 0.0, (double)Z[a]);
+    initialize(D, A, 0.0, Ne[a]);                                  // U(Rmax) = electron count (PoissonSolver.h:76 passes Z: neutral)
     const double err = run_cycles<true>(D, A, 0, 100, 1E-3, 1E-14, red, c);      // FullCycle(1E-3, 1E-14), PoissonSolver.h:78
     PROF_ADD(5, 21);
     const double* __restrict__ P = A.cur_phi(0, L0);

@@ -17,6 +17,8 @@
 #include "ordered_sum.h"
 #include "xc.h"
 
+namespace dfta { void config_set_error(const char* msg); }   // ctx_grid.cpp: the text dfta_config_last_error() returns
+
 namespace {
 
 constexpr double kPi = 3.14159265358979323846;
@@ -24,8 +26,9 @@ constexpr double fourM_PI = 4. * kPi;
 constexpr double kTotalEnergyErr = 1E-11;   // DFTAtom.cpp:349
 
 struct AtomState {          // per atom, device
-    int Z;
-    int nAlphaE, nBetaE;    // electrons per spin (LSDA), DFTAtom.cpp:611-638
+    int Z;                  // nuclear charge: potential, energies, bracket bottoms, R[0] of the record
+    double nE;              // electrons: the flat start density and the multigrid's outer boundary (== Z for a neutral atom)
+    double nAlphaE, nBetaE; // electrons per spin (LSDA), DFTAtom.cpp:611-638
     int job_off, job_end;   // jobs of this atom in the level solver (alpha levels first, then beta)
     int lastTimeConverged;
     int finished;
@@ -43,7 +46,7 @@ __global__ void k_init_density(const AtomState* __restrict__ atoms, int lsda, in
     const AtomState s = atoms[a];
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < N; i += gridDim.x * blockDim.x) {
         const size_t o = (size_t)a * N + i;
-        if (!lsda) density[o] = (i == 0) ? 0. : s.Z / volume;
+        if (!lsda) density[o] = (i == 0) ? 0. : s.nE / volume;
         else {
             const double cA = s.nAlphaE / volume, cB = s.nBetaE / volume;
             dA[o] = (i == 0) ? 0. : cA;
@@ -160,7 +163,7 @@ __global__ void k_tail(const AtomState* __restrict__ atoms, int lsda, int N, con
 
 // energy assembly and the reference's stop test (DFTAtom.cpp:459-481 / 985-1006); one thread per atom
 __global__ void k_energies(AtomState* __restrict__ atoms, int natoms, const dfta::Job* __restrict__ jobs,
-                           const double* __restrict__ integrals, double* __restrict__ records, int* __restrict__ fin)
+                           const double* __restrict__ occ, const double* __restrict__ integrals, double* __restrict__ records, int* __restrict__ fin)
 {
     const int a = blockIdx.x * blockDim.x + threadIdx.x;
     if (a >= natoms) return;
@@ -169,7 +172,7 @@ __global__ void k_energies(AtomState* __restrict__ atoms, int natoms, const dfta
     double Eelectronic = 0;
     bool conv = true;
     for (int k = s.job_off; k < s.job_end; ++k) {
-        Eelectronic += jobs[k].occ * jobs[k].E;                    // DFTAtom.cpp:561
+        Eelectronic += occ[k] * jobs[k].E;                         // DFTAtom.cpp:561 (occ[k] == (double)jobs[k].occ for Aufbau)
         conv = conv && (jobs[k].converged != 0);
     }
     const double* I = integrals + (size_t)a * 5;
@@ -231,9 +234,10 @@ struct dfta_scf {
     struct LiveSolver { dfta_poisson* p = nullptr; int G = 0; bool tried = false; };
     LiveSolver live_solver[kLiveClasses];
     int live_cap = 0;                     // atoms the gather buffers hold
-    int* d_liveZ = nullptr;               // live_cap charges, live_cap skip flags, live_cap atom indices
-    double *d_liveRho = nullptr, *d_liveU = nullptr;
+    int* d_liveIdx = nullptr;             // live_cap skip flags, then live_cap atom indices
+    double *d_liveNe = nullptr, *d_liveRho = nullptr, *d_liveU = nullptr;   // d_liveNe: the live atoms' electron counts
     std::vector<AtomState> h_atoms;
+    std::vector<double> h_liveNe;         // host staging of d_liveNe (the copy is asynchronous)
     std::vector<double> h_bottom0;        // per potential: -Z^2-1 (DFTAtom.cpp:407)
     std::vector<double> h_job_bottom;     // per job: bracket start of the next level solve
     std::vector<dfta::Job> h_jobs;        // job results of the last step
@@ -247,7 +251,7 @@ struct dfta_scf {
     int steps_done = 0;
     std::vector<int> spin_nlev[2];      // per atom number of levels per spin
     AtomState* d_atoms = nullptr;
-    int* d_Z = nullptr;
+    double* d_Ne = nullptr;               // per atom: electrons, the multigrid's outer boundary U(Rmax)
     double *d_density = nullptr, *d_dA = nullptr, *d_dB = nullptr, *d_V = nullptr, *d_U = nullptr, *d_Vexc = nullptr,
            *d_va = nullptr, *d_vb = nullptr, *d_eexc = nullptr, *d_newDensity = nullptr, *d_integrands = nullptr,
            *d_integrals = nullptr, *d_records = nullptr;
@@ -275,13 +279,13 @@ extern "C" {
 void dfta_scf_destroy(dfta_scf* s)
 {
     if (!s) return;
-    void* ptrs[] = {s->d_fin, s->d_atoms, s->d_Z, s->d_density, s->d_dA, s->d_dB, s->d_V, s->d_U, s->d_Vexc, s->d_va, s->d_vb, s->d_eexc,
+    void* ptrs[] = {s->d_fin, s->d_atoms, s->d_Ne, s->d_density, s->d_dA, s->d_dB, s->d_V, s->d_U, s->d_Vexc, s->d_va, s->d_vb, s->d_eexc,
                     s->d_newDensity, s->d_integrands, s->d_integrals, s->d_records};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     for (hipEvent_t e : s->ev) if (e) (void)hipEventDestroy(e);
     if (s->poisson) dfta_poisson_destroy(s->poisson);
     for (auto& ls : s->live_solver) if (ls.p) dfta_poisson_destroy(ls.p);
-    for (void* p : {(void*)s->d_liveZ, (void*)s->d_liveRho, (void*)s->d_liveU}) if (p) (void)hipFree(p);
+    for (void* p : {(void*)s->d_liveIdx, (void*)s->d_liveNe, (void*)s->d_liveRho, (void*)s->d_liveU}) if (p) (void)hipFree(p);
     delete s;
 }
 
@@ -296,9 +300,40 @@ int dfta_scf_create(dfta_ctx* ctx, const dfta_grid* g, int lsda, int natoms, con
 int dfta_scf_create_ex(dfta_ctx* ctx, const dfta_grid* g, int lsda, int natoms, const int* Z, double alpha, int levels_mode,
                        int tree_depth, const dfta_scf_options* options, dfta_scf** out)
 {
+    return dfta_scf_create_config(ctx, g, lsda, natoms, Z, nullptr, nullptr, nullptr, nullptr, alpha, levels_mode, tree_depth, options, out);
+}
+
+// the levels of one spin channel of an explicit configuration: sorted by (n, l) (DFTAtom.cpp:367) and checked; ne += their electrons
+static bool config_channel(dfta_ctx* ctx, int a, int lsda, int cnt, const int* n, const int* l, const double* occ,
+                           std::vector<std::pair<std::pair<int, int>, double>>& lev, double& ne)
+{
+    lev.clear();
+    for (int k = 0; k < cnt; ++k) lev.push_back({{n[k], l[k]}, occ[k]});
+    std::stable_sort(lev.begin(), lev.end(), [](const auto& x, const auto& y) { return x.first < y.first; });
+    const double perl = lsda ? 1. : 2.;
+    for (size_t k = 0; k < lev.size(); ++k) {
+        const int N = lev[k].first.first, L = lev[k].first.second;
+        const double o = lev[k].second;
+        // N: principal quantum number - 1, as dfta_get_subshells_ex and dfta_scf_get_levels report it
+        if (L < 0 || L > 3 || N < L) { snprintf(ctx->err, sizeof(ctx->err), "atom %d: level n = %d, l = %d (needs 0 <= l < n, l <= 3)", a, N + 1, L); return false; }
+        if (k > 0 && lev[k - 1].first == lev[k].first) { snprintf(ctx->err, sizeof(ctx->err), "atom %d: level n = %d, l = %d given twice", a, N + 1, L); return false; }
+        if (!(o > 0) || o > perl * (2 * L + 1)) {
+            snprintf(ctx->err, sizeof(ctx->err), "atom %d: level n = %d, l = %d: occupation %g outside (0, %g]", a, N + 1, L, o, perl * (2 * L + 1));
+            return false;
+        }
+        ne += o;
+    }
+    return true;
+}
+
+int dfta_scf_create_config(dfta_ctx* ctx, const dfta_grid* g, int lsda, int natoms, const int* Z, const int* nlev, const int* cn,
+                           const int* cl, const double* cocc, double alpha, int levels_mode, int tree_depth,
+                           const dfta_scf_options* options, dfta_scf** out)
+{
     if (!ctx || !g || !out) return DFTA_ERR_INVALID;
     DFTA_ENTER(ctx);
     DFTA_REQUIRE(ctx, natoms >= 1 && Z && alpha >= 0 && alpha <= 1, "scf arguments");
+    DFTA_REQUIRE(ctx, !nlev || (cn && cl && cocc), "configuration: n, l and occ are needed with nlev");
     dfta_scf_options opt = {(int)sizeof(dfta_scf_options), DFTA_INT_SIMPSON38, DFTA_XC_VWN, DFTA_AUFBAU_REFERENCE, -1, DFTA_SWEEPS_EXACT};
     if (options) {
         // the caller's struct may be shorter (an older header) or longer (a newer one) than this library's: read what both know
@@ -331,23 +366,59 @@ int dfta_scf_create_ex(dfta_ctx* ctx, const dfta_grid* g, int lsda, int natoms, 
     s->h_atoms.resize(natoms);
     s->h_bottom0.resize(s->nV);
     s->spin_nlev[0].resize(natoms); s->spin_nlev[1].assign(natoms, 0);
+    std::vector<std::pair<std::pair<int, int>, double>> lev;
+    size_t coff = 0;                                           // running offset into the caller's n / l / occ
     for (int a = 0; a < natoms; ++a) {
-        DFTA_REQUIRE(ctx, Z[a] >= 1 && Z[a] <= 118, "Z out of range");
+        if (Z[a] < 1 || Z[a] > 118) {
+            snprintf(ctx->err, sizeof(ctx->err), "Z out of range");
+            if (nlev) dfta::config_set_error(ctx->err);
+            dfta_scf_destroy(s);
+            return DFTA_ERR_INVALID;
+        }
         AtomState& st = s->h_atoms[a];
         memset(&st, 0, sizeof(st));
         st.Z = Z[a];
         st.job_off = (int)specs.size();
         int an[32], al[32], ao[32], bn[32], bl[32], bo[32], nA = 0, nB = 0;
-        if (!lsda) {
+        if (nlev) {                                            // explicit configuration (fractional occupations, cations)
+            nA = nlev[2 * a];
+            nB = nlev[2 * a + 1];
+            double ne = 0, neA = 0;
+            bool ok = nA >= 0 && nB >= 0 && nA + nB >= 1 && nA <= 32 && nB <= 32 && (lsda || nB == 0);
+            if (!ok) snprintf(ctx->err, sizeof(ctx->err), "atom %d: level counts %d / %d (1 .. 32 levels; LDA: no beta levels)", a, nA, nB);
+            for (int spin = 0; ok && spin < (lsda ? 2 : 1); ++spin) {
+                const int cnt = spin ? nB : nA;
+                ok = config_channel(ctx, a, lsda, cnt, cn + coff, cl + coff, cocc + coff, lev, ne);
+                coff += (size_t)cnt;
+                for (size_t k = 0; ok && k < lev.size(); ++k) {
+                    const double o = lev[k].second;
+                    const int io = (o == std::floor(o)) ? static_cast<int>(o) : 0;     // Job::occ: the integer, 0 for a fractional one
+                    specs.push_back({lsda ? 2 * a + spin : a, lev[k].first.first, lev[k].first.second, io, o});
+                }
+                if (spin == 0) neA = ne;
+            }
+            if (ok && ne > Z[a] + 1e-9) {
+                snprintf(ctx->err, sizeof(ctx->err), "atom %d: %g electrons for Z = %d (anions are not supported)", a, ne, Z[a]);
+                ok = false;
+            }
+            if (!ok) { dfta::config_set_error(ctx->err); dfta_scf_destroy(s); return DFTA_ERR_INVALID; }
+            st.nE = ne;
+            st.nAlphaE = neA;
+            st.nBetaE = ne - neA;
+            s->h_bottom0[lsda ? 2 * a : a] = -double(Z[a]) * Z[a] - 1.;
+            if (lsda) s->h_bottom0[2 * a + 1] = -double(Z[a]) * Z[a] - 1.;
+        } else if (!lsda) {
             nA = dfta_get_subshells_ex(Z[a], opt.aufbau, an, al, ao, 32);
             if (nA < 0) { dfta_scf_destroy(s); return DFTA_ERR_INVALID; }
-            for (int k = 0; k < nA; ++k) specs.push_back({a, an[k], al[k], ao[k]});
+            for (int k = 0; k < nA; ++k) specs.push_back({a, an[k], al[k], ao[k], static_cast<double>(ao[k])});
+            st.nE = Z[a];
             s->h_bottom0[a] = -double(Z[a]) * Z[a] - 1.;                                   // DFTAtom.cpp:407
         } else {
             if (dfta_split_spin_ex(Z[a], opt.aufbau, &nA, &nB, an, al, ao, bn, bl, bo, 32) != DFTA_OK) { dfta_scf_destroy(s); return DFTA_ERR_INVALID; }
             int ne = 0;
-            for (int k = 0; k < nA; ++k) { specs.push_back({2 * a, an[k], al[k], ao[k]}); ne += ao[k]; }
-            for (int k = 0; k < nB; ++k) specs.push_back({2 * a + 1, bn[k], bl[k], bo[k]});
+            for (int k = 0; k < nA; ++k) { specs.push_back({2 * a, an[k], al[k], ao[k], static_cast<double>(ao[k])}); ne += ao[k]; }
+            for (int k = 0; k < nB; ++k) specs.push_back({2 * a + 1, bn[k], bl[k], bo[k], static_cast<double>(bo[k])});
+            st.nE = Z[a];
             st.nAlphaE = ne;
             st.nBetaE = Z[a] - ne;
             s->h_bottom0[2 * a] = s->h_bottom0[2 * a + 1] = -double(Z[a]) * Z[a] - 1.;     // DFTAtom.cpp:919,929
@@ -372,12 +443,14 @@ int dfta_scf_create_ex(dfta_ctx* ctx, const dfta_grid* g, int lsda, int natoms, 
     al(&s->d_va, aN); al(&s->d_vb, aN); al(&s->d_eexc, aN); al(&s->d_newDensity, aN * s->nspin); al(&s->d_integrands, aN * 5);
     al(&s->d_integrals, (size_t)natoms * 5); al(&s->d_records, (size_t)natoms * DFTA_RECORD_DOUBLES);
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&s->d_atoms), sizeof(AtomState) * natoms);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&s->d_Z), sizeof(int) * natoms);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&s->d_Ne), sizeof(double) * natoms);
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&s->d_fin), sizeof(int) * natoms);
     if (e == hipSuccess) e = hipMemsetAsync(s->d_fin, 0, sizeof(int) * natoms, st);
     for (auto& ev : s->ev) if (e == hipSuccess) e = hipEventCreate(&ev);
     if (e == hipSuccess) e = hipMemcpyAsync(s->d_atoms, s->h_atoms.data(), sizeof(AtomState) * natoms, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(s->d_Z, Z, sizeof(int) * natoms, hipMemcpyHostToDevice, st);
+    std::vector<double> h_ne(natoms);
+    for (int a = 0; a < natoms; ++a) h_ne[a] = s->h_atoms[a].nE;
+    if (e == hipSuccess) e = hipMemcpyAsync(s->d_Ne, h_ne.data(), sizeof(double) * natoms, hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemsetAsync(s->d_records, 0, sizeof(double) * natoms * DFTA_RECORD_DOUBLES, st);
     if (e != hipSuccess) {
         snprintf(ctx->err, sizeof(ctx->err), "scf alloc: %s", hipGetErrorString(e));
@@ -387,8 +460,8 @@ int dfta_scf_create_ex(dfta_ctx* ctx, const dfta_grid* g, int lsda, int natoms, 
     // DFTAtom.cpp:371-392 / 874-904: flat density, Poisson, v_xc, start potential
     const dim3 grid(std::min(64, (N + 255) / 256), natoms), block(256);
     hipLaunchKernelGGL(k_init_density, grid, block, 0, st, s->d_atoms, s->lsda, N, g->Rmax, s->d_density, s->d_dA, s->d_dB);
-    rc = dfta_poisson_solve_launch(s->poisson, s->d_Z, s->d_density, s->d_U, nullptr, nullptr, nullptr);
-    if (!rc) rc = dfta_poisson_finish(s->poisson, s->d_Z, s->d_density, s->d_U, nullptr, nullptr, nullptr);
+    rc = dfta_poisson_solve_launch(s->poisson, s->d_Ne, s->d_density, s->d_U, nullptr, nullptr, nullptr);
+    if (!rc) rc = dfta_poisson_finish(s->poisson, s->d_Ne, s->d_density, s->d_U, nullptr, nullptr, nullptr);
     if (!rc) rc = scf_xc(s);
     if (rc) { dfta_scf_destroy(s); return rc; }
     hipLaunchKernelGGL(k_potential, grid, block, 0, st, s->d_atoms, s->lsda, N, g->d_r, s->d_U, s->d_Vexc, s->d_va, s->d_vb, s->d_V);
@@ -487,16 +560,17 @@ int dfta_scf_step(dfta_scf* s, dfta_step_stats* stats)
     bool use_live = pl != nullptr;
     std::vector<int> h_live;
     if (use_live && s->live_cap < cls_atoms) {
-        for (void* q : {(void*)s->d_liveZ, (void*)s->d_liveRho, (void*)s->d_liveU}) if (q) (void)hipFree(q);
-        s->d_liveZ = nullptr; s->d_liveRho = nullptr; s->d_liveU = nullptr;
+        for (void* q : {(void*)s->d_liveIdx, (void*)s->d_liveNe, (void*)s->d_liveRho, (void*)s->d_liveU}) if (q) (void)hipFree(q);
+        s->d_liveIdx = nullptr; s->d_liveNe = nullptr; s->d_liveRho = nullptr; s->d_liveU = nullptr;
         s->live_cap = 0;
-        hipError_t e = hipMalloc(reinterpret_cast<void**>(&s->d_liveZ), sizeof(int) * 3 * cls_atoms);
+        hipError_t e = hipMalloc(reinterpret_cast<void**>(&s->d_liveIdx), sizeof(int) * 2 * cls_atoms);
+        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&s->d_liveNe), sizeof(double) * cls_atoms);
         if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&s->d_liveRho), sizeof(double) * (size_t)cls_atoms * N);
         if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&s->d_liveU), sizeof(double) * (size_t)cls_atoms * N);
         if (e == hipSuccess) s->live_cap = cls_atoms;
         else {                                             // no room for the gathered copies: the batch's own solver (same bits)
-            for (void* q : {(void*)s->d_liveZ, (void*)s->d_liveRho, (void*)s->d_liveU}) if (q) (void)hipFree(q);
-            s->d_liveZ = nullptr; s->d_liveRho = nullptr; s->d_liveU = nullptr;
+            for (void* q : {(void*)s->d_liveIdx, (void*)s->d_liveNe, (void*)s->d_liveRho, (void*)s->d_liveU}) if (q) (void)hipFree(q);
+            s->d_liveIdx = nullptr; s->d_liveNe = nullptr; s->d_liveRho = nullptr; s->d_liveU = nullptr;
             (void)hipGetLastError();
             use_live = false;
             pl = nullptr;
@@ -504,33 +578,35 @@ int dfta_scf_step(dfta_scf* s, dfta_step_stats* stats)
     }
     if (use_live) {
         const int cap = s->live_cap;
-        h_live.assign(3 * cap, 0);
+        h_live.assign(2 * cap, 0);
+        s->h_liveNe.assign(cap, 1.);
         for (int i = 0; i < cap; ++i) {
             const bool on = i < nlive;
-            h_live[i] = on ? s->h_atoms[live_atoms[i]].Z : 1;
-            h_live[cap + i] = on ? 0 : 1;
-            h_live[2 * cap + i] = on ? live_atoms[i] : 0;
+            if (on) s->h_liveNe[i] = s->h_atoms[live_atoms[i]].nE;
+            h_live[i] = on ? 0 : 1;
+            h_live[cap + i] = on ? live_atoms[i] : 0;
         }
-        DFTA_HIP(ctx, hipMemcpyAsync(s->d_liveZ, h_live.data(), sizeof(int) * h_live.size(), hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(k_gather_rows, dim3(std::min(256, (N + 255) / 256), nlive), dim3(256), 0, st, s->d_density, s->d_liveZ + 2 * cap, N, s->d_liveRho);
+        DFTA_HIP(ctx, hipMemcpyAsync(s->d_liveIdx, h_live.data(), sizeof(int) * h_live.size(), hipMemcpyHostToDevice, st));
+        DFTA_HIP(ctx, hipMemcpyAsync(s->d_liveNe, s->h_liveNe.data(), sizeof(double) * cap, hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(k_gather_rows, dim3(std::min(256, (N + 255) / 256), nlive), dim3(256), 0, st, s->d_density, s->d_liveIdx + cap, N, s->d_liveRho);
         DFTA_CHECK_LAUNCH(ctx);
     }
     {
         dfta_range r_poisson("dfta: multigrid Poisson solve (FullCycle)");
         dfta_poisson* ps = use_live ? pl : s->poisson;
-        const int* pZ = use_live ? s->d_liveZ : s->d_Z;
+        const double* pNe = use_live ? s->d_liveNe : s->d_Ne;
         const double* pRho = use_live ? s->d_liveRho : s->d_density;
         double* pU = use_live ? s->d_liveU : s->d_U;
-        const int* pSkip = use_live ? s->d_liveZ + s->live_cap : s->d_fin;
-        rc = dfta_poisson_solve_launch(ps, pZ, pRho, pU, nullptr, nullptr, pSkip);
+        const int* pSkip = use_live ? s->d_liveIdx : s->d_fin;
+        rc = dfta_poisson_solve_launch(ps, pNe, pRho, pU, nullptr, nullptr, pSkip);
         if (rc) return rc;
         DFTA_HIP(ctx, hipEventRecord(s->ev[2], st));   // ev[1]..ev[2] brackets exactly the persistent multigrid kernel
         // synchronises and inspects the group barriers' abort flag on EVERY step; an aborted solve is repeated with one
         // workgroup per atom before anything reads U
-        rc = dfta_poisson_finish(ps, pZ, pRho, pU, nullptr, nullptr, pSkip);
+        rc = dfta_poisson_finish(ps, pNe, pRho, pU, nullptr, nullptr, pSkip);
         if (rc) return rc;
         if (use_live) {
-            hipLaunchKernelGGL(k_scatter_rows, dim3(std::min(256, (N + 255) / 256), nlive), dim3(256), 0, st, s->d_liveU, s->d_liveZ + 2 * s->live_cap, N, s->d_U);
+            hipLaunchKernelGGL(k_scatter_rows, dim3(std::min(256, (N + 255) / 256), nlive), dim3(256), 0, st, s->d_liveU, s->d_liveIdx + s->live_cap, N, s->d_U);
             DFTA_CHECK_LAUNCH(ctx);
         }
     }
@@ -548,7 +624,7 @@ int dfta_scf_step(dfta_scf* s, dfta_step_stats* stats)
     else
         rc = dfta_launch_integrate_ordered(ctx, s->integ_rule, g->uniform ? g->h : 1.0, s->d_integrands, N, natoms * 5, (size_t)N, s->d_integrals);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_energies, dim3((natoms + 63) / 64), dim3(64), 0, st, s->d_atoms, natoms, s->solver.d_jobs, s->d_integrals,
+    hipLaunchKernelGGL(k_energies, dim3((natoms + 63) / 64), dim3(64), 0, st, s->d_atoms, natoms, s->solver.d_jobs, s->solver.d_occ, s->d_integrals,
                        s->d_records, s->d_fin);
     DFTA_CHECK_LAUNCH(ctx);
     DFTA_HIP(ctx, hipEventRecord(s->ev[3], st));
@@ -657,14 +733,30 @@ int dfta_scf_get_levels(dfta_scf* s, int atom, int spin, int* n, int* l, int* oc
     DFTA_REQUIRE(ctx, !jobs.empty(), "no SCF step has run yet");
     int k0 = s->h_atoms[atom].job_off + (spin ? s->spin_nlev[0][atom] : 0);
     const int cnt = s->spin_nlev[spin][atom];
+    if (occ)                                     // the whole channel is checked before anything is written
+        for (int k = 0; k < cnt; ++k) {
+            const double o = s->solver.h_occ[k0 + k];
+            DFTA_REQUIRE(ctx, o == std::floor(o), "a fractional occupation: read it with dfta_scf_get_occupations");
+        }
     for (int k = 0; k < cnt; ++k) {
         const dfta::Job& j = jobs[k0 + k];
         if (n) n[k] = j.n;
         if (l) l[k] = j.l;
-        if (occ) occ[k] = j.occ;
+        if (occ) occ[k] = static_cast<int>(s->solver.h_occ[k0 + k]);
         if (E) E[k] = j.E;
         if (converged) converged[k] = j.converged;
     }
+    return DFTA_OK;
+}
+
+int dfta_scf_get_occupations(dfta_scf* s, int atom, int spin, double* occ)
+{
+    if (!s) return DFTA_ERR_INVALID;
+    dfta_ctx* ctx = s->ctx;
+    DFTA_ENTER(ctx);
+    DFTA_REQUIRE(ctx, atom >= 0 && atom < s->natoms && spin >= 0 && spin < s->nspin && occ, "atom/spin/occ");
+    const int k0 = s->h_atoms[atom].job_off + (spin ? s->spin_nlev[0][atom] : 0);
+    for (int k = 0; k < s->spin_nlev[spin][atom]; ++k) occ[k] = s->solver.h_occ[k0 + k];
     return DFTA_OK;
 }
 

@@ -15,10 +15,11 @@ int dfta_launch_pw92_lsda(dfta_ctx* ctx, const double* dNa, const double* dNb, s
 int dfta_launch_pbe_radial(dfta_ctx* ctx, const dfta_grid* g, int natoms, const double* dNa, const double* dNb, double* dRes,
                            double* dVa, double* dVb, double* dEexc, const int* dFin);
 // poisson.hip: launch (asynchronous) / finish (synchronises, inspects the group barriers' abort flag and repeats the solve with
-// one workgroup per atom if it was raised).  dSkip: per atom, non-zero = leave this atom alone (may be null).
-int dfta_poisson_solve_launch(dfta_poisson* p, const int* dZ, const double* dDensity, double* dU, int* dVcycles, double* dErr,
+// one workgroup per atom if it was raised).  dSkip: per atom, non-zero = leave this atom alone (may be null).  dNe: per atom, the
+// electron count, the outer boundary value U(Rmax) (the reference's Z: (double)Z for a neutral atom).
+int dfta_poisson_solve_launch(dfta_poisson* p, const double* dNe, const double* dDensity, double* dU, int* dVcycles, double* dErr,
                               const int* dSkip);
-int dfta_poisson_finish(dfta_poisson* p, const int* dZ, const double* dDensity, double* dU, int* dVcycles, double* dErr,
+int dfta_poisson_finish(dfta_poisson* p, const double* dNe, const double* dDensity, double* dU, int* dVcycles, double* dErr,
                         const int* dSkip);
 int dfta_poisson_take_vcycles(dfta_poisson* p, unsigned long long* out);
 int dfta_poisson_group_state(const dfta_poisson* p, int* G, int* degraded, int* aborts);

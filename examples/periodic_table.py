@@ -7,6 +7,8 @@ costs nothing more (dfta_scf_step).  The fixed-size result records are gathered 
 
     python examples/periodic_table.py                       # one GPU
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 examples/periodic_table.py
+    python examples/periodic_table.py --charge 1            # the cations X+ (Z > charge)
+    python examples/periodic_table.py --ionization          # IE = E(X+) - E(X): neutral atom and cation of every Z in ONE batch per rank
 """
 import argparse
 import json
@@ -39,6 +41,11 @@ def main():
                     help="one GPU, no launcher: run each of the N shards of an N-rank sweep alone, one after the other, and report the "
                          "per-shard wall times; their maximum PREDICTS the N-GPU wall time (shards never interact; the only collective "
                          "is a gather of 64 doubles per atom)")
+    ap.add_argument("--charge", type=int, default=0, help="ionic charge of every atom (cations: dftatom_amd.ion_config); atoms with Z <= charge are skipped")
+    ap.add_argument("--lsda", action="store_true", help="spin-polarised (LSDA) instead of LDA")
+    ap.add_argument("--ionization", action="store_true",
+                    help="first ionization energies: the neutral atom and the +1 cation of every Z of a rank's shard advance in one batch; "
+                         "IE = E(+1) - E(0) per Z (H+ has no electron: E = 0)")
     args = ap.parse_args()
 
     import torch
@@ -62,7 +69,7 @@ def main():
     delta, rmax = {14: (5e-4, 25.0), 17: (1e-4, 50.0)}.get(args.levels, (1e-4, 50.0))
     grid = D.Grid(ctx, args.levels, delta, rmax)
 
-    Zs = list(range(args.zmin, args.zmax + 1))
+    Zs = [z for z in range(args.zmin, args.zmax + 1) if z > args.charge]
     cost = sweep.atom_cost if args.partition == "work" else None
     modes = dict(sweep_mode=D.SWEEPS_TOLERANCE if args.sweeps == "tolerance" else D.SWEEPS_EXACT,
                  poisson_mode={"tolerance": D.POISSON_TOLERANCE, "adaptive": D.POISSON_ADAPTIVE}.get(args.poisson, D.POISSON_EXACT),
@@ -108,10 +115,12 @@ def main():
         grid.close()
         ctx.close()
         return
+    if args.ionization:
+        return ionization(args, D, dist, ctx, grid, sweep.partition_atoms(Zs, world, cost=cost, model=cost_model)[rank], modes, world, rank)
     mine = sweep.partition_atoms(Zs, world, cost=cost, model=cost_model)[rank]
     cap = max(len(s) for s in sweep.partition_atoms(Zs, world, cost=cost, model=cost_model))
     t0 = time.time()
-    scf = D.Scf(ctx, grid, mine, lsda=False, **modes)
+    scf = D.Scf(ctx, grid, mine, lsda=args.lsda, charge=args.charge if args.charge else None, **modes)
     steps = 0
     while steps < args.max_steps:
         scf.step(want_stats=False)
@@ -138,6 +147,49 @@ def main():
                            "atoms": [{"Z": r["Z"], "Etotal": r["Etotal"], "steps": r["steps"], "finished": r["finished"]} for r in rows]},
                           f, indent=1)
     scf.close()
+    grid.close()
+    ctx.close()
+    if world > 1:
+        dist.barrier()
+        dist.destroy_process_group()
+
+
+def ionization(args, D, dist, ctx, grid, mine, modes, world, rank):
+    """neutral atoms and +1 cations of this rank's Z in ONE batch; results are matched to (Z, charge) by the batch's own order"""
+    HARTREE_EV = 27.211386245988
+    t0 = time.time()
+    Z = list(mine) + [z for z in mine if z > 1]
+    charge = [0] * len(mine) + [1] * (len(Z) - len(mine))
+    scf = D.Scf(ctx, grid, Z, lsda=args.lsda, charge=charge, **modes)
+    steps = 0
+    while steps < args.max_steps:
+        scf.step(want_stats=False)
+        steps += 1
+        if scf.energies()[1].all():
+            break
+    en, fin = scf.energies()
+    scf.close()
+    E = {(z, q): (en[k].Etotal, int(fin[k])) for k, (z, q) in enumerate(zip(Z, charge))}
+    rows = {z: {"Z": z, "E0": E[(z, 0)][0], "E1": E[(z, 1)][0] if z > 1 else 0.0,
+                "finished": E[(z, 0)][1] and (E[(z, 1)][1] if z > 1 else 1)} for z in mine}
+    for r in rows.values():
+        r["IE_Ha"] = r["E1"] - r["E0"]
+        r["IE_eV"] = r["IE_Ha"] * HARTREE_EV
+    if world > 1:
+        parts = [None] * world
+        dist.all_gather_object(parts, rows)
+        rows = {z: r for p in parts for z, r in p.items()}
+    elapsed = time.time() - t0
+    if rank == 0:
+        for z in sorted(rows):
+            r = rows[z]
+            print("Z %3d  E(0) %16.6f  E(+1) %16.6f  IE %10.6f Ha = %8.3f eV  finished %d" % (z, r["E0"], r["E1"], r["IE_Ha"], r["IE_eV"], r["finished"]))
+        print("%d atoms + %d cations in one batch per rank, %d GPU(s), %d SCF steps (rank 0), %.1f s"
+              % (len(rows), sum(1 for z in rows if z > 1), world, steps, elapsed))
+        if args.out:
+            with open(args.out, "w") as f:
+                json.dump({"n_gpus": world, "levels": args.levels, "lsda": args.lsda, "steps": steps, "seconds": elapsed,
+                           "ionization": [rows[z] for z in sorted(rows)]}, f, indent=1)
     grid.close()
     ctx.close()
     if world > 1:

@@ -391,6 +391,36 @@ int dfta_split_spin(int Z, int* nA, int* nB, int* an, int* al, int* aocc, int* b
 int dfta_get_subshells_ex(int Z, int aufbau, int* n, int* l, int* occ, int cap);
 int dfta_split_spin_ex(int Z, int aufbau, int* nA, int* nB, int* an, int* al, int* aocc, int* bn, int* bl, int* bocc, int cap);
 
+/* ---- electron configurations: cations, holes, excited and fractional occupations (beyond the reference) --------------------
+ * A configuration is a list of occupied levels per spin channel: LDA fills the alpha arrays only (nB = 0); LSDA lists the alpha
+ * levels, then the beta levels.  n counts as in dfta_get_subshells (the reference's m_N: principal quantum number - 1; the text
+ * uses the principal quantum number).  Levels are sorted by (n, l) as DFTAtom.cpp:367 sorts them.  Rules (DFTA_ERR_INVALID otherwise,
+ * reason in dfta_config_last_error()): 1 <= Z <= 118; 0 <= l < n, l <= 3; no (n, l) twice in one channel; 0 < occ <= 2(2l+1)
+ * (LDA) or <= 2l+1 (one LSDA channel); 0 < N_e = sum occ <= Z (no anions).
+ *
+ * dfta_config_parse: blank-separated tokens.  `[He]` .. `[Rn]`: that noble gas's Aufbau configuration; `<n><spdf><occ>` (occ may
+ * be fractional: `3p5.5`) sets a subshell, replacing what the core holds there, occ 0 removes it; LSDA only: `<n><spdf><a>/<b>`
+ * gives the alpha / beta split explicitly, otherwise the split of dfta_split_spin_ex applies (alpha = min(occ, 2l+1)).
+ * dfta_ion_config: the Aufbau configuration of Z (option `aufbau`) with `charge` electrons removed from the subshell of highest n,
+ * ties to the highest l (Fe+: 3d6 4s1), then the split of dfta_split_spin_ex; charge 0 gives exactly dfta_get_subshells_ex /
+ * dfta_split_spin_ex.  Both are host-only. */
+int dfta_config_parse(int Z, int lsda, int aufbau, const char* text, int cap, int* nA, int* nB, int* an, int* al, double* aocc,
+                      int* bn, int* bl, double* bocc);
+int dfta_ion_config(int Z, int charge, int lsda, int aufbau, int cap, int* nA, int* nB, int* an, int* al, double* aocc,
+                    int* bn, int* bl, double* bocc);
+/* reason of the last DFTA_ERR_INVALID of dfta_config_parse / dfta_ion_config / dfta_scf_create_config on the calling thread */
+const char* dfta_config_last_error(void);
+/* dfta_scf_create_ex for explicit configurations.  nlev: natoms x 2 level counts (alpha, beta; LDA: beta 0), NULL -> exactly
+ * dfta_scf_create_ex (Aufbau configurations of Z); n, l, occ: atom-major, the alpha levels of an atom then its beta levels.  The
+ * nuclear charge stays Z (potential, energies, bracket bottoms); the electron count N_e = sum occ sets the flat start density
+ * N_e / volume and the multigrid's outer boundary U(Rmax) = N_e.  Neutral integer configurations run bit for bit as
+ * dfta_scf_create_ex. */
+int  dfta_scf_create_config(dfta_ctx* ctx, const dfta_grid* g, int lsda, int natoms, const int* Z, const int* nlev, const int* n,
+                            const int* l, const double* occ, double alpha, int levels_mode, int tree_depth,
+                            const dfta_scf_options* options, dfta_scf** out);
+/* occupations of (atom, spin) as doubles (dfta_scf_get_levels reports them as int and refuses a channel with a fractional one) */
+int  dfta_scf_get_occupations(dfta_scf* s, int atom, int spin, double* occ);
+
 #ifdef __cplusplus
 }
 #endif
