@@ -120,7 +120,7 @@ __device__ __forceinline__ XcPoint xc_point(double na, double nb, double saa, do
     double dedz = rho * c.dz;                          // d(rho eps_c)/dzeta at fixed rho
     double dsig = 0.;
     if (GGA) {
-        const double sigma = POL ? saa + 2. * sab + sbb : saa;
+        const double sigma = POL ? (saa + sbb) + 2. * sab : saa;     // in this order: exchanging the spins exchanges the outputs' bits
         double phi = 1., dphi = 0.;
         if (POL) {
             phi = 0.5 * (cp * cp + cm * cm);

@@ -7,7 +7,14 @@ the one of gga.hip, written again over whole arrays.
 
 Thresholds as the library's: a total density below 1e-18 gives zeros; a spin channel below it has no exchange and zeta is then
 the constant +-1.  Complex inputs are compared through their real parts.
+
+Every function works in the floating type of its inputs: fp64 arrays give the fp64 reference, np.longdouble arrays (x87 80-bit
+where the host has it) the extended one that tests/test_gpu_xc_radial.py measures the kernels and the fp64 reference against.
+The irrational constants are formed in that type (consts()), cube roots go through np.cbrt and not through an fp64 exponent 1/3;
+the fitted constants of the papers are the doubles the kernels hold.
 """
+import types
+
 import numpy as np
 
 PI = np.pi
@@ -25,6 +32,31 @@ PW92_STIFF = (0.0168869, 0.11125, 10.357, 3.6231, 0.88026, 0.49671)      # G = -
 
 PW92, PBE = 3, 4                  # DFTA_XC_PW92, DFTA_XC_PBE
 
+_CONSTS = {}
+
+
+def real_type(x):
+    """the real floating dtype of an array or dtype (the component type of a complex one)"""
+    dt = np.dtype(getattr(x, "dtype", x))
+    return np.zeros(0, dt).real.dtype if dt.kind == "c" else (dt if dt.kind == "f" else np.dtype(float))
+
+
+def complex_type(dt):
+    return np.result_type(real_type(dt), np.complex64)
+
+
+def consts(x):
+    """pi, mu, gamma, 2^(4/3) - 2 and f''(0) in the real type of x"""
+    dt = real_type(x)
+    if dt not in _CONSTS:
+        one = dt.type(1)
+        pi = 4 * np.arctan(one)
+        gamma = (one - np.log(2 * one)) / (pi * pi)
+        fden = 2 * np.cbrt(2 * one) - 2
+        _CONSTS[dt] = types.SimpleNamespace(PI=pi, MU=BETA * pi * pi / 3, GAMMA=gamma, FDEN=fden, FZ0=8 * one / (9 * fden),
+                                            eps=np.finfo(dt).eps)
+    return _CONSTS[dt]
+
 
 # ---- complex-safe elementary functions (accurate real parts, exact first-order imaginary parts) ----------------------------
 def _log1p(z):
@@ -41,63 +73,74 @@ def _expm1(z):
     return np.expm1(z.real) * np.cos(z.imag) + (np.cos(z.imag) - 1.0) + 1j * np.exp(z.real) * np.sin(z.imag)
 
 
-def _pow(x, a):
-    """x^a for x >= 0 (real part), 0 at x == 0"""
+def _cbrt(x):
+    """x^(1/3) for a real part >= 0; a complex step goes through to first order"""
     x = np.asarray(x)
     if not np.iscomplexobj(x):
-        return np.where(x > 0, np.abs(x) ** a, 0.0)
-    out = np.zeros_like(x)
-    nz = x != 0
-    out[nz] = x[nz] ** a
-    return out
+        return np.cbrt(x)
+    c = np.cbrt(x.real)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return c + 1j * np.where(c > 0, x.imag / (3.0 * c * c), 0.0)
+
+
+def _p23(x):
+    c = _cbrt(x)
+    return c * c
+
+
+def _p43(x):
+    return x * _cbrt(x)
 
 
 # ---- the functionals -------------------------------------------------------------------------------------------------------
 def pw92_G(rs, fit):
     """G(rs) = -2A (1 + a1 rs) ln(1 + 1 / (2A (b1 rs^1/2 + b2 rs + b3 rs^3/2 + b4 rs^2)))"""
     A, a1, b1, b2, b3, b4 = fit
-    q = b1 * np.sqrt(rs) + b2 * rs + b3 * rs ** 1.5 + b4 * rs ** 2
+    q = b1 * np.sqrt(rs) + b2 * rs + b3 * rs * np.sqrt(rs) + b4 * rs * rs
     return -2.0 * A * (1.0 + a1 * rs) * _log1p(1.0 / (2.0 * A * q))
 
 
 def pw92_dG(rs, fit):
     """analytic dG/drs (checked against complex steps in test_gga_reference.py)"""
     A, a1, b1, b2, b3, b4 = fit
-    q = b1 * np.sqrt(rs) + b2 * rs + b3 * rs ** 1.5 + b4 * rs ** 2
+    q = b1 * np.sqrt(rs) + b2 * rs + b3 * rs * np.sqrt(rs) + b4 * rs * rs
     dq = 0.5 * b1 / np.sqrt(rs) + b2 + 1.5 * b3 * np.sqrt(rs) + 2.0 * b4 * rs
     return -2.0 * A * a1 * np.log1p(1.0 / (2.0 * A * q)) + (1.0 + a1 * rs) * dq / (q * q + q / (2.0 * A))
 
 
 def spin_f(z):
-    return (_pow(1.0 + z, 4.0 / 3.0) + _pow(1.0 - z, 4.0 / 3.0) - 2.0) / FDEN
+    return (_p43(1.0 + z) + _p43(1.0 - z) - 2.0) / consts(z).FDEN
 
 
 def pw92_eps(rs, z):
     """PW92 correlation energy per particle"""
     e0, e1, mac = pw92_G(rs, PW92_PARA), pw92_G(rs, PW92_FERRO), pw92_G(rs, PW92_STIFF)
-    f, z4 = spin_f(z), z ** 4
-    return e0 - mac * f * (1.0 - z4) / FZ0 + (e1 - e0) * f * z4
+    f, z4 = spin_f(z), (z * z) * (z * z)
+    return e0 - mac * f * (1.0 - z4) / consts(z).FZ0 + (e1 - e0) * f * z4
 
 
 def pbe_Fx(s2):
-    return 1.0 + KAPPA - KAPPA / (1.0 + MU * s2 / KAPPA)
+    return 1.0 + KAPPA - KAPPA / (1.0 + consts(s2).MU * s2 / KAPPA)
 
 
 def exchange_unpolarised(n, sigma, gga):
     """e_x of the unpolarised gas: n eps_x^unif(n) F_x(s), s = |grad n| / (2 k_F n)"""
-    kf = (3.0 * PI ** 2 * n) ** (1.0 / 3.0)
-    ex = -3.0 * kf / (4.0 * PI) * n
+    pi = consts(n).PI
+    kf = _cbrt(3.0 * pi * pi * n)
+    ex = -3.0 * kf / (4.0 * pi) * n
     if not gga:
         return ex
     return ex * pbe_Fx(sigma / (2.0 * kf * n) ** 2)
 
 
 def pbe_H(rho, z, sigma, eps):
-    phi = 0.5 * (_pow(1.0 + z, 2.0 / 3.0) + _pow(1.0 - z, 2.0 / 3.0))
-    kf = (3.0 * PI ** 2 * rho) ** (1.0 / 3.0)
-    ks = np.sqrt(4.0 * kf / PI)
+    k = consts(rho)
+    phi = 0.5 * (_p23(1.0 + z) + _p23(1.0 - z))
+    kf = _cbrt(3.0 * k.PI * k.PI * rho)
+    ks = np.sqrt(4.0 * kf / k.PI)
     t2 = sigma / (2.0 * phi * ks * rho) ** 2
-    gp3 = GAMMA * phi ** 3
+    gp3 = k.GAMMA * phi ** 3
+    GAMMA = k.GAMMA
     A = (BETA / GAMMA) / _expm1(-eps / gp3)
     y = A * t2
     D = 1.0 + y + y * y
@@ -139,7 +182,7 @@ def energy_density(functional, na, nb=None, saa=None, sab=None, sbb=None, part="
         ex = exchange_unpolarised(rho, saa, gga)
         z = np.zeros_like(rho)
         sigma = saa
-    rs = (3.0 / (4.0 * PI * rho)) ** (1.0 / 3.0)
+    rs = _cbrt(3.0 / (4.0 * consts(rho).PI * rho))
     eps = pw92_eps(rs, z)
     part = part.replace("c", "lh")
     ec = rho * eps if "l" in part else 0.0
@@ -171,17 +214,19 @@ def _step(x, scale):
 
 def pointwise(functional, na, nb=None, saa=None, sab=None, sbb=None, part="xlh"):
     """e and its partial derivatives by complex steps.  Unpolarised: dict(e, dn, dsigma); polarised: dict(e, dna, dnb, dsaa, dsab, dsbb)."""
-    na = np.asarray(na, float)
-    shape = na.shape
     pol = nb is not None
-    args = [na] + [np.zeros(shape) + (0.0 if x is None else np.asarray(x, float)) for x in ((nb, saa, sab, sbb) if pol else (saa,))]
+    rest = (nb, saa, sab, sbb) if pol else (saa,)
+    dt = real_type(np.result_type(*(np.asarray(x) for x in (na,) + rest if x is not None)))
+    na = np.asarray(na, dt)
+    shape = na.shape
+    args = [na] + [np.zeros(shape, dt) + (0.0 if x is None else np.asarray(x, dt)) for x in rest]
     rho = args[0] + (args[1] if pol else 0.0)
     sscale = np.maximum(rho, THRESHOLD) ** (8.0 / 3.0)           # the sigma of s ~ 1
     out = {"e": energy_density(functional, *(args if pol else [args[0], None, args[1]]), part=part).real}
     names = ("dna", "dnb", "dsaa", "dsab", "dsbb") if pol else ("dn", "dsigma")
     for k, name in enumerate(names):
         h = _step(args[k], np.maximum(rho, THRESHOLD) if (k < 2 if pol else k < 1) else sscale)
-        pert = [a.astype(complex) for a in args]
+        pert = [a.astype(complex_type(dt)) for a in args]
         pert[k] = pert[k] + 1j * h
         e = energy_density(functional, *(pert if pol else [pert[0], None, pert[1]]), part=part)
         out[name] = e.imag / h
@@ -197,7 +242,24 @@ def log_grid(levels, delta, Rmax):
 
 
 def d_index(f):
-    """df/di along the last axis: 5-point central, second-order one-sided at 0, 1, N-2, N-1"""
+    """df/di along the last axis: 5-point central, second-order one-sided at 0, 1, N-2, N-1.
+
+    Differences first, as gga.hip: neighbouring nodes differ by delta |f|, their difference is (nearly) exact in fp64 and the
+    result keeps its digits.  d_index_sums() is the same stencil summed value by value; its partial sums are of size 7 |f| for
+    a result of size delta |f| (tests/test_gga_reference.py::test_stencil_form_rounding measures both)."""
+    f = np.asarray(f)
+    d = np.empty_like(f)
+    d[..., 2:-2] = (8.0 * (f[..., 3:-1] - f[..., 1:-3]) - (f[..., 4:] - f[..., :-4])) / 12.0
+    for j in (0, 1):
+        d[..., j] = (4.0 * (f[..., j + 1] - f[..., j]) - (f[..., j + 2] - f[..., j])) * 0.5
+    N = f.shape[-1]
+    for j in (N - 2, N - 1):
+        d[..., j] = (4.0 * (f[..., j] - f[..., j - 1]) - (f[..., j] - f[..., j - 2])) * 0.5
+    return d
+
+
+def d_index_sums(f):
+    """the stencils of d_index in the form that cancels (the library's until the radial tests measured it): NOT the reference"""
     f = np.asarray(f)
     d = np.empty_like(f)
     d[..., 2:-2] = (f[..., :-4] - 8.0 * f[..., 1:-3] + 8.0 * f[..., 3:-1] - f[..., 4:]) / 12.0
@@ -209,15 +271,26 @@ def d_index(f):
     return d
 
 
-def radial(functional, r, cnst, na, nb=None):
-    """LDA: (Vexc, eexc); LSDA: (res, va, vb, eexc) -- dfta_xc_radial's outputs for densities of shape (..., N)"""
-    na = np.asarray(na, float)
+def radial(functional, r, cnst, na, nb=None, scale=False, stencil=None):
+    """LDA: (Vexc, eexc); LSDA: (res, va, vb, eexc) -- dfta_xc_radial's outputs for densities of shape (..., N), in the floating
+    type of the densities.  PBE writes zeros at node 0 and below the threshold; PW92 is pointwise (k_pw92_*: zeros below the
+    threshold only -- the SCF's density is 0 at node 0).
+    scale=True: also the tuple T of the same layout, the sum of the magnitudes of the terms each output is made of
+    (|de/drho| + |dF/dr| + 2 |F| / r, plus |e / rho| for eexc; res: the density-weighted mean of the two spins').
+    stencil: d_index (default) or d_index_sums."""
+    D = stencil or d_index
     pol = nb is not None
+    dt = real_type(np.result_type(np.asarray(na), *([np.asarray(nb)] if pol else [])))
+    na = np.asarray(na, dt)
+    nb = np.asarray(nb, dt) if pol else None
+    r, cnst = np.asarray(r, dt), np.asarray(cnst, dt)
+    gga = functional == PBE
     rho = na + nb if pol else na
-    if functional == PBE:
-        ga = d_index(na) / cnst
+    fa = fb = None
+    if gga:
+        ga = D(na) / cnst
         if pol:
-            gb = d_index(nb) / cnst
+            gb = D(nb) / cnst
             p = pointwise(functional, na, nb, ga * ga, ga * gb, gb * gb)
             fa = 2.0 * p["dsaa"] * ga + p["dsab"] * gb
             fb = 2.0 * p["dsbb"] * gb + p["dsab"] * ga
@@ -226,38 +299,56 @@ def radial(functional, r, cnst, na, nb=None):
             fa = 2.0 * p["dsigma"] * ga
     else:
         p = pointwise(functional, na, nb) if pol else pointwise(functional, na)
-    off = (rho < THRESHOLD) | (np.arange(na.shape[-1]) == 0)
+    off = rho < THRESHOLD
+    if gga:
+        off = off | (np.arange(na.shape[-1]) == 0)
+    z = lambda x: np.where(off, 0.0, x)                                            # noqa: E731
+
+    def potential(dn, F):
+        if not gga:
+            return dn, np.abs(dn)
+        dF, c = D(F) / cnst, 2.0 * F / r
+        return dn - (dF + c), np.abs(dn) + np.abs(dF) + np.abs(c)
+
     with np.errstate(divide="ignore", invalid="ignore"):
-        div = lambda F: d_index(F) / cnst + 2.0 * F / r
-        va = (p["dna"] if pol else p["dn"]) - (div(fa) if functional == PBE else 0.0)
+        va, ta = potential(p["dna"] if pol else p["dn"], fa)
         exc = p["e"] / rho
         if not pol:
-            return np.where(off, 0.0, va), np.where(off, 0.0, exc - va)
-        vb = p["dnb"] - (div(fb) if functional == PBE else 0.0)
-        mean = (va * na + vb * nb) / rho
-    z = lambda x: np.where(off, 0.0, x)
-    return z(mean), z(va), z(vb), z(exc - mean)
+            out, T = (z(va), z(exc - va)), (z(ta), z(ta + np.abs(exc)))
+        else:
+            vb, tb = potential(p["dnb"], fb)
+            mean, tm = (va * na + vb * nb) / rho, (ta * na + tb * nb) / rho
+            out, T = (z(mean), z(va), z(vb), z(exc - mean)), (z(tm), z(ta), z(tb), z(tm + np.abs(exc)))
+    return (out, T) if scale else out
+
+
+def running_max(x, w=8):
+    """max of x over j-w .. j+w (a rounding error taken node by node is noise with zeros in it)"""
+    out = x.copy()
+    for k in range(1, w + 1):
+        out[k:] = np.maximum(out[k:], x[:-k])
+        out[:-k] = np.maximum(out[:-k], x[k:])
+    return out
 
 
 def energy(functional, r, cnst, na, nb=None):
     """E_xc = 4 pi Int e r^2 dr (trapezoid rule in the grid index)"""
-    e = energy_density(functional, np.asarray(na, float), None if nb is None else np.asarray(nb, float),
-                       *_sigmas(functional, cnst, na, nb)).real
-    return 4.0 * PI * _trapezoid(e * r * r * cnst)
+    e = energy_density(functional, np.asarray(na), None if nb is None else np.asarray(nb), *_sigmas(functional, cnst, na, nb)).real
+    return 4.0 * consts(e).PI * _trapezoid(e * r * r * cnst)
 
 
 def potential_integral(r, cnst, v, dn):
     """4 pi Int v dn r^2 dr, same rule"""
-    return 4.0 * PI * _trapezoid(v * dn * r * r * cnst)
+    return 4.0 * consts(np.asarray(v)).PI * _trapezoid(v * dn * r * r * cnst)
 
 
 def _sigmas(functional, cnst, na, nb):
     if functional != PBE:
         return None, None, None
-    ga = d_index(np.asarray(na, float)) / cnst
+    ga = d_index(np.asarray(na)) / cnst
     if nb is None:
         return ga * ga, None, None
-    gb = d_index(np.asarray(nb, float)) / cnst
+    gb = d_index(np.asarray(nb)) / cnst
     return ga * ga, ga * gb, gb * gb
 
 

@@ -1,7 +1,10 @@
 """CPU suite: the NumPy reference of the PW92 / PBE functionals (tests/_gga_ref.py) on its own -- its analytic pieces against complex
 steps, PW92 against the VWN fit of the oracle, the functional-derivative identity of the radial scheme -- and the public constants.
 
-The reference has no GGA, so there is no oracle for PBE: these checks and the GPU ones in test_gpu_gga.py are what it rests on."""
+The reference program has no GGA, so there is no oracle for PBE.  What stands in for one: this NumPy reference, here checked on its
+own and -- evaluated in np.longdouble -- used as the yardstick of the radial kernels in test_gpu_xc_radial.py; test_gpu_gga.py holds
+the pointwise kernels and the SCF to it.  test_stencil_form_rounding records why the difference stencils are written differences
+first."""
 import ctypes as C
 import os
 import re
@@ -101,6 +104,63 @@ def test_functional_derivative_identity(levels, delta):
             F = 2.0 * p["dsigma"] * ga
             wrong = va + 2.0 * F / np.where(r > 0, r, 1.0)
             assert abs(R.potential_integral(r, cnst, wrong, dr) - lhs) > 1e-5 * abs(rhs)
+
+
+LD = np.longdouble
+HEADLINE_GRIDS = [(14, 5e-4, 25.0), (17, 1e-4, 50.0), (20, 1.25e-5, 50.0)]
+
+
+def _neon_lsda(levels, delta, Rmax):
+    r, cnst = R.log_grid(levels, delta, Rmax)
+    rho = R.neon_like(r)
+    return r, cnst, 0.55 * rho, 0.45 * rho
+
+
+@pytest.mark.parametrize("levels,delta,Rmax", HEADLINE_GRIDS)
+def test_stencil_form_rounding(levels, delta, Rmax):
+    """Why d_index (here and in gga.hip) takes differences first.  v_a of a Ne-like LSDA density, fp64 against np.longdouble, largest
+    relative difference over the nodes with rho >= 1e-17 (in the last decade above the 1e-18 threshold v_a is a remainder of
+    cancelling terms and a relative figure says nothing):
+        differences first   1.4e-13 / 4.0e-12 / 3.6e-11   at 16 385 / 131 073 / 1 048 577 nodes   (gate 1e-10)
+        summed by value     1.8e-10 / 6.0e-07 / 3.9e-05                                           (> 1e-7 from 131 073 nodes on)
+    Summed by value, (f[k-2] - 8 f[k-1] + 8 f[k+1] - f[k+2]) / 12 goes through partial sums of size 7 |f| for a result of size
+    delta |f|, and the divergence of the flux divides by delta once more."""
+    assert np.finfo(LD).eps < 1.2e-19, "needs an extended np.longdouble"
+    r, cnst, na, nb = _neon_lsda(levels, delta, Rmax)
+    ext = R.radial(R.PBE, r, cnst, na.astype(LD), nb.astype(LD))[1]
+    assert ext.dtype == LD
+    m = (na + nb) >= 1e-17
+    m[0] = False
+    rel = lambda v: float(np.max(np.abs(v[m] - ext[m]) / np.abs(ext[m])))          # noqa: E731
+    first = rel(R.radial(R.PBE, r, cnst, na, nb)[1])
+    summed = rel(R.radial(R.PBE, r, cnst, na, nb, stencil=R.d_index_sums)[1])
+    print("levels %d: differences first %.2e, summed by value %.2e" % (levels, first, summed))
+    assert first <= 1e-10, first
+    assert summed > 50 * first
+    if levels >= 17:
+        assert summed > 1e-7, summed
+
+
+@pytest.mark.parametrize("levels,delta,Rmax", HEADLINE_GRIDS)
+def test_input_noise_sensitivity_is_recorded(levels, delta, Rmax):
+    """A measurement, no gate on its size: how far one ulp of noise on the input density moves v_a (extended arithmetic throughout, so
+    this is conditioning, not rounding): about 1e-9 / 4e-6 / 2e-3 relative at the three sizes -- a second derivative on a grid
+    of spacing delta amplifies by 1 / delta^2 whatever the stencil's form.  Taken on six windows of N / 16 nodes."""
+    r, cnst, na, nb = _neon_lsda(levels, delta, Rmax)
+    rng = np.random.default_rng(levels)
+    N, worst = r.size, 0.0
+    W = N // 16
+    for start in np.linspace(0, N - W, 6).astype(int):
+        w = slice(start, start + W)
+        a, b = na[w], nb[w]
+        if (a + b).min() < 1e-17:
+            continue
+        a1 = a + np.spacing(a) * rng.integers(-1, 2, a.size)
+        v0 = R.radial(R.PBE, r[w], cnst[w], a.astype(LD), b.astype(LD))[1][8:-8]
+        v1 = R.radial(R.PBE, r[w], cnst[w], a1.astype(LD), b.astype(LD))[1][8:-8]
+        worst = max(worst, float(np.max(np.abs(v1 - v0) / np.abs(v0))))
+    print("levels %d: one ulp of input noise moves v_a by %.1e relative" % (levels, worst))
+    assert worst > 0 and np.isfinite(worst)
 
 
 def test_public_constants():

@@ -1,8 +1,10 @@
 """GPU suite (-m gpu): the PW92 and PBE functionals (gga.h, gga.hip, the PW92 kernels of xc.hip) and their SCF path.
 
-The reference has LDA only, so there is no oracle: the kernels are held to the independent NumPy reference tests/_gga_ref.py
-(energy density in the papers' variables, derivatives by complex steps), to the functional-derivative identity, to batch-against-
-single bit pins, and -- coarsely -- to published PBE total energies.
+The reference program has LDA only, so the compiled oracle does not cover these.  What stands in for it: the independent NumPy
+reference tests/_gga_ref.py (energy density in the papers' variables, derivatives by complex steps) -- here for the pointwise
+kernels, the functional-derivative identity, batch-against-single bit pins and, coarsely, published PBE totals; in
+test_gpu_xc_radial.py, evaluated in extended precision, for the radial kernels at their edges; and in test_gpu_scf_ref.py, plugged
+into the step reference tests/_scf_ref.py, for whole SCF steps.
 """
 import os
 import re

@@ -4,6 +4,8 @@ dfta_scf_create_config).
 The nuclear charge Z stays in the potential and the energies; the electron count N_e sets the flat start density and the multigrid's
 outer boundary U(Rmax) = N_e.  A neutral Aufbau configuration given explicitly must run bit for bit as the default path; a cation
 must carry N_e electrons and see the Coulomb tail -(Z - N_e)/r; fractional occupations must obey Janak's theorem dE/dn_i = eps_i.
+The oracle (tests/_ion_ref.py) takes integer occupations; fractional ones are held step by step to tests/_scf_ref.py, which solves
+every level with the oracle and weights it in NumPy, in test_gpu_scf_ref.py.
 """
 import os
 import re
