@@ -166,14 +166,7 @@ struct dfta_grid {
     double* d_rsrc = nullptr;   // the r factor of the Poisson source: d_r, or FillR's (Rmax i) / (N-1) on a uniform grid (PoissonSolver.cpp:200-210)
 };
 
-template <typename T>
-static inline int dfta_alloc(dfta_ctx* ctx, T** p, size_t count)
-{
-    DFTA_HIP(ctx, hipMalloc(reinterpret_cast<void**>(p), count * sizeof(T)));
-    return DFTA_OK;
-}
-
-// simple RAII device buffer for call-scoped scratch
+// RAII device buffer: call-scoped scratch and the solvers' members (passes where a T* is expected; null while empty)
 template <typename T>
 struct DevBuf {
     T* p = nullptr;
@@ -181,14 +174,33 @@ struct DevBuf {
     DevBuf() = default;
     DevBuf(const DevBuf&) = delete;
     DevBuf& operator=(const DevBuf&) = delete;
-    ~DevBuf() { if (p) (void)hipFree(p); }
+    ~DevBuf() { reset(); }
+    operator T*() const { return p; }
+    void reset() { if (p) (void)hipFree(p); p = nullptr; n = 0; }
     hipError_t alloc(size_t count)
     {
-        if (p) { (void)hipFree(p); p = nullptr; }
+        reset();
         n = count;
         if (count == 0) return hipSuccess;
         return hipMalloc(reinterpret_cast<void**>(&p), count * sizeof(T));
     }
+};
+// owners of an event and of a stream (the holder creates them through .e / .s; null: none)
+struct DevEvent {
+    hipEvent_t e = nullptr;
+    DevEvent() = default;
+    DevEvent(const DevEvent&) = delete;
+    DevEvent& operator=(const DevEvent&) = delete;
+    ~DevEvent() { if (e) (void)hipEventDestroy(e); }
+    operator hipEvent_t() const { return e; }
+};
+struct DevStream {
+    hipStream_t s = nullptr;
+    DevStream() = default;
+    DevStream(const DevStream&) = delete;
+    DevStream& operator=(const DevStream&) = delete;
+    ~DevStream() { if (s) (void)hipStreamDestroy(s); }
+    operator hipStream_t() const { return s; }
 };
 
 // A pointer that reaches a non-inlined device function has no known address space: the compiler emits FLAT loads and stores, which count

@@ -87,13 +87,27 @@ struct Job {
     long long n_points;              // grid points traversed by the sweeps ON the bisection path (n_count + n_zero executed ones) + the match solve
 };
 
+// how the levels of a run were searched (LevelStats::layout, dfta_step_stats::levels_layout: the values are part of the ABI)
+enum LevelLayout {
+    LAYOUT_STATIC = 0,         // host rounds: one static block of trials per job
+    LAYOUT_LATENCY = 1,        // host rounds: latency mode (k_allot re-allots the trial slots among the active jobs)
+    LAYOUT_PACKED = 2,         // host rounds: packed (k_pack)
+    LAYOUT_LATENCY_LIVE = 3,   // host rounds: latency mode over the live jobs of a batch
+    LAYOUT_SCAN = 4,           // the scan search (tolerance mode of the sweeps)
+    LAYOUT_PERSIST = 5,        // the device-side search (persist.inc)
+    LAYOUT_OWN = 6,            // the own-pace search (own.inc)
+};
+
 struct LevelStats {
     int rounds = 0;
     long sweeps_issued = 0;
     long points_traversed = 0;
     float ms_sweep = 0;          // HIP-event time summed over the sweep launches
-    int layout = 0;              // 0 static blocks, 1 latency mode, 2 packed rounds, 3 latency mode over the live jobs of a batch
+    int layout = 0;              // LevelLayout: 0 static blocks, 1 latency mode, 2 packed rounds, 3 latency mode over the live jobs of a batch,
+                                 // 4 scan search, 5 device-side search, 6 own-pace search
 };
+
+struct RunPlan;                  // levels.hip: what one run() has decided, handed from phase to phase
 
 struct LevelSolver {
     dfta_ctx* ctx = nullptr;
@@ -106,49 +120,49 @@ struct LevelSolver {
     bool use_prediction = true;
     int debug_rounds = 0;          // $DFTA_DEBUG_ROUNDS, read once in setup()
     int integ_rule = DFTA_INT_SIMPSON38;   // quadrature of the normalisation integral (the reference calls Simpson38: DFTAtom.cpp:27,51)
-    Job* d_jobs = nullptr;
+    DevBuf<Job> d_jobs;
     std::vector<double> h_occ;     // per job: JobSpec::docc (Job keeps its int occ: persist.inc / own.inc copy Job as 8-byte words)
-    double* d_occ = nullptr;
-    int *d_chain_off = nullptr, *d_chain_off_b = nullptr, *d_v_off = nullptr, *d_slot_v = nullptr, *d_slot_l = nullptr;
-    double2* d_tab = nullptr;
-    double *d_E = nullptr, *d_us = nullptr, *d_us1 = nullptr, *d_u0 = nullptr, *d_phi = nullptr;
-    int *d_limit = nullptr, *d_start = nullptr, *d_count = nullptr, *d_istop = nullptr, *d_trip = nullptr;
-    int *d_wave_kind = nullptr, *d_wave_slot = nullptr, *d_wave_first = nullptr, *d_wave_cnt = nullptr, *d_wave_job = nullptr;
+    DevBuf<double> d_occ;
+    DevBuf<int> d_chain_off, d_chain_off_b, d_v_off, d_slot_v, d_slot_l;
+    DevBuf<double2> d_tab;
+    DevBuf<double> d_E, d_us, d_us1, d_u0, d_phi;
+    DevBuf<int> d_limit, d_start, d_count, d_istop, d_trip;
+    DevBuf<int> d_wave_kind, d_wave_slot, d_wave_first, d_wave_cnt, d_wave_job;
     bool dynamic = false;          // trial slots re-allotted among the active jobs every round (few jobs: latency mode)
     // a static / packed solver whose live jobs have dropped to <= 64 (frozen atoms) runs its rounds in latency mode (k_allot over d_live)
     bool can_switch = false, tables_dirty = false;
     long static_trials = 0, budget_trials = 0;
-    int* d_live = nullptr;
+    DevBuf<int> d_live;
     std::vector<int> h_wave_job, h_wave_slot;
     // packed rounds (batches): the trials of a round laid out job after job inside their (table slot, kind) group by k_pack
     bool packed = false;
     int pack_dmin = 3, pack_dmax = 12, pack_lanes_small = 0, pack_dsmall = 3, pack_lanes_large = 0;
-    int *d_lane_job = nullptr, *d_slot_off = nullptr, *d_slot_jobs = nullptr, *d_gsz = nullptr, *d_goff = nullptr, *d_pack_out = nullptr;
-    unsigned long long* d_counters = nullptr;   // [0] issued trials, [1] traversed points, [2] scratch
-    double *d_Psi = nullptr, *d_Q = nullptr;     // njobs*N each
-    double *d_jE = nullptr, *d_jus = nullptr, *d_jus1 = nullptr;
-    int *d_jslot = nullptr, *d_jl = nullptr, *d_jstart = nullptr, *d_jmp = nullptr;
-    double* d_slot_min = nullptr;   // per table slot: min_i Veff_l(i)
-    double2* d_bounds = nullptr;    // per table slot: fast-division range bounds (numerov.hip)
-    hipEvent_t ev[2] = {nullptr, nullptr};
+    DevBuf<int> d_lane_job, d_slot_off, d_slot_jobs, d_gsz, d_goff, d_pack_out;
+    DevBuf<unsigned long long> d_counters;      // [0] issued trials, [1] traversed points, [2] scratch
+    DevBuf<double> d_Psi, d_Q;                   // njobs*N each
+    DevBuf<double> d_jE, d_jus, d_jus1;
+    DevBuf<int> d_jslot, d_jl, d_jstart, d_jmp;
+    DevBuf<double> d_slot_min;      // per table slot: min_i Veff_l(i)
+    DevBuf<double2> d_bounds;       // per table slot: fast-division range bounds (numerov.hip)
+    DevEvent ev[2];
     // Early match solves (latency mode): a level whose search has ended is matched on a second stream while the remaining levels'
     // last rounds run -- the outer levels, whose outward streams are the long ones, end a round or two before the core levels.
-    hipStream_t st2 = nullptr;
-    hipEvent_t ev_walk = nullptr, ev_early = nullptr, ev_taken = nullptr;
-    int *d_jmatched = nullptr, *d_jstart_keep = nullptr;
-    double* d_snapE = nullptr;          // snapshot of the jobs' eigenvalues / "search ended" flags, taken on the first stream after every walk
-    int *d_snapReady = nullptr, *d_jtake = nullptr;
+    DevStream st2;
+    DevEvent ev_walk, ev_early, ev_taken;
+    DevBuf<int> d_jmatched, d_jstart_keep;
+    DevBuf<double> d_snapE;             // snapshot of the jobs' eigenvalues / "search ended" flags, taken on the first stream after every walk
+    DevBuf<int> d_snapReady, d_jtake;
     bool early_match = false;
     // Tolerance mode of the sweeps (scan.hip; DFTA_SWEEPS_TOLERANCE, set before setup()): interleaved tables per slot, per-lane {min, max}
     int sweep_mode = DFTA_SWEEPS_EXACT;
     dfta_scan_tables scan_tb;
-    int* d_scan_live = nullptr;                   // live jobs of a grouped scan search
-    unsigned long long* d_scan_xch = nullptr;     // 32 words per job: the members' results of a round, two parities
+    DevBuf<int> d_scan_live;                      // live jobs of a grouped scan search
+    DevBuf<unsigned long long> d_scan_xch;        // 32 words per job: the members' results of a round, two parities
     int scan_group = 1;             // workgroups per level of the last scan search (1, 3, 7 or 15)
     int scan_predict = 0;           // $DFTA_DEBUG LEVELS_SCAN_PREDICT (measurements): the scan's first bisection predicts the exact search's first spines
     double scan_predict_factor = 1.5, scan_predict_shift = 0.0;
-    Job* d_jobs_scan = nullptr;     // ... on a copy of the records
-    unsigned long long* d_counters_scan = nullptr;
+    DevBuf<Job> d_jobs_scan;        // ... on a copy of the records
+    DevBuf<unsigned long long> d_counters_scan;
     int scan_fallbacks = 0;         // solves the scan handed back to the exact kernels (a trial it could not decide)
     // Device-side exact search (persist.inc): up to 64 live levels of an un-chained solve on the logarithmic grid run their three bisections in ONE
     // persistent kernel, every level at its own pace; the host rounds of run() remain for everything else and as the fallback
@@ -161,9 +175,9 @@ struct LevelSolver {
     // Own-pace search of a batch (own.inc): more than 64 live levels, one workgroup of W waves per level, one ordinary launch
     bool own_ok = false;
     int own_waves = 2048, own_wmax = 8, own_spine_cap = -1, own_last_W = 0;
-    int* d_own_live = nullptr;
+    DevBuf<int> d_own_live;
     // balanced launch of the fused sweeps (numerov.hip:k_sweep_queue): [0, C) entries per length class, [C] the ticket counter, then C lists of nwaves blocks
-    int* d_queue = nullptr;
+    DevBuf<int> d_queue;
     double tuning[4] = {1e-11, 16e-12, 1.5e-11, 0.25};     // noise band (rel, abs, secant) and the secant's kappa, as set in setup()
     int fixed_point = 1;
     // history bracket of the first spines (Job::hist_c / hist_w): extrapolation with the last movement ratio ($DFTA_DEBUG LEVELS_NOEXTRAP: the
@@ -175,14 +189,25 @@ struct LevelSolver {
     LevelSolver() = default;
     LevelSolver(const LevelSolver&) = delete;
     LevelSolver& operator=(const LevelSolver&) = delete;
-    ~LevelSolver();
-    void release();
+    ~LevelSolver();             // the device buffers, the stream and the events own themselves; scan_tb and pb are destroyed here
     int persist_cap = 256;      // live levels the device-side search takes (LEVELS_PERSIST_WIDE=n: 64 .. 256)
+    // once per solver
     int setup(dfta_ctx* c, const dfta_grid* grid, int mode, int tree_depth, int nV, const std::vector<JobSpec>& specs);
     // frozen (host, njobs, may be null): jobs whose result of the previous run() stands (finished atoms of an SCF batch)
     int run(const double* dV, const double* job_bottom, int run_mode, double* dNewDensity, LevelStats* stats,
             const unsigned char* frozen = nullptr);
     int fetch_jobs(std::vector<Job>& out);
+
+private:
+    // the phases of run(), in their order (levels.hip)
+    void make_plan(RunPlan& p, int run_mode, const unsigned char* frozen) const;
+    void host_round_slots(const RunPlan& p, int k, Job& j) const;
+    void prepare_jobs(RunPlan& p, const double* job_bottom, const unsigned char* frozen) const;
+    void rank_feedback(RunPlan& p);
+    int clamp_job_bottoms(const RunPlan& p), restore_jobs_for_rounds(RunPlan& p);
+    int search_scan(RunPlan& p), predict_scan(RunPlan& p), search_persist(RunPlan& p), search_own(RunPlan& p);
+    int plan_round(const RunPlan& p), early_match_solves(RunPlan& p), search_rounds(RunPlan& p);
+    int finish_wavefunctions(RunPlan& p), fill_stats(RunPlan& p, LevelStats* stats);
 };
 
 }  // namespace dfta

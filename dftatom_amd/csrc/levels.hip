@@ -162,6 +162,7 @@ __global__ void k_plan(dfta::Job* __restrict__ jobs, int njobs, int nopredict, i
 // rest get deeper trees.  Which midpoints are integrated changes; the decisions do not (the walk follows the reference's
 // predicates on whatever nodes it finds).
 constexpr int kPackThreads = 1024;
+constexpr int kMaxRounds = 4096;       // host rounds of one solve
 constexpr int kPackSpineCap = 40;      // decisions of one round's spine (the tree behind it adds d more)
 
 
@@ -615,62 +616,116 @@ __global__ void k_mask_frozen(const dfta::Job* __restrict__ jobs, int njobs, int
 
 namespace dfta {
 
-LevelSolver::~LevelSolver() { release(); }
+// What one run() has decided and what its phases hand to each other: built once at the top of run(), passed to every phase.
+// It OWNS every host buffer that is the source or the target of an asynchronous copy (jobs, live, plive, scan_live, pack_out): such a
+// buffer must live until the synchronisation that follows its copy, and the plan lives in run()'s frame, to the end of the solve.
+struct RunPlan {
+    const double* dV = nullptr;
+    double* dNewDensity = nullptr;
+    bool stats = false;                // the caller wants LevelStats: event pairs around the sweeps, the trip counters
+    bool chained = false;
+    const int* d_chains = nullptr;     // the chain table of this run and its length
+    int run_chains = 0;
+    std::vector<Job> jobs;             // the records of this run as the host prepared them (uploaded; uploaded again by a fall-back)
+    std::vector<int> live;             // the live jobs of a batch with frozen atoms
+    std::vector<int> plive, plevel;    // the levels of the device-side / own-pace search, and each job's index among them (-1: none)
+    std::vector<int> second_share;     // more than nblocks / 2 live levels: the levels that get a second workgroup of their own (the others have one)
+    std::vector<int> scan_live;        // live jobs of the tolerance-mode scan
+    // this run's layout: the solver's own, or -- a batch most of whose atoms have finished (sw) -- latency mode over the live jobs
+    bool sw = false, dyn = false, pk = false, early = false, wide = false, use_persist = false, use_own = false;
+    int own_W = 1, nfrozen = 0;
+    bool carry_cand_hist = true;       // LEVELS_PERSIST_NOBUDGET: off
+    bool scan_wanted = false;          // a live level whose history bracket is still wide (or missing): the batch predictor runs
+    int scan_match_mode = 0;           // the tolerance-mode scan matches (1) and normalises (2) in its own kernel
+    int pack_out[4] = {0, 0, 0, 0};    // k_pack's report on the round it has laid out
+    // what the engine that ran leaves behind for the tail and the statistics
+    bool searched = false;             // an engine has taken every live level to its eigenvalue
+    LevelLayout layout = LAYOUT_STATIC;
+    int rounds = 0;
+    float ms_sweep = 0;
+    bool early_pending = false;        // early match solves are under way on the second stream
+};
 
-void LevelSolver::release()
+namespace {
+
+// setup(): allocate / allocate and upload on the context's stream; false: setup() reports the HIP error
+template <typename T> bool dev_alloc(DevBuf<T>& buf, size_t count) { return buf.alloc(count) == hipSuccess; }
+template <typename T> bool dev_upload(hipStream_t st, DevBuf<T>& buf, const std::vector<T>& vec)
 {
-    void* ptrs[] = {d_jobs, d_occ, d_chain_off, d_chain_off_b, d_v_off, d_slot_v, d_slot_l, d_tab, d_E, d_limit, d_start, d_us, d_us1, d_count,
-                    d_u0, d_phi, d_istop, d_trip, d_wave_job, d_wave_kind, d_wave_slot, d_wave_first, d_wave_cnt, d_counters, d_Psi, d_Q, d_jE, d_jslot, d_jl,
-                    d_jstart, d_jus, d_jus1, d_jmp, d_slot_min, d_bounds};
-    for (void* p : ptrs) if (p) (void)hipFree(p);
-    dfta_scan_tables_destroy(&scan_tb);
-    dfta_persist_destroy(&pb);
-    persist_ok = false;
-    if (d_jobs_scan) (void)hipFree(d_jobs_scan);
-    if (d_counters_scan) (void)hipFree(d_counters_scan);
-    d_jobs_scan = nullptr; d_counters_scan = nullptr;
-    if (d_scan_live) (void)hipFree(d_scan_live);
-    if (d_scan_xch) (void)hipFree(d_scan_xch);
-    d_scan_live = nullptr; d_scan_xch = nullptr;
-    if (d_jmatched) (void)hipFree(d_jmatched);
-    if (d_jstart_keep) (void)hipFree(d_jstart_keep);
-    d_jmatched = nullptr; d_jstart_keep = nullptr;
-    own_ok = false;
-    for (int** q : {&d_lane_job, &d_slot_off, &d_slot_jobs, &d_gsz, &d_goff, &d_pack_out, &d_live, &d_own_live, &d_queue}) { if (*q) (void)hipFree(*q); *q = nullptr; }
-    if (st2) { (void)hipStreamDestroy(st2); st2 = nullptr; }
-    if (ev_walk) { (void)hipEventDestroy(ev_walk); ev_walk = nullptr; }
-    if (ev_early) { (void)hipEventDestroy(ev_early); ev_early = nullptr; }
-    if (ev_taken) { (void)hipEventDestroy(ev_taken); ev_taken = nullptr; }
-    for (void* q : {(void*)d_snapE, (void*)d_snapReady, (void*)d_jtake}) if (q) (void)hipFree(q);
-    d_snapE = nullptr; d_snapReady = nullptr; d_jtake = nullptr;
-    for (hipEvent_t& e : ev) if (e) { (void)hipEventDestroy(e); e = nullptr; }
-    d_jobs = nullptr; d_occ = nullptr; d_chain_off = nullptr; d_chain_off_b = nullptr; d_v_off = nullptr; d_slot_v = nullptr; d_slot_l = nullptr; d_tab = nullptr;
-    d_E = nullptr; d_limit = nullptr; d_start = nullptr; d_us = nullptr; d_us1 = nullptr; d_count = nullptr; d_u0 = nullptr; d_phi = nullptr; d_istop = nullptr; d_trip = nullptr;
-    d_wave_kind = nullptr; d_wave_slot = nullptr; d_wave_first = nullptr; d_wave_cnt = nullptr; d_counters = nullptr; d_wave_job = nullptr;
-    d_Psi = nullptr; d_Q = nullptr; d_jE = nullptr; d_jslot = nullptr; d_jl = nullptr; d_jstart = nullptr; d_jus = nullptr;
-    d_jus1 = nullptr; d_jmp = nullptr; d_slot_min = nullptr; d_bounds = nullptr;
+    return dev_alloc(buf, vec.size()) && hipMemcpyAsync(buf.p, vec.data(), sizeof(T) * vec.size(), hipMemcpyHostToDevice, st) == hipSuccess;
 }
 
-// jobs must be ordered by potential index v (levels of one potential contiguous, in the reference's (N,L) order)
+// $DFTA_DEBUG LEVELS_PERSIST_TRACE: one line per closed round of the device-side search, in the order of the closings: time since the
+// first record [us], level, rounds taken, then what was planned
+void print_persist_trace(const std::vector<unsigned long long>& trace, float ms_kernel)
+{
+    const size_t n = trace.size() / 4;
+    std::vector<size_t> order(n);
+    for (size_t q = 0; q < n; ++q) order[q] = q;
+    std::sort(order.begin(), order.end(), [&](size_t x, size_t y) { return trace[4 * x] < trace[4 * y]; });
+    const unsigned long long t0 = n ? trace[4 * order[0]] : 0;
+    fprintf(stderr, "persist trace: %zu records, kernel %.3f ms\n", n, ms_kernel);
+    for (size_t q : order) {
+        const unsigned long long *w = &trace[4 * q];
+        const int ph = (int)(w[2] >> 56);
+        if (ph == PH_DONE + 1) fprintf(stderr, "  %9.1f us  job %2d round %2d  search ended\n", (w[0] - t0) * 0.01, (int)(w[1] >> 32), (int)(w[1] & 0xffffffff));
+        else if (ph == PH_DONE) fprintf(stderr, "  %9.1f us  job %2d round %2d  DONE (matched, start %llu, candidate %d)\n", (w[0] - t0) * 0.01, (int)(w[1] >> 32), (int)(w[1] & 0xffffffff), w[3] & 0xffffffffull, (int)(signed char)((w[3] >> 32) & 0xff));
+        else fprintf(stderr, "  %9.1f us  job %2d round %2d  next: phase %d done %2d blocks %3d spine %2d capz %5d tcap %5d cand %d/%d\n", (w[0] - t0) * 0.01, (int)(w[1] >> 32),
+                     (int)(w[1] & 0xffffffff), ph, (int)((w[2] >> 32) & 0xff), (int)((w[2] >> 16) & 0xffff), (int)(w[2] & 0xffff), (int)((w[3] >> 32) & 0xffff), (int)(w[3] & 0xffffffff),
+                     (int)((w[3] >> 56) & 0xff), (int)(signed char)((w[3] >> 48) & 0xff));
+    }
+}
+
+// $DFTA_DEBUG DEBUG_ROUNDS: census of the jobs after a host round (phase / decisions taken), stderr
+void print_census(const std::vector<Job>& dbg, int rounds, int debug_rounds)
+{
+    const int njobs = (int)dbg.size();
+    fprintf(stderr, "round %2d |", rounds);
+    for (int q = 0; q < njobs; ++q)
+        if (dbg[q].phase != PH_DONE) fprintf(stderr, " %d:%d/%d", q, dbg[q].phase, dbg[q].phase_done);
+    fprintf(stderr, "\n");
+    if (debug_rounds >= 3)
+        for (int q = 0; q < njobs; ++q) {
+            const Job& J = dbg[q];
+            fprintf(stderr, "   J %2d ph %d done %d l %d boe %.17g toe %.17g top %.17g sc_ok %d sc_lo %.17g sc_hi %.17g spine %d use_sp %d miss %d tcap %d\n",
+                    q, J.phase, J.phase_done, J.l, J.boe, J.toe, J.top, J.sc_ok, J.sc_lo, J.sc_hi, J.spine, J.use_sp, J.miss, J.tcap);
+        }
+    if (debug_rounds >= 2)
+        for (int q = 0; q < njobs; ++q) {
+            const Job& J = dbg[q];
+            if (J.phase != PH_TOP) continue;
+            fprintf(stderr, "   job %2d l=%d w=%.3e ok=%d spine=%d use_sp=%d miss=%d | a: is=%d phi=%.4e  b: is=%s%d phi=%.4e  c: de=%.3e is=%s%d phi=%.4e | pred w/e=%.3e\n",
+                    q, J.l, J.toe - J.boe, J.sc_ok, J.spine, J.use_sp, J.miss, J.sc_is[0], J.sc_phi[0],
+                    (J.sc_is[1] >= 0 && (J.sc_is[1] & kStopOver)) ? "o" : "", J.sc_is[1] < 0 ? -1 : (J.sc_is[1] & ~kStopOver), J.sc_phi[1],
+                    J.sc_e[2] - J.sc_e[0], (J.sc_is[2] >= 0 && (J.sc_is[2] & kStopOver)) ? "o" : "", J.sc_is[2] < 0 ? -1 : (J.sc_is[2] & ~kStopOver), J.sc_phi[2],
+                    J.sc_ok ? (J.toe - J.boe) / (J.sc_hi - J.sc_lo) : 0.0);
+        }
+}
+
+}  // namespace
+
+LevelSolver::~LevelSolver()
+{
+    dfta_scan_tables_destroy(&scan_tb);
+    dfta_persist_destroy(&pb);
+}
+
+// Once per solver.  jobs must be ordered by potential index v (levels of one potential contiguous, in the reference's (N,L) order)
 int LevelSolver::setup(dfta_ctx* c, const dfta_grid* grid, int mode_, int tree_depth, int nV_, const std::vector<JobSpec>& specs)
 {
-    release();
     ctx = c; g = grid; mode = mode_; nV = nV_;
     use_prediction = dfta_knob("LEVELS_NOPREDICT") == nullptr;   // measurements / tests: every spine and scout off
     {   // tuning of the predictions (never of a result): the defaults, or what the environment says, every time a solver is made
-        double v[3] = {1e-11, 16e-12, 1.5e-11}, k = 0.25;
-        if (const char* e = dfta_knob("LEVELS_NOISE")) sscanf(e, "%lf:%lf:%lf", &v[0], &v[1], &v[2]);   // "rel:abs:secant" of the noise band (':' -- the knob list itself is comma-separated)
+        if (const char* e = dfta_knob("LEVELS_NOISE")) sscanf(e, "%lf:%lf:%lf", &tuning[0], &tuning[1], &tuning[2]);   // "rel:abs:secant" of the noise band (':' -- the knob list itself is comma-separated)
         hist_extrapolate = dfta_knob("LEVELS_NOEXTRAP") == nullptr;
         if (const char* e = dfta_knob("LEVELS_EXTRAP")) sscanf(e, "%lf:%lf", &hist_kA, &hist_kB);
-        if (const char* e = dfta_knob("LEVELS_SECANT_KAPPA")) k = atof(e);                                // trust in the parabolic correction
-        (void)hipMemcpyToSymbol(HIP_SYMBOL(g_noise_rel), &v[0], sizeof(double));
-        (void)hipMemcpyToSymbol(HIP_SYMBOL(g_noise_abs), &v[1], sizeof(double));
-        (void)hipMemcpyToSymbol(HIP_SYMBOL(g_secant_noise), &v[2], sizeof(double));
-        (void)hipMemcpyToSymbol(HIP_SYMBOL(g_secant_kappa), &k, sizeof(double));
-        const int fp = dfta_knob("LEVELS_NOFIXEDPOINT") ? 0 : 1;
-        (void)hipMemcpyToSymbol(HIP_SYMBOL(g_fixed_point), &fp, sizeof(int));
-        tuning[0] = v[0]; tuning[1] = v[1]; tuning[2] = v[2]; tuning[3] = k;
-        fixed_point = fp;
+        if (const char* e = dfta_knob("LEVELS_SECANT_KAPPA")) tuning[3] = atof(e);                              // trust in the parabolic correction
+        (void)hipMemcpyToSymbol(HIP_SYMBOL(g_noise_rel), &tuning[0], sizeof(double));
+        (void)hipMemcpyToSymbol(HIP_SYMBOL(g_noise_abs), &tuning[1], sizeof(double));
+        (void)hipMemcpyToSymbol(HIP_SYMBOL(g_secant_noise), &tuning[2], sizeof(double));
+        (void)hipMemcpyToSymbol(HIP_SYMBOL(g_secant_kappa), &tuning[3], sizeof(double));
+        fixed_point = dfta_knob("LEVELS_NOFIXEDPOINT") ? 0 : 1;
+        (void)hipMemcpyToSymbol(HIP_SYMBOL(g_fixed_point), &fixed_point, sizeof(int));
     }
     debug_rounds = dfta_knob("DEBUG_ROUNDS") ? atoi(dfta_knob("DEBUG_ROUNDS")) : 0;
     njobs = static_cast<int>(specs.size());
@@ -754,7 +809,6 @@ int LevelSolver::setup(dfta_ctx* c, const dfta_grid* grid, int mode_, int tree_d
     h_jobs_template = jobs;
     nslots = static_cast<int>(slot_v.size());
     if (packed) {
-        pack_dmin = 3; pack_dmax = 12;
         pack_lanes_small = std::max(ctx->num_cu, 64) * 64;   // one pass of one block per compute unit: the pipelined kernel's regime
         pack_dsmall = 3;                                     // ... as long as that leaves every job a tree of this depth
         pack_lanes_large = 131072;                   // two waves per SIMD of the fused kernel
@@ -774,9 +828,7 @@ int LevelSolver::setup(dfta_ctx* c, const dfta_grid* grid, int mode_, int tree_d
     if (own_ok) {
         own_waves = 2048;                            // two waves per SIMD: what the sweep's registers (177 VGPRs) leave resident
         if (const char* e = dfta_knob("LEVELS_OWN_WAVES")) own_waves = std::max(64, atoi(e));      // measurements
-        own_wmax = 8;
         if (const char* e = dfta_knob("LEVELS_OWN_WMAX")) own_wmax = std::min(8, std::max(1, atoi(e)));
-        own_spine_cap = -1;
         if (const char* e = dfta_knob("LEVELS_OWN_SPINE_CAP")) own_spine_cap = atoi(e);
         ntrials = std::max<long>(ntrials, 64L * std::max<long>(own_waves, njobs));
     }
@@ -794,65 +846,50 @@ int LevelSolver::setup(dfta_ctx* c, const dfta_grid* grid, int mode_, int tree_d
     }
     h_wave_job = wave_job;
     h_wave_slot = wave_slot;
-    tables_dirty = false;
 
     hipStream_t st = ctx->stream;
-#define ALLOC(ptr, type, count) DFTA_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&ptr), sizeof(type) * (size_t)(count)))
-#define UPLOAD(ptr, vec) DFTA_HIP(ctx, hipMemcpyAsync(ptr, vec.data(), sizeof(vec[0]) * vec.size(), hipMemcpyHostToDevice, st))
-    ALLOC(d_jobs, Job, njobs);
+    auto no_memory = [&]() { snprintf(ctx->err, sizeof(ctx->err), "level solver: device buffers -> %s", hipGetErrorString(hipGetLastError())); return (int)DFTA_ERR_HIP; };
     h_occ.resize(njobs);
     for (int k = 0; k < njobs; ++k) h_occ[k] = specs[k].docc;
-    ALLOC(d_occ, double, njobs); UPLOAD(d_occ, h_occ);
-    ALLOC(d_chain_off, int, chain_off.size()); UPLOAD(d_chain_off, chain_off);
-    ALLOC(d_chain_off_b, int, chain_off_b.size()); UPLOAD(d_chain_off_b, chain_off_b);
-    ALLOC(d_v_off, int, v_off.size()); UPLOAD(d_v_off, v_off);
-    ALLOC(d_slot_v, int, nslots); UPLOAD(d_slot_v, slot_v);
-    ALLOC(d_slot_l, int, nslots); UPLOAD(d_slot_l, slot_l);
-    ALLOC(d_tab, double2, (size_t)nslots * N);
-    ALLOC(d_E, double, ntrials); ALLOC(d_limit, int, ntrials); ALLOC(d_start, int, ntrials);
-    ALLOC(d_us, double, ntrials); ALLOC(d_us1, double, ntrials); ALLOC(d_count, int, ntrials); ALLOC(d_u0, double, ntrials); ALLOC(d_phi, double, ntrials); ALLOC(d_istop, int, ntrials); ALLOC(d_trip, int, ntrials);
-    ALLOC(d_wave_kind, int, nwaves);
-    ALLOC(d_wave_slot, int, nwaves); UPLOAD(d_wave_slot, wave_slot);
-    ALLOC(d_wave_first, int, nwaves); UPLOAD(d_wave_first, wave_first);
-    ALLOC(d_wave_cnt, int, nwaves); UPLOAD(d_wave_cnt, wave_cnt);
-    ALLOC(d_wave_job, int, nwaves); UPLOAD(d_wave_job, wave_job);
-    if (packed) {
+    const size_t nt = (size_t)ntrials;
+    bool ok = dev_alloc(d_jobs, njobs) && dev_upload(st, d_occ, h_occ) && dev_upload(st, d_chain_off, chain_off) && dev_upload(st, d_chain_off_b, chain_off_b) &&
+              dev_upload(st, d_v_off, v_off) && dev_upload(st, d_slot_v, slot_v) && dev_upload(st, d_slot_l, slot_l) && dev_alloc(d_tab, (size_t)nslots * N) &&
+              dev_alloc(d_E, nt) && dev_alloc(d_limit, nt) && dev_alloc(d_start, nt) && dev_alloc(d_us, nt) && dev_alloc(d_us1, nt) &&
+              dev_alloc(d_count, nt) && dev_alloc(d_u0, nt) && dev_alloc(d_phi, nt) && dev_alloc(d_istop, nt) && dev_alloc(d_trip, nt) &&
+              dev_alloc(d_wave_kind, nwaves) && dev_upload(st, d_wave_slot, wave_slot) && dev_upload(st, d_wave_first, wave_first) &&
+              dev_upload(st, d_wave_cnt, wave_cnt) && dev_upload(st, d_wave_job, wave_job);
+    if (ok && packed) {
         std::vector<int> slot_off(nslots + 1, 0), slot_jobs(njobs);
         for (int k = 0; k < njobs; ++k) slot_off[jobs[k].slot + 1]++;
         for (int q = 0; q < nslots; ++q) slot_off[q + 1] += slot_off[q];
         std::vector<int> fill(slot_off.begin(), slot_off.end() - 1);
         for (int k = 0; k < njobs; ++k) slot_jobs[fill[jobs[k].slot]++] = k;
-        ALLOC(d_slot_off, int, nslots + 1); UPLOAD(d_slot_off, slot_off);
-        ALLOC(d_slot_jobs, int, njobs); UPLOAD(d_slot_jobs, slot_jobs);
-        ALLOC(d_gsz, int, 2 * nslots); ALLOC(d_goff, int, 2 * nslots);
-        ALLOC(d_lane_job, int, ntrials);
-        ALLOC(d_pack_out, int, 4);
-        DFTA_HIP(ctx, hipStreamSynchronize(st));     // the vectors above are the sources of the copies
+        ok = dev_upload(st, d_slot_off, slot_off) && dev_upload(st, d_slot_jobs, slot_jobs) && dev_alloc(d_gsz, 2 * (size_t)nslots) &&
+             dev_alloc(d_goff, 2 * (size_t)nslots) && dev_alloc(d_lane_job, nt) && dev_alloc(d_pack_out, 4);
+        if (ok) DFTA_HIP(ctx, hipStreamSynchronize(st));     // the vectors above are the sources of the copies
     }
-    ALLOC(d_counters, unsigned long long, 4);
+    if (!ok || !dev_alloc(d_counters, 4)) return no_memory();
     // the device-side search takes up to 256 live levels: one workgroup per level and compute unit, two for as many levels as there are
     // compute units left (all of them up to 128 levels), the rest in the pool; LEVELS_PERSIST_WIDE=n: up to 64 <= n <= 256 levels (64: one
     // atom's worth, round 5 -- larger batches then run host rounds)
-    persist_cap = 256;
     if (const char* e = dfta_knob("LEVELS_PERSIST_WIDE")) persist_cap = std::min(256, std::max(64, atoi(e)));
     if (persist_ok) { const int prc = dfta_persist_create(ctx, g, std::min(njobs, persist_cap), &pb); if (prc) return prc; }
-    if (can_switch) ALLOC(d_live, int, 64);
-    if (!g->uniform && dfta_knob("LEVELS_NOQUEUE") == nullptr) ALLOC(d_queue, int, kSweepQueueClasses + 1 + (size_t)kSweepQueueClasses * nwaves);
-    if (own_ok) ALLOC(d_own_live, int, njobs);
-    ALLOC(d_Psi, double, (size_t)njobs * N);
-    ALLOC(d_Q, double, (size_t)njobs * N);
-    ALLOC(d_jE, double, njobs); ALLOC(d_jslot, int, njobs); ALLOC(d_jl, int, njobs); ALLOC(d_jstart, int, njobs);
-    ALLOC(d_jmatched, int, njobs); ALLOC(d_jstart_keep, int, njobs);
-    ALLOC(d_snapE, double, njobs); ALLOC(d_snapReady, int, njobs); ALLOC(d_jtake, int, njobs);
+    ok = (!can_switch || dev_alloc(d_live, 64)) &&
+         (g->uniform || dfta_knob("LEVELS_NOQUEUE") != nullptr || dev_alloc(d_queue, kSweepQueueClasses + 1 + (size_t)kSweepQueueClasses * nwaves)) &&
+         (!own_ok || dev_alloc(d_own_live, njobs)) && dev_alloc(d_Psi, (size_t)njobs * N) && dev_alloc(d_Q, (size_t)njobs * N) &&
+         dev_alloc(d_jE, njobs) && dev_alloc(d_jslot, njobs) && dev_alloc(d_jl, njobs) && dev_alloc(d_jstart, njobs) &&
+         dev_alloc(d_jmatched, njobs) && dev_alloc(d_jstart_keep, njobs) && dev_alloc(d_snapE, njobs) && dev_alloc(d_snapReady, njobs) &&
+         dev_alloc(d_jtake, njobs);
+    if (!ok) return no_memory();
     if (early_match) {
-        DFTA_HIP(ctx, hipStreamCreateWithFlags(&st2, hipStreamNonBlocking));
-        DFTA_HIP(ctx, hipEventCreateWithFlags(&ev_walk, hipEventDisableTiming));
-        DFTA_HIP(ctx, hipEventCreateWithFlags(&ev_early, hipEventDisableTiming));
-        DFTA_HIP(ctx, hipEventCreateWithFlags(&ev_taken, hipEventDisableTiming));
+        DFTA_HIP(ctx, hipStreamCreateWithFlags(&st2.s, hipStreamNonBlocking));
+        DFTA_HIP(ctx, hipEventCreateWithFlags(&ev_walk.e, hipEventDisableTiming));
+        DFTA_HIP(ctx, hipEventCreateWithFlags(&ev_early.e, hipEventDisableTiming));
+        DFTA_HIP(ctx, hipEventCreateWithFlags(&ev_taken.e, hipEventDisableTiming));
     }
-    ALLOC(d_jus, double, njobs); ALLOC(d_jus1, double, njobs); ALLOC(d_jmp, int, njobs);
-    ALLOC(d_slot_min, double, nslots);
-    ALLOC(d_bounds, double2, (size_t)nslots * dfta_bounds_stride(g));
+    ok = dev_alloc(d_jus, njobs) && dev_alloc(d_jus1, njobs) && dev_alloc(d_jmp, njobs) && dev_alloc(d_slot_min, nslots) &&
+         dev_alloc(d_bounds, (size_t)nslots * dfta_bounds_stride(g));
+    if (!ok) return no_memory();
     // Round 6: the scan search (scan.hip: 40 - 60 us per sweep instead of 4 ms) runs the FIRST bisection of every live level ahead of the
     // device-side exact search and hands its end point to plan_round as the bracket of the exact search's first spine -- speculation only,
     // as the history bracket it replaces: the exact sweeps at the reference's midpoints take every decision.  One atom / a few atoms
@@ -862,20 +899,16 @@ int LevelSolver::setup(dfta_ctx* c, const dfta_grid* grid, int mode_, int tree_d
     scan_predict = (sweep_mode != DFTA_SWEEPS_TOLERANCE && dfta_scan_supported(g) && dfta_knob("LEVELS_NOSCANPREDICT") == nullptr && use_prediction &&
                     mode == DFTA_LEVELS_BATCHED && tree_depth <= 0 &&
                     ((persist_ok && dynamic) || (!dynamic && (size_t)nslots * N * sizeof(double) <= ((size_t)2 << 30) && dfta_knob("LEVELS_NOSCANPREDICT_BATCH") == nullptr))) ? 1 : 0;
-    scan_predict_factor = 1.5; scan_predict_shift = 0.0;
     if (const char* e = dfta_knob("LEVELS_SCAN_PREDICT_W")) scan_predict_factor = atof(e);
     if (const char* e = dfta_knob("LEVELS_SCAN_PREDICT_SHIFT")) scan_predict_shift = atof(e);
-    if (scan_predict) { ALLOC(d_jobs_scan, Job, njobs); ALLOC(d_counters_scan, unsigned long long, 4); }
+    if (scan_predict && !(dev_alloc(d_jobs_scan, njobs) && dev_alloc(d_counters_scan, 4))) return no_memory();
     if ((sweep_mode == DFTA_SWEEPS_TOLERANCE || scan_predict) && dfta_scan_supported(g)) {      // scan.hip: interleaved tables + per-lane {min, max}
         const int trc = dfta_scan_tables_create(ctx, g, nslots, &scan_tb);
         if (trc) return trc;
-        ALLOC(d_scan_live, int, njobs);
-        ALLOC(d_scan_xch, unsigned long long, 32 * (size_t)njobs);
+        if (!(dev_alloc(d_scan_live, njobs) && dev_alloc(d_scan_xch, 32 * (size_t)njobs))) return no_memory();
     }
-#undef ALLOC
-#undef UPLOAD
-    DFTA_HIP(ctx, hipEventCreate(&ev[0]));
-    DFTA_HIP(ctx, hipEventCreate(&ev[1]));
+    DFTA_HIP(ctx, hipEventCreate(&ev[0].e));
+    DFTA_HIP(ctx, hipEventCreate(&ev[1].e));
     DFTA_HIP(ctx, hipMemsetAsync(d_count, 0, sizeof(int) * ntrials, st));
     DFTA_HIP(ctx, hipMemsetAsync(d_u0, 0, sizeof(double) * ntrials, st));
     DFTA_HIP(ctx, hipMemsetAsync(d_trip, 0, sizeof(int) * ntrials, st));
@@ -883,79 +916,79 @@ int LevelSolver::setup(dfta_ctx* c, const dfta_grid* grid, int mode_, int tree_d
     return DFTA_OK;
 }
 
-// Solve all levels for the potentials dV (device, nV*N).
-//   job_bottom (host, njobs): BottomEnergy at entry of LocateInterval for every job.  CHAINED uses only the entry
-//   of the first job of each potential (-Z^2-1, DFTAtom.cpp:407) and hands E-3 from level to level (DFTAtom.cpp:541);
-//   BATCHED starts every level from its own entry (the caller's hint: E_{k-1} of the previous SCF step - 3).
-int LevelSolver::run(const double* dV, const double* job_bottom, int run_mode, double* dNewDensity, LevelStats* stats,
-                     const unsigned char* frozen)
+// What this run does: the layout of its host rounds and the engines that may run ahead of them (no HIP call)
+void LevelSolver::make_plan(RunPlan& p, int run_mode, const unsigned char* frozen) const
 {
-    if (njobs == 0) return DFTA_OK;
-    const int N = g->N;
-    hipStream_t st = ctx->stream;
-    const bool chained = (run_mode == DFTA_LEVELS_CHAINED);
-    const int* d_chains = chained ? d_chain_off : d_chain_off_b;
-    const int run_chains = chained ? nchains_chained : njobs;
-    std::vector<Job> jobs = h_jobs_template;
-    int nfrozen = 0;
-    bool scan_wanted = false;          // a live level whose history bracket is still wide (or missing): the batch predictor runs
+    p.chained = (run_mode == DFTA_LEVELS_CHAINED);
+    p.d_chains = p.chained ? d_chain_off : d_chain_off_b;
+    p.run_chains = p.chained ? nchains_chained : njobs;
+    const bool have_last = h_last.size() == (size_t)njobs;
     // this run's layout: the solver's own, or -- a batch most of whose atoms have finished -- latency mode over the live jobs
-    std::vector<int> live;
-    if (frozen && h_last.size() == jobs.size())
-        for (int k = 0; k < njobs; ++k) if (!frozen[k]) live.push_back(k);
-    const bool sw = can_switch && !chained && frozen && h_last.size() == jobs.size() && !live.empty() && live.size() <= 64;
-    const bool dyn = dynamic || sw;
-    const bool pk = packed && !sw;
-    const bool early = early_match && dyn;
+    if (frozen && have_last)
+        for (int k = 0; k < njobs; ++k) if (!frozen[k]) p.live.push_back(k);
+    p.sw = can_switch && !p.chained && frozen && have_last && !p.live.empty() && p.live.size() <= 64;
+    p.dyn = dynamic || p.sw;
+    p.pk = packed && !p.sw;
+    p.early = early_match && p.dyn;
+    p.layout = p.sw ? LAYOUT_LATENCY_LIVE : (dynamic ? LAYOUT_LATENCY : (p.pk ? LAYOUT_PACKED : LAYOUT_STATIC));      // of the host rounds; an engine that runs instead says so
     // the live levels of a latency-mode run search on the device, each at its own pace (persist.inc), when every one of them can have two
-    // 64-trial blocks of its own; the host rounds below are the fallback
-    std::vector<int> plive;
-    if (sw) plive = live;
-    else for (int k = 0; k < njobs; ++k) if (!(frozen && frozen[k] && h_last.size() == jobs.size())) plive.push_back(k);
+    // 64-trial blocks of its own; the host rounds are the fallback
+    if (p.sw) p.plive = p.live;
+    else for (int k = 0; k < njobs; ++k) if (!(frozen && frozen[k] && have_last)) p.plive.push_back(k);
+    const int nplive = (int)p.plive.size();
     // (wide: 65 .. persist_cap live levels of a batch whose host rounds -- the fallback -- are the solver's own static / packed layout)
-    const bool wide = !dyn && !own_ok && persist_cap > 64 && (int)plive.size() > 64;          // (LEVELS_OWN: that search was asked for)
-    const bool use_persist = persist_ok && (dyn || wide) && !chained && sweep_mode != DFTA_SWEEPS_TOLERANCE && !plive.empty() && (int)plive.size() <= pb.nlive_cap &&
-                             pb.nblocks / (int)plive.size() >= (persist_cap > 128 ? 1 : 2) && debug_rounds == 0;
+    p.wide = !p.dyn && !own_ok && persist_cap > 64 && nplive > 64;          // (LEVELS_OWN: that search was asked for)
+    p.use_persist = persist_ok && (p.dyn || p.wide) && !p.chained && sweep_mode != DFTA_SWEEPS_TOLERANCE && nplive > 0 && nplive <= pb.nlive_cap &&
+                    pb.nblocks / nplive >= (persist_cap > 128 ? 1 : 2) && debug_rounds == 0;
     // more than 64 live levels: every level at its own pace all the same, one workgroup of W waves each in ONE ordinary launch (own.inc)
-    const bool use_own = own_ok && !dyn && !chained && sweep_mode != DFTA_SWEEPS_TOLERANCE && !plive.empty() && debug_rounds == 0;
-    int own_W = 1;
-    if (use_own) { while (own_W < own_wmax && (long)plive.size() * own_W * 2 <= own_waves) own_W *= 2; }
-    std::vector<int> plevel(njobs, -1);
-    if (use_persist || use_own) for (size_t q = 0; q < plive.size(); ++q) plevel[plive[q]] = (int)q;
-    if (sw) {
-        DFTA_HIP(ctx, hipMemcpyAsync(d_live, live.data(), sizeof(int) * live.size(), hipMemcpyHostToDevice, st));
-        tables_dirty = true;
-    } else if (tables_dirty && !use_own) {           // back from latency mode / the own-pace search: the solver's own block tables
-        DFTA_HIP(ctx, hipMemcpyAsync(d_wave_job, h_wave_job.data(), sizeof(int) * h_wave_job.size(), hipMemcpyHostToDevice, st));
-        DFTA_HIP(ctx, hipMemcpyAsync(d_wave_slot, h_wave_slot.data(), sizeof(int) * h_wave_slot.size(), hipMemcpyHostToDevice, st));
-        tables_dirty = false;
-    }
+    p.use_own = own_ok && !p.dyn && !p.chained && sweep_mode != DFTA_SWEEPS_TOLERANCE && nplive > 0 && debug_rounds == 0;
+    if (p.use_own) { while (p.own_W < own_wmax && (long)nplive * p.own_W * 2 <= own_waves) p.own_W *= 2; }
+    p.plevel.assign(njobs, -1);
+    if (p.use_persist || p.use_own) for (int q = 0; q < nplive; ++q) p.plevel[p.plive[q]] = q;
+    p.carry_cand_hist = dfta_knob("LEVELS_PERSIST_NOBUDGET") == nullptr;
+    // the match solve and the normalisation in the scan's own kernel (SCAN_NOMATCH: the exact k_match / k_normalize follow, measurements)
+    p.scan_match_mode = dfta_knob("SCAN_NOMATCH") ? 0 : (integ_rule == DFTA_INT_SIMPSON38 ? 2 : 1);
+}
+
+// Trial slots of job k in the host rounds: its own static block; packed rounds: k_pack lays the trials out (latency mode: k_allot)
+void LevelSolver::host_round_slots(const RunPlan& p, int k, Job& j) const
+{
+    j.tbase = (p.pk || p.sw) ? 0 : k * tpj;
+    j.tcap = (p.pk || p.sw) ? 0 : tpj;
+}
+
+// The records of this run (p.jobs) from the template, the frozen mask, the previous solve's records (h_last) and the bracket bottoms:
+// path predictions, history brackets, scan_wanted, the candidate budget.  Host arithmetic only.
+void LevelSolver::prepare_jobs(RunPlan& p, const double* job_bottom, const unsigned char* frozen) const
+{
+    std::vector<Job>& jobs = p.jobs;
+    jobs = h_jobs_template;
+    const bool have_last = h_last.size() == jobs.size();
     for (int k = 0; k < njobs; ++k) {
         Job& j = jobs[k];
-        if (frozen && frozen[k] && h_last.size() == jobs.size()) {
+        if (frozen && frozen[k] && have_last) {
             j = h_last[k];             // E, interval, convergence flag, match point, history: as the last solve left them
             j.phase = PH_DONE;
             j.frozen = 1;
             j.spine = 0;
             j.capz = 0;
-            ++nfrozen;
+            ++p.nfrozen;
             continue;
         }
         j.frozen = 0;
-        j.tbase = (pk || sw) ? 0 : k * tpj;      // packed rounds: k_pack lays the trials out (latency mode: k_allot)
-        j.tcap = (pk || sw) ? 0 : tpj;
-        if (use_persist) { j.tbase = plevel[k] * pb.tmax; j.tcap = 0; }      // its own region of the device-side search's trial arrays
-        if (use_own) { j.tbase = plevel[k] * 64 * own_W; j.tcap = 64 * own_W; }
+        host_round_slots(p, k, j);
+        if (p.use_persist) { j.tbase = p.plevel[k] * pb.tmax; j.tcap = 0; }      // its own region of the device-side search's trial arrays
+        if (p.use_own) { j.tbase = p.plevel[k] * 64 * p.own_W; j.tcap = 64 * p.own_W; }
         j.rounds = 0;
         j.t_end_us = 0;
         j.deep = -1;
-        j.cand_hist = (use_prediction && h_last.size() == jobs.size() && dfta_knob("LEVELS_PERSIST_NOBUDGET") == nullptr) ? h_last[k].cand_hist : 0;
+        j.cand_hist = (use_prediction && have_last && p.carry_cand_hist) ? h_last[k].cand_hist : 0;
         j.bottom0 = job_bottom[k];
         const bool first = (k == 0 || jobs[k].v != jobs[k - 1].v);
-        if (!chained || first) { j.phase = PH_TOP; j.toe = 50; j.boe = j.bottom0; }   // DFTAtom.cpp:499
+        if (!p.chained || first) { j.phase = PH_TOP; j.toe = 50; j.boe = j.bottom0; }   // DFTAtom.cpp:499
         else j.phase = PH_WAIT;
         // path prediction from the previous solve of the same job list (speculation only)
-        if (use_prediction && h_last.size() == jobs.size()) {
+        if (use_prediction && have_last) {
             for (int ph = 0; ph < 3; ++ph) {
                 j.pred_bits[ph] = h_last[k].cur_bits[ph];
                 j.pred_len[ph] = h_last[k].cur_len[ph];
@@ -988,404 +1021,447 @@ int LevelSolver::run(const double* dV, const double* job_bottom, int run_mode, d
         }
         {   // does this level still want the scan predictor of its first spine?  (scan.hip:k_scan_levels: the same rule, per level)
             const double T = j.hist_c[0], band = 6e-11 * fabs(T) + 6e-10;
-            if (!(j.hist_ok >= 2 && j.hist_d[0] >= 0 && j.hist_w[0] + 1e-10 * fabs(T) + 64e-12 <= 4096. * band)) scan_wanted = true;
+            if (!(j.hist_ok >= 2 && j.hist_d[0] >= 0 && j.hist_w[0] + 1e-10 * fabs(T) + 64e-12 <= 4096. * band)) p.scan_wanted = true;
         }
-        j.miss = 0;
-        j.capz = 0;
-        j.se_state = 0;
-        j.se_stop = 0;
-        j.se_sl = 0;
-        j.se_tok = 0;
+        j.miss = j.capz = j.se_state = j.se_stop = j.se_sl = j.se_tok = j.sc_ok = j.use_sp = j.sp_len = j.phase_done = 0;
         j.se_plo = j.se_phi = NAN;
         j.sc_is[0] = j.sc_is[1] = j.sc_is[2] = -1;
-        j.sc_ok = 0;
-        j.use_sp = 0;
-        j.sp_len = 0;
         j.sp_bits = 0;
-        j.spine = 0;           // planned on the device (k_plan below), after the bottoms have been clamped
-        j.phase_done = 0;
+        j.spine = 0;           // planned on the device (k_plan), after the bottoms have been clamped
     }
-    persist_deep_reserve = 0;
-    std::vector<int> second_share;          // more than nblocks / 2 live levels: the levels that get a second workgroup of their own (the others have one)
-    if (use_persist && h_last.size() == jobs.size() && !pb.equal_shares) {
-        // Feedback (speculation only): the levels whose search ended last in the previous step get first call on the pool (persist_plan,
-        // deep = 2: as many as the pool can give a second share to), those within 15 % of the last one may match candidate eigenvalues
-        // (deep = 1), the rest have time to spare (deep = 0)
-        // (ranked by the maximum over the last three steps: a level that gets its deeper trees ends earlier, and a one-step memory would
-        // take them away again in the next step)
-        if (persist_tend.size() != 3 * jobs.size()) persist_tend.assign(3 * jobs.size(), 0);
-        for (int k : plive) {
-            int* h = &persist_tend[3 * (size_t)k];
-            if (h_last[k].t_end_us > 0) { h[2] = h[1]; h[1] = h[0]; h[0] = h_last[k].t_end_us; }
-        }
-        auto score = [&](int k) { const int* h = &persist_tend[3 * (size_t)k]; return std::max(h[0], std::max(h[1], h[2])); };
-        std::vector<int> order;
-        for (int k : plive) if (score(k) > 0) order.push_back(k);
-        if (order.size() == plive.size()) {
-            std::sort(order.begin(), order.end(), [&](int x, int y) { return score(x) > score(y); });
-            const int equal = pb.nblocks / (int)plive.size();
-            if (equal == 1) second_share.assign(order.begin(), order.begin() + std::min<size_t>(order.size(), pb.nblocks - (int)plive.size()));
-            int pool = pb.nblocks - equal * (int)plive.size();
-            for (int k : plive) if (jobs[k].nodes == 0 && equal >= 8) pool += equal / 2;
-            const int ndeep = std::min<int>((int)order.size(), pool / std::max(equal - 1, 1));
-            persist_deep_reserve = ndeep * (equal - 1);
-            const int tmax_us = score(order[0]);
-            for (size_t q = 0; q < order.size(); ++q)
-                jobs[order[q]].deep = (int)q < ndeep ? 2 : (score(order[q]) > 0.85 * tmax_us ? 1 : 0);
-            if (pb.want_trace) {
-                fprintf(stderr, "persist feedback: pool %d, reserve %d; search ends of the previous step [us]:", pool, persist_deep_reserve);
-                for (size_t q = 0; q < order.size(); ++q) fprintf(stderr, " %d:%d%s", order[q], score(order[q]), jobs[order[q]].deep == 2 ? "*" : "");
-                fprintf(stderr, "\n");
-            }
-        }
-    }
-    DFTA_HIP(ctx, hipMemcpyAsync(d_jobs, jobs.data(), sizeof(Job) * njobs, hipMemcpyHostToDevice, st));
-    DFTA_HIP(ctx, hipMemsetAsync(d_counters, 0, sizeof(unsigned long long) * 4, st));
-    DFTA_HIP(ctx, hipMemsetAsync(d_jmatched, 0, sizeof(int) * njobs, st));
-    if (nfrozen == njobs) {            // nothing to solve: Psi, density contributions and job records stand
-        DFTA_HIP(ctx, hipStreamSynchronize(st));      // `jobs` is the source of the copy above
-        if (stats) *stats = LevelStats();
-        return DFTA_OK;
-    }
-    int rc = dfta_launch_build_tab(ctx, g, d_tab, dV, d_slot_v, d_slot_l, nslots, d_bounds);
-    if (rc) return rc;
-    if (!chained && clamp_bottoms) {
-        hipLaunchKernelGGL(k_slot_min, dim3(nslots), dim3(1024), 0, st, d_tab, N, d_slot_min);
-        DFTA_CHECK_LAUNCH(ctx);
-        hipLaunchKernelGGL(k_clamp_bottoms, dim3((njobs + 63) / 64), dim3(64), 0, st, d_jobs, njobs, d_slot_min);
-        DFTA_CHECK_LAUNCH(ctx);
-    }
+}
 
-    auto plan = [&]() -> int {          // spines (and, in latency mode, the slots) of the next round
-        if (dyn)
-            hipLaunchKernelGGL(k_allot, dim3(1), dim3(64), 0, st, d_jobs, sw ? (int)live.size() : njobs, (int)budget_trials, use_prediction ? 0 : 1, d_wave_job,
-                               d_wave_slot, sw ? d_live : nullptr);
-        else
-            hipLaunchKernelGGL(k_plan, dim3((njobs + 63) / 64), dim3(64), 0, st, d_jobs, njobs, use_prediction ? 0 : 1, pk ? (1 << 14) : 0);
+// Feedback of the device-side search (speculation only): the levels whose search ended last in the previous step get first call on the pool
+// (persist_plan, deep = 2: as many as the pool can give a second share to), those within 15 % of the last one may match candidate
+// eigenvalues (deep = 1), the rest have time to spare (deep = 0)
+// (ranked by the maximum over the last three steps: a level that gets its deeper trees ends earlier, and a one-step memory would take
+// them away again in the next step)
+void LevelSolver::rank_feedback(RunPlan& p)
+{
+    persist_deep_reserve = 0;
+    std::vector<Job>& jobs = p.jobs;
+    const std::vector<int>& plive = p.plive;
+    if (!(p.use_persist && h_last.size() == jobs.size() && !pb.equal_shares)) return;
+    if (persist_tend.size() != 3 * jobs.size()) persist_tend.assign(3 * jobs.size(), 0);
+    for (int k : plive) {
+        int* h = &persist_tend[3 * (size_t)k];
+        if (h_last[k].t_end_us > 0) { h[2] = h[1]; h[1] = h[0]; h[0] = h_last[k].t_end_us; }
+    }
+    auto score = [&](int k) { const int* h = &persist_tend[3 * (size_t)k]; return std::max(h[0], std::max(h[1], h[2])); };
+    std::vector<int> order;
+    for (int k : plive) if (score(k) > 0) order.push_back(k);
+    if (order.size() != plive.size()) return;
+    std::sort(order.begin(), order.end(), [&](int x, int y) { return score(x) > score(y); });
+    const int equal = pb.nblocks / (int)plive.size();
+    if (equal == 1) p.second_share.assign(order.begin(), order.begin() + std::min<size_t>(order.size(), pb.nblocks - (int)plive.size()));
+    int pool = pb.nblocks - equal * (int)plive.size();
+    for (int k : plive) if (jobs[k].nodes == 0 && equal >= 8) pool += equal / 2;
+    const int ndeep = std::min<int>((int)order.size(), pool / std::max(equal - 1, 1));
+    persist_deep_reserve = ndeep * (equal - 1);
+    const int tmax_us = score(order[0]);
+    for (size_t q = 0; q < order.size(); ++q)
+        jobs[order[q]].deep = (int)q < ndeep ? 2 : (score(order[q]) > 0.85 * tmax_us ? 1 : 0);
+    if (pb.want_trace) {
+        fprintf(stderr, "persist feedback: pool %d, reserve %d; search ends of the previous step [us]:", pool, persist_deep_reserve);
+        for (size_t q = 0; q < order.size(); ++q) fprintf(stderr, " %d:%d%s", order[q], score(order[q]), jobs[order[q]].deep == 2 ? "*" : "");
+        fprintf(stderr, "\n");
+    }
+}
+
+// Back to the host rounds after an engine gave the solve up: the records as they were uploaded, in the host rounds' own trial slots, the
+// counters zeroed, the bottoms clamped again.  (The scan search hands back records whose slots ARE the host rounds' -- use_persist and
+// use_own are false in tolerance mode, and nothing writes p.jobs after prepare_jobs / rank_feedback -- so setting them is a no-op there.)
+int LevelSolver::restore_jobs_for_rounds(RunPlan& p)
+{
+    hipStream_t st = ctx->stream;
+    for (int k = 0; k < njobs; ++k) if (!p.jobs[k].frozen) host_round_slots(p, k, p.jobs[k]);
+    DFTA_HIP(ctx, hipMemcpyAsync(d_jobs, p.jobs.data(), sizeof(Job) * njobs, hipMemcpyHostToDevice, st));
+    DFTA_HIP(ctx, hipMemsetAsync(d_counters, 0, sizeof(unsigned long long) * 4, st));
+    return clamp_job_bottoms(p);
+}
+
+int LevelSolver::clamp_job_bottoms(const RunPlan& p)
+{
+    if (p.chained || !clamp_bottoms) return DFTA_OK;
+    hipLaunchKernelGGL(k_clamp_bottoms, dim3((njobs + 63) / 64), dim3(64), 0, ctx->stream, d_jobs.p, njobs, d_slot_min.p);
+    DFTA_CHECK_LAUNCH(ctx);
+    return DFTA_OK;
+}
+
+// TOLERANCE MODE of the sweeps (scan.hip, opt-in): every level's three bisections by one workgroup, start to end on the device --
+// no rounds, no speculation.  A sweep the scan cannot decide (non-finite values, f >= 12 in a step row: never seen for the
+// potential of an SCF) sends the whole solve to the exact kernels: the host rounds.
+int LevelSolver::search_scan(RunPlan& p)
+{
+    hipStream_t st = ctx->stream;
+    int rc = dfta_launch_scan_build_tab(ctx, g, scan_tb, p.dV, d_slot_v, d_slot_l);
+    if (rc) return rc;
+    // a handful of levels leave compute units idle: K = 15, 7 or 3 workgroups per level take a depth-4, 3 or 2 bisection tree per round
+    std::vector<int>& live_jobs = p.scan_live;
+    for (int k = 0; k < njobs; ++k) if (!p.jobs[k].frozen) live_jobs.push_back(k);
+    int K = 1;
+    if (!p.chained && !live_jobs.empty()) {
+        for (int cand : {15, 7, 3}) if ((long)live_jobs.size() * cand <= ctx->num_cu) { K = cand; break; }
+        if (const char* e = dfta_knob("SCAN_GROUP")) { const int f = atoi(e); K = (f == 15 || f == 7 || f == 3) && (long)live_jobs.size() * f <= ctx->num_cu ? f : 1; }
+    }
+    DFTA_HIP(ctx, hipEventRecord(ev[0], st));
+    rc = DFTA_ERR_NOT_CONVERGED;
+    if (K > 1) {
+        DFTA_HIP(ctx, hipMemcpyAsync(d_scan_live, live_jobs.data(), sizeof(int) * live_jobs.size(), hipMemcpyHostToDevice, st));
+        DFTA_HIP(ctx, hipMemsetAsync(d_jstart_keep, 0xff, sizeof(int) * njobs, st));      // -1: frozen (the live jobs write their cut-off index)
+        rc = dfta_launch_scan_levels_group(ctx, g, d_jobs, d_scan_live, (int)live_jobs.size(), K, scan_tb, dfta_knob("LEVELS_NOFIXEDPOINT") ? 0 : 1, d_counters,
+                                           d_scan_xch, p.scan_match_mode, d_Psi, d_jstart_keep);
+        if (rc && rc != DFTA_ERR_NOT_CONVERGED) return rc;
+    }
+    if (rc == DFTA_ERR_NOT_CONVERGED) {
+        K = 1;
+        rc = dfta_launch_scan_levels(ctx, g, d_jobs, p.d_chains, p.run_chains, p.chained ? 1 : 0, scan_tb, dfta_knob("LEVELS_NOFIXEDPOINT") ? 0 : 1, d_counters,
+                                     p.scan_match_mode, d_Psi, d_jstart_keep);
+    }
+    if (rc) return rc;
+    scan_group = K;
+    DFTA_HIP(ctx, hipEventRecord(ev[1], st));
+    unsigned long long flag = 0;
+    DFTA_HIP(ctx, hipMemcpyAsync(&flag, d_counters + 3, sizeof(flag), hipMemcpyDeviceToHost, st));
+    DFTA_HIP(ctx, hipStreamSynchronize(st));
+    if (p.stats) DFTA_HIP(ctx, hipEventElapsedTime(&p.ms_sweep, ev[0], ev[1]));
+    if (flag) {                  // back to the exact kernels with the job records as they were uploaded (a trial the scan could not decide, or a lost group member)
+        ++scan_fallbacks;
+        return restore_jobs_for_rounds(p);
+    }
+    p.searched = true;
+    p.layout = LAYOUT_SCAN;
+    p.rounds = 1;
+    return DFTA_OK;
+}
+
+// The scan search of the first bisection as a predictor of the exact search's first spines (speculation only): a group of workgroups per
+// level ahead of the device-side search, one workgroup per level ahead of the host rounds of a batch
+int LevelSolver::predict_scan(RunPlan& p)
+{
+    const std::vector<int>& plive = p.plive;
+    if (!(!p.chained && scan_predict && scan_tb.tabv != nullptr && !plive.empty() && debug_rounds == 0 && ((p.use_persist && !p.wide) || p.scan_wanted))) return DFTA_OK;
+    hipStream_t st = ctx->stream;
+    int K = 1;
+    if (p.use_persist) for (int cand : {15, 7, 3}) if ((long)plive.size() * cand <= ctx->num_cu) { K = cand; break; }
+    const bool grouped = p.use_persist && K > 1;             // (a wide device-side search: one workgroup per level, as for the host rounds)
+    if (!(grouped || !p.use_persist || p.wide)) return DFTA_OK;
+    const int rc = dfta_launch_scan_build_tab(ctx, g, scan_tb, p.dV, d_slot_v, d_slot_l);
+    if (rc) return rc;
+    DFTA_HIP(ctx, hipMemcpyAsync(d_jobs_scan, d_jobs, sizeof(Job) * njobs, hipMemcpyDeviceToDevice, st));
+    DFTA_HIP(ctx, hipMemcpyAsync(d_scan_live, plive.data(), sizeof(int) * plive.size(), hipMemcpyHostToDevice, st));
+    DFTA_HIP(ctx, hipMemsetAsync(d_counters_scan, 0, sizeof(unsigned long long) * 4, st));
+    const int prc = grouped
+        ? dfta_launch_scan_levels_group(ctx, g, d_jobs_scan, d_scan_live, (int)plive.size(), K, scan_tb, fixed_point, d_counters_scan, d_scan_xch, -1, nullptr, nullptr)
+        : dfta_launch_scan_levels(ctx, g, d_jobs_scan, d_chain_off_b, njobs, 0, scan_tb, fixed_point, d_counters_scan, -1, nullptr, nullptr);
+    if (prc == DFTA_OK) {
+        hipLaunchKernelGGL(k_inject_scan_top, dim3(((int)plive.size() + 63) / 64), dim3(64), 0, st, d_jobs.p, d_jobs_scan.p, d_scan_live.p, (int)plive.size(), d_counters_scan.p, scan_predict_factor, scan_predict_shift);
         DFTA_CHECK_LAUNCH(ctx);
-        if (pk) {
-            hipLaunchKernelGGL(k_pack, dim3(1), dim3(kPackThreads), 0, st, d_jobs, njobs, nslots, d_slot_off, d_slot_jobs, pack_lanes_small,
-                               pack_dsmall, pack_lanes_large, pack_dmin, pack_dmax, d_gsz, d_goff, d_lane_job, d_wave_slot, d_pack_out);
-            DFTA_CHECK_LAUNCH(ctx);
-            hipLaunchKernelGGL(k_pack_lanes, dim3((njobs + 3) / 4), dim3(256), 0, st, d_jobs, njobs, d_lane_job);
-            DFTA_CHECK_LAUNCH(ctx);
-        }
-        return DFTA_OK;
-    };
-    // TOLERANCE MODE of the sweeps (scan.hip, opt-in): every level's three bisections by one workgroup, start to end on the device --
-    // no rounds, no speculation.  A sweep the scan cannot decide (non-finite values, f >= 12 in a step row: never seen for the
-    // potential of an SCF) sends the whole solve to the exact kernels below.
-    bool scan = sweep_mode == DFTA_SWEEPS_TOLERANCE && scan_tb.tabv != nullptr;
-    // the match solve and the normalisation in the same kernel (SCAN_NOMATCH: the exact k_match / k_normalize follow, measurements)
-    const int scan_match_mode = dfta_knob("SCAN_NOMATCH") ? 0 : (integ_rule == DFTA_INT_SIMPSON38 ? 2 : 1);
-    float ms_scan = 0;
-    if (scan) {
-        rc = dfta_launch_scan_build_tab(ctx, g, scan_tb, dV, d_slot_v, d_slot_l);
-        if (rc) return rc;
-        // a handful of levels leave compute units idle: K = 15, 7 or 3 workgroups per level take a depth-4, 3 or 2 bisection tree per round
-        std::vector<int> live_jobs;
-        for (int k = 0; k < njobs; ++k) if (!jobs[k].frozen) live_jobs.push_back(k);
-        int K = 1;
-        if (!chained && !live_jobs.empty()) {
-            for (int cand : {15, 7, 3}) if ((long)live_jobs.size() * cand <= ctx->num_cu) { K = cand; break; }
-            if (const char* e = dfta_knob("SCAN_GROUP")) { const int f = atoi(e); K = (f == 15 || f == 7 || f == 3) && (long)live_jobs.size() * f <= ctx->num_cu ? f : 1; }
-        }
-        DFTA_HIP(ctx, hipEventRecord(ev[0], st));
-        rc = DFTA_ERR_NOT_CONVERGED;
-        if (K > 1) {
-            DFTA_HIP(ctx, hipMemcpyAsync(d_scan_live, live_jobs.data(), sizeof(int) * live_jobs.size(), hipMemcpyHostToDevice, st));
-            DFTA_HIP(ctx, hipMemsetAsync(d_jstart_keep, 0xff, sizeof(int) * njobs, st));      // -1: frozen (the live jobs write their cut-off index)
-            rc = dfta_launch_scan_levels_group(ctx, g, d_jobs, d_scan_live, (int)live_jobs.size(), K, scan_tb, dfta_knob("LEVELS_NOFIXEDPOINT") ? 0 : 1, d_counters,
-                                               d_scan_xch, scan_match_mode, d_Psi, d_jstart_keep);
-            if (rc && rc != DFTA_ERR_NOT_CONVERGED) return rc;
-        }
-        if (rc == DFTA_ERR_NOT_CONVERGED) {
-            K = 1;
-            rc = dfta_launch_scan_levels(ctx, g, d_jobs, d_chains, run_chains, chained ? 1 : 0, scan_tb, dfta_knob("LEVELS_NOFIXEDPOINT") ? 0 : 1, d_counters,
-                                         scan_match_mode, d_Psi, d_jstart_keep);
-        }
-        if (rc) return rc;
-        scan_group = K;
-        DFTA_HIP(ctx, hipEventRecord(ev[1], st));
-        unsigned long long flag = 0;
-        DFTA_HIP(ctx, hipMemcpyAsync(&flag, d_counters + 3, sizeof(flag), hipMemcpyDeviceToHost, st));
-        DFTA_HIP(ctx, hipStreamSynchronize(st));
-        if (stats) DFTA_HIP(ctx, hipEventElapsedTime(&ms_scan, ev[0], ev[1]));
-        if (flag) {                  // back to the exact kernels with the job records as they were uploaded (a trial the scan could not decide, or a lost group member)
-            scan = false;
-            ++scan_fallbacks;
-            DFTA_HIP(ctx, hipMemcpyAsync(d_jobs, jobs.data(), sizeof(Job) * njobs, hipMemcpyHostToDevice, st));
-            DFTA_HIP(ctx, hipMemsetAsync(d_counters, 0, sizeof(unsigned long long) * 4, st));
-            if (!chained && clamp_bottoms) {
-                hipLaunchKernelGGL(k_clamp_bottoms, dim3((njobs + 63) / 64), dim3(64), 0, st, d_jobs, njobs, d_slot_min);
-                DFTA_CHECK_LAUNCH(ctx);
-            }
-        }
-    }
-    bool persisted = false;
-    int persist_rounds = 0;
+    } else if (prc != DFTA_ERR_NOT_CONVERGED) return prc;
+    return DFTA_OK;
+}
+
+// The device-side search (persist.inc): sweeps, walk, match and normalisation of every live level in one persistent kernel.  A lost
+// worker (or a grid that cannot be co-resident) sends the whole solve to the host rounds, from the records as they were.
+int LevelSolver::search_persist(RunPlan& p)
+{
+    hipStream_t st = ctx->stream;
+    const std::vector<int>& plive = p.plive;
+    dfta_range r_p("dfta: level search on the device (persistent kernel: sweeps, walk, match, normalisation)");
+    DFTA_HIP(ctx, hipMemsetAsync(d_jstart_keep, 0xff, sizeof(int) * njobs, st));      // -1: frozen (the live levels write their cut-off index)
+    if (p.stats) DFTA_HIP(ctx, hipEventRecord(ev[0], st));
+    int aborted = 0, persist_rounds = 0;
     float ms_persist = 0;
-    if (!scan && !chained && scan_predict && scan_tb.tabv != nullptr && !plive.empty() && debug_rounds == 0 && ((use_persist && !wide) || scan_wanted)) {
-        // the scan search of the first bisection as a predictor of the exact search's first spines (speculation only): a group of workgroups per
-        // level ahead of the device-side search, one workgroup per level ahead of the host rounds of a batch
-        int K = 1;
-        if (use_persist) for (int cand : {15, 7, 3}) if ((long)plive.size() * cand <= ctx->num_cu) { K = cand; break; }
-        const bool grouped = use_persist && K > 1;             // (a wide device-side search: one workgroup per level, as for the host rounds)
-        if (grouped || !use_persist || wide) {
-            rc = dfta_launch_scan_build_tab(ctx, g, scan_tb, dV, d_slot_v, d_slot_l);
-            if (rc) return rc;
-            DFTA_HIP(ctx, hipMemcpyAsync(d_jobs_scan, d_jobs, sizeof(Job) * njobs, hipMemcpyDeviceToDevice, st));
-            DFTA_HIP(ctx, hipMemcpyAsync(d_scan_live, plive.data(), sizeof(int) * plive.size(), hipMemcpyHostToDevice, st));
-            DFTA_HIP(ctx, hipMemsetAsync(d_counters_scan, 0, sizeof(unsigned long long) * 4, st));
-            const int prc = grouped
-                ? dfta_launch_scan_levels_group(ctx, g, d_jobs_scan, d_scan_live, (int)plive.size(), K, scan_tb, fixed_point, d_counters_scan, d_scan_xch, -1, nullptr, nullptr)
-                : dfta_launch_scan_levels(ctx, g, d_jobs_scan, d_chain_off_b, njobs, 0, scan_tb, fixed_point, d_counters_scan, -1, nullptr, nullptr);
-            if (prc == DFTA_OK) {
-                hipLaunchKernelGGL(k_inject_scan_top, dim3(((int)plive.size() + 63) / 64), dim3(64), 0, st, d_jobs, d_jobs_scan, d_scan_live, (int)plive.size(), d_counters_scan, scan_predict_factor, scan_predict_shift);
-                DFTA_CHECK_LAUNCH(ctx);
-            } else if (prc != DFTA_ERR_NOT_CONVERGED) return prc;
+    const bool want_trace = pb.want_trace;
+    // A level without nodes has no second bisection (walk_job takes it without a sweep): a third of the search less, so half of its equal
+    // share goes to the pool, from which the levels whose phases need one decision more than their trees hold take deeper ones
+    std::vector<int> share(plive.size());
+    const int equal = pb.nblocks / (int)plive.size();
+    const bool float_shares = !pb.equal_shares && equal >= 8;
+    for (size_t q = 0; q < plive.size(); ++q) share[q] = (float_shares && p.jobs[plive[q]].nodes == 0) ? equal - equal / 2 : equal;
+    if (equal == 1 && !pb.equal_shares) {
+        // one workgroup per level leaves nblocks - nlive over: second workgroups (scouts, a tree one level deeper) for the levels whose
+        // search ended last in the previous steps; without that feedback, for the first ones of the list
+        if (p.second_share.empty()) for (size_t q = 0; q < plive.size() && (int)q < pb.nblocks - (int)plive.size(); ++q) share[q] = 2;
+        else for (int k : p.second_share) share[p.plevel[k]] = 2;
+    }
+    const int rc = dfta_launch_levels_persist(ctx, g, &pb, d_jobs, plive.data(), (int)plive.size(), d_tab, d_bounds, d_Psi, d_Q, d_jstart_keep, d_counters, p.stats,
+                                              use_prediction ? 0 : 1, integ_rule, tuning, fixed_point, &persist_rounds, &aborted, want_trace ? &persist_trace : nullptr, share.data(), persist_deep_reserve);
+    if (rc) return rc;
+    if (p.stats) { DFTA_HIP(ctx, hipEventRecord(ev[1], st)); DFTA_HIP(ctx, hipEventSynchronize(ev[1])); DFTA_HIP(ctx, hipEventElapsedTime(&ms_persist, ev[0], ev[1])); }
+    ++persist_runs;
+    if (!aborted) {
+        if (want_trace) print_persist_trace(persist_trace, ms_persist);
+        p.searched = true;            // every live level was matched and normalised by the workgroup that closed its search
+        p.layout = LAYOUT_PERSIST;
+        p.rounds = persist_rounds;
+        p.ms_sweep = ms_persist;
+        return DFTA_OK;
+    }
+    ++persist_fallbacks;
+    {   // said once per process: the results are the same, the step is slower (dfta_step_stats::levels_fallbacks counts them)
+        static bool told = false;
+        if (!told) {
+            told = true;
+            fprintf(stderr, "dftatom_hip: the device-side level search did not finish (a workgroup of its cooperative launch was not scheduled -- "
+                            "another process on the device, masked compute units -- or timed out); this solve and any later one that fails the "
+                            "same way run with host-synchronised rounds instead: same results, slower steps\n");
         }
     }
-    if (!scan && use_persist) {
-        dfta_range r_p("dfta: level search on the device (persistent kernel: sweeps, walk, match, normalisation)");
-        DFTA_HIP(ctx, hipMemsetAsync(d_jstart_keep, 0xff, sizeof(int) * njobs, st));      // -1: frozen (the live levels write their cut-off index)
-        if (stats) DFTA_HIP(ctx, hipEventRecord(ev[0], st));
-        int aborted = 0;
-        const bool want_trace = pb.want_trace;
-        // A level without nodes has no second bisection (walk_job takes it without a sweep): a third of the search less, so half of its equal
-        // share goes to the pool, from which the levels whose phases need one decision more than their trees hold take deeper ones
-        std::vector<int> share(plive.size());
-        const int equal = pb.nblocks / (int)plive.size();
-        const bool float_shares = !pb.equal_shares && equal >= 8;
-        for (size_t q = 0; q < plive.size(); ++q) share[q] = (float_shares && jobs[plive[q]].nodes == 0) ? equal - equal / 2 : equal;
-        if (equal == 1 && !pb.equal_shares) {
-            // one workgroup per level leaves nblocks - nlive over: second workgroups (scouts, a tree one level deeper) for the levels whose
-            // search ended last in the previous steps; without that feedback, for the first ones of the list
-            if (second_share.empty()) for (size_t q = 0; q < plive.size() && (int)q < pb.nblocks - (int)plive.size(); ++q) share[q] = 2;
-            else for (int k : second_share) share[plevel[k]] = 2;
-        }
-        rc = dfta_launch_levels_persist(ctx, g, &pb, d_jobs, plive.data(), (int)plive.size(), d_tab, d_bounds, d_Psi, d_Q, d_jstart_keep, d_counters, stats != nullptr,
-                                        use_prediction ? 0 : 1, integ_rule, tuning, fixed_point, &persist_rounds, &aborted, want_trace ? &persist_trace : nullptr, share.data(), persist_deep_reserve);
-        if (rc) return rc;
-        if (stats) { DFTA_HIP(ctx, hipEventRecord(ev[1], st)); DFTA_HIP(ctx, hipEventSynchronize(ev[1])); DFTA_HIP(ctx, hipEventElapsedTime(&ms_persist, ev[0], ev[1])); }
-        ++persist_runs;
-        if (want_trace && !aborted) {
-            // one line per closed round, in the order of the closings: time since the first record [us], level, rounds taken, then what was planned
-            const size_t n = persist_trace.size() / 4;
-            std::vector<size_t> order(n);
-            for (size_t q = 0; q < n; ++q) order[q] = q;
-            std::sort(order.begin(), order.end(), [&](size_t x, size_t y) { return persist_trace[4 * x] < persist_trace[4 * y]; });
-            const unsigned long long t0 = n ? persist_trace[4 * order[0]] : 0;
-            fprintf(stderr, "persist trace: %zu records, kernel %.3f ms\n", n, ms_persist);
-            for (size_t q : order) {
-                const unsigned long long *w = &persist_trace[4 * q];
-                const int ph = (int)(w[2] >> 56);
-                if (ph == PH_DONE + 1) fprintf(stderr, "  %9.1f us  job %2d round %2d  search ended\n", (w[0] - t0) * 0.01, (int)(w[1] >> 32), (int)(w[1] & 0xffffffff));
-                else if (ph == PH_DONE) fprintf(stderr, "  %9.1f us  job %2d round %2d  DONE (matched, start %llu, candidate %d)\n", (w[0] - t0) * 0.01, (int)(w[1] >> 32), (int)(w[1] & 0xffffffff), w[3] & 0xffffffffull, (int)(signed char)((w[3] >> 32) & 0xff));
-                else fprintf(stderr, "  %9.1f us  job %2d round %2d  next: phase %d done %2d blocks %3d spine %2d capz %5d tcap %5d cand %d/%d\n", (w[0] - t0) * 0.01, (int)(w[1] >> 32),
-                             (int)(w[1] & 0xffffffff), ph, (int)((w[2] >> 32) & 0xff), (int)((w[2] >> 16) & 0xffff), (int)(w[2] & 0xffff), (int)((w[3] >> 32) & 0xffff), (int)(w[3] & 0xffffffff),
-                             (int)((w[3] >> 56) & 0xff), (int)(signed char)((w[3] >> 48) & 0xff));
-            }
-        }
-        if (!aborted) persisted = true;
-        else {
-            // a worker was lost (or the grid cannot be co-resident): the whole solve again with host rounds, from the records as they were
-            ++persist_fallbacks;
-            {   // said once per process: the results are the same, the step is slower (dfta_step_stats::levels_fallbacks counts them)
-                static bool told = false;
-                if (!told) {
-                    told = true;
-                    fprintf(stderr, "dftatom_hip: the device-side level search did not finish (a workgroup of its cooperative launch was not scheduled -- "
-                                    "another process on the device, masked compute units -- or timed out); this solve and any later one that fails the "
-                                    "same way run with host-synchronised rounds instead: same results, slower steps\n");
-                }
-            }
-            for (int k = 0; k < njobs; ++k)
-                if (!jobs[k].frozen) { jobs[k].tbase = (pk || sw) ? 0 : k * tpj; jobs[k].tcap = (pk || sw) ? 0 : tpj; }
-            DFTA_HIP(ctx, hipMemcpyAsync(d_jobs, jobs.data(), sizeof(Job) * njobs, hipMemcpyHostToDevice, st));
-            DFTA_HIP(ctx, hipMemsetAsync(d_counters, 0, sizeof(unsigned long long) * 4, st));
-            if (!chained && clamp_bottoms) {
-                hipLaunchKernelGGL(k_clamp_bottoms, dim3((njobs + 63) / 64), dim3(64), 0, st, d_jobs, njobs, d_slot_min);
-                DFTA_CHECK_LAUNCH(ctx);
-            }
-        }
+    return restore_jobs_for_rounds(p);
+}
+
+// The own-pace search of a batch (own.inc): one workgroup of W waves per live level, sweeps + walk in one ordinary launch
+int LevelSolver::search_own(RunPlan& p)
+{
+    hipStream_t st = ctx->stream;
+    dfta_range r_o("dfta: level search on the device (own pace: one workgroup per level, sweeps + walk)");
+    DFTA_HIP(ctx, hipMemcpyAsync(d_own_live, p.plive.data(), sizeof(int) * p.plive.size(), hipMemcpyHostToDevice, st));
+    if (p.stats) DFTA_HIP(ctx, hipEventRecord(ev[0], st));
+    const int rc = dfta_launch_levels_own(ctx, g, d_jobs, d_own_live, (int)p.plive.size(), p.own_W, d_tab, d_bounds, d_wave_slot, d_wave_first, d_wave_cnt, d_E, d_limit, d_start,
+                                          d_us, d_us1, d_count, d_u0, d_phi, d_istop, d_trip, d_counters, p.stats, use_prediction ? 0 : 1, own_spine_cap);
+    if (rc) return rc;
+    if (p.stats) DFTA_HIP(ctx, hipEventRecord(ev[1], st));
+    tables_dirty = true;             // the kernel wrote its blocks' table slots
+    own_last_W = p.own_W;
+    p.searched = true;
+    p.layout = LAYOUT_OWN;           // (rounds and sweep time: read with the counters, fill_stats)
+    return DFTA_OK;
+}
+
+// spines (and, in latency mode, the slots) of the next host round
+int LevelSolver::plan_round(const RunPlan& p)
+{
+    hipStream_t st = ctx->stream;
+    if (p.dyn)
+        hipLaunchKernelGGL(k_allot, dim3(1), dim3(64), 0, st, d_jobs.p, p.sw ? (int)p.live.size() : njobs, (int)budget_trials, use_prediction ? 0 : 1, d_wave_job.p,
+                           d_wave_slot.p, p.sw ? d_live.p : nullptr);
+    else
+        hipLaunchKernelGGL(k_plan, dim3((njobs + 63) / 64), dim3(64), 0, st, d_jobs.p, njobs, use_prediction ? 0 : 1, p.pk ? (1 << 14) : 0);
+    DFTA_CHECK_LAUNCH(ctx);
+    if (p.pk) {
+        hipLaunchKernelGGL(k_pack, dim3(1), dim3(kPackThreads), 0, st, d_jobs.p, njobs, nslots, d_slot_off.p, d_slot_jobs.p, pack_lanes_small,
+                           pack_dsmall, pack_lanes_large, pack_dmin, pack_dmax, d_gsz.p, d_goff.p, d_lane_job.p, d_wave_slot.p, d_pack_out.p);
+        DFTA_CHECK_LAUNCH(ctx);
+        hipLaunchKernelGGL(k_pack_lanes, dim3((njobs + 3) / 4), dim3(256), 0, st, d_jobs.p, njobs, d_lane_job.p);
+        DFTA_CHECK_LAUNCH(ctx);
     }
-    bool owned = false;
-    if (!scan && !persisted && use_own) {
-        dfta_range r_o("dfta: level search on the device (own pace: one workgroup per level, sweeps + walk)");
-        DFTA_HIP(ctx, hipMemcpyAsync(d_own_live, plive.data(), sizeof(int) * plive.size(), hipMemcpyHostToDevice, st));
-        if (stats) DFTA_HIP(ctx, hipEventRecord(ev[0], st));
-        rc = dfta_launch_levels_own(ctx, g, d_jobs, d_own_live, (int)plive.size(), own_W, d_tab, d_bounds, d_wave_slot, d_wave_first, d_wave_cnt, d_E, d_limit, d_start,
-                                    d_us, d_us1, d_count, d_u0, d_phi, d_istop, d_trip, d_counters, stats != nullptr, use_prediction ? 0 : 1, own_spine_cap);
-        if (rc) return rc;
-        if (stats) DFTA_HIP(ctx, hipEventRecord(ev[1], st));
-        tables_dirty = true;             // the kernel wrote its blocks' table slots
-        owned = true;
-        own_last_W = own_W;
+    return DFTA_OK;
+}
+
+// Match solves of the levels whose search has ended while others still search: on the second stream, under the next round's sweeps
+// (two waves and 8 KB of LDS per level fit next to a sweep block)
+int LevelSolver::early_match_solves(RunPlan& p)
+{
+    DFTA_HIP(ctx, hipStreamWaitEvent(st2, ev_walk, 0));
+    hipLaunchKernelGGL(k_take_ready, dim3((njobs + 63) / 64), dim3(64), 0, st2.s, d_snapE.p, d_snapReady.p, d_jmatched.p, njobs, d_jE.p, d_jtake.p);
+    DFTA_CHECK_LAUNCH(ctx);
+    DFTA_HIP(ctx, hipEventRecord(ev_taken, st2));
+    int erc = dfta_launch_boundary(ctx, g, d_jE, njobs, d_jstart, d_jus, d_jus1, 1, d_jl, d_Q, st2);
+    if (!erc) {
+        hipLaunchKernelGGL(k_mask_ready, dim3((njobs + 63) / 64), dim3(64), 0, st2.s, d_jtake.p, njobs, d_jstart.p, d_jmatched.p, d_jstart_keep.p);
+        DFTA_CHECK_LAUNCH(ctx);
+        erc = dfta_launch_match(ctx, g, njobs, d_tab, d_jslot, d_jE, d_jstart, d_jus, d_jus1, d_jl, d_Psi, d_Q, d_jmp, d_bounds, d_Q, st2);
     }
-    if (!scan && !persisted && !owned) {
-        rc = plan();
-        if (rc) return rc;
-    }
+    if (erc) return erc;
+    DFTA_HIP(ctx, hipEventRecord(ev_early, st2));
+    p.early_pending = true;
+    return DFTA_OK;
+}
+
+// The host rounds: expand, sweeps, scout, walk, plan -- one host synchronisation per round, all levels in lock step
+int LevelSolver::search_rounds(RunPlan& p)
+{
+    const int N = g->N;
+    hipStream_t st = ctx->stream;
+    const bool pk = p.pk, early = p.early, stats = p.stats;
+    int rc = plan_round(p);
+    if (rc) return rc;
     // trials of the coming round: the whole static / latency-mode layout, or what k_pack has just laid out
-    long round_trials = dyn ? budget_trials : static_trials;
-    int pack_out[4] = {0, 0, 0, 0};
-    if (pk && !scan && !persisted && !owned) {
-        DFTA_HIP(ctx, hipMemcpyAsync(pack_out, d_pack_out, sizeof(pack_out), hipMemcpyDeviceToHost, st));
+    long round_trials = p.dyn ? budget_trials : static_trials;
+    int* pack_out = p.pack_out;
+    if (pk) {
+        DFTA_HIP(ctx, hipMemcpyAsync(pack_out, d_pack_out, sizeof(p.pack_out), hipMemcpyDeviceToHost, st));
         DFTA_HIP(ctx, hipStreamSynchronize(st));
         round_trials = pack_out[0];
     }
-    if (early && !scan && !persisted && !owned) {
-        hipLaunchKernelGGL(k_job_slots, dim3((njobs + 63) / 64), dim3(64), 0, st, d_jobs, njobs, d_jslot, d_jl);
+    if (early) {
+        hipLaunchKernelGGL(k_job_slots, dim3((njobs + 63) / 64), dim3(64), 0, st, d_jobs.p, njobs, d_jslot.p, d_jl.p);
         DFTA_CHECK_LAUNCH(ctx);
         DFTA_HIP(ctx, hipMemsetAsync(d_jE, 0xff, sizeof(double) * njobs, st));      // NaN: "no energy yet" (k_take_ready)
     }
     int* d_ndone = reinterpret_cast<int*>(d_counters + 2);
-    int rounds = scan ? 1 : (persisted ? persist_rounds : 0);
-    float ms_sweep = persisted ? ms_persist : ms_scan;
-    const int max_rounds = 4096;
-    int done_seen = nfrozen;
-    bool early_pending = false;
-    while (!scan && !persisted && !owned && rounds < max_rounds) {
+    int done_seen = p.nfrozen;
+    while (p.rounds < kMaxRounds) {
         dfta_range r_round("dfta: level-search round (expand, sweeps, scout, walk, plan)");
         if (round_trials <= 0 || round_trials > ntrials) { snprintf(ctx->err, sizeof(ctx->err), "level solver: packed round of %ld trials (room for %ld)", round_trials, ntrials); return DFTA_ERR_HIP; }
         const int round_waves = static_cast<int>(round_trials / 64);
         // the fused sweeps of a batch are launched as a queue of blocks, longest first (numerov.hip:k_sweep_queue)
         // (the pipelined kernel likewise once a round has more blocks than compute units: its second pass is then made of the short blocks)
-        const bool queued = d_queue != nullptr && !g->uniform && (dfta_sweep_is_fused(ctx, round_waves) || round_waves > ctx->num_cu);
+        const bool queued = d_queue.p != nullptr && !g->uniform && (dfta_sweep_is_fused(ctx, round_waves) || round_waves > ctx->num_cu);
         if (queued) DFTA_HIP(ctx, hipMemsetAsync(d_queue, 0, sizeof(int) * (kSweepQueueClasses + 1), st));
-        hipLaunchKernelGGL(k_expand, dim3((unsigned)((round_trials + 255) / 256)), dim3(256), 0, st, d_jobs, pk ? d_lane_job : d_wave_job, pk ? 0 : 6,
-                           (int)round_trials, g->d_r, N, g->delta, g->far_arg_threshold, d_E, d_limit, d_start, d_us, d_us1, d_wave_kind, d_counters, g->uniform,
-                           g->Rmax, g->h, queued ? d_queue : nullptr, queued ? d_queue + kSweepQueueClasses + 1 : nullptr, nwaves);
+        hipLaunchKernelGGL(k_expand, dim3((unsigned)((round_trials + 255) / 256)), dim3(256), 0, st, d_jobs.p, pk ? d_lane_job.p : d_wave_job.p, pk ? 0 : 6,
+                           (int)round_trials, g->d_r, N, g->delta, g->far_arg_threshold, d_E.p, d_limit.p, d_start.p, d_us.p, d_us1.p, d_wave_kind.p, d_counters.p, g->uniform,
+                           g->Rmax, g->h, queued ? d_queue.p : nullptr, queued ? d_queue + kSweepQueueClasses + 1 : nullptr, nwaves);
         DFTA_CHECK_LAUNCH(ctx);
         if (stats) DFTA_HIP(ctx, hipEventRecord(ev[0], st));
         rc = dfta_launch_sweep(ctx, g, DFTA_SWEEP_COUNT, d_wave_kind, round_waves, d_tab, d_wave_slot, d_wave_first, d_wave_cnt, d_E,
-                               d_limit, d_start, d_us, d_us1, d_count, d_u0, stats ? d_trip : nullptr, stats ? d_counters + 1 : nullptr, g->uniform ? nullptr : d_bounds, d_phi,
-                               d_istop, d_slot_l, queued ? d_queue : nullptr, nwaves);
+                               d_limit, d_start, d_us, d_us1, d_count, d_u0, stats ? d_trip.p : nullptr, stats ? d_counters + 1 : nullptr, g->uniform ? nullptr : d_bounds.p, d_phi,
+                               d_istop, d_slot_l, queued ? d_queue.p : nullptr, nwaves);
         if (rc) return rc;
         if (stats) DFTA_HIP(ctx, hipEventRecord(ev[1], st));
         if (!pk) {          // packed rounds have no scouts (capz == tcap)
-            hipLaunchKernelGGL(k_scout, dim3(njobs), dim3(64), 0, st, d_jobs, d_E, d_start, d_u0);
+            hipLaunchKernelGGL(k_scout, dim3(njobs), dim3(64), 0, st, d_jobs.p, d_E.p, d_start.p, d_u0.p);
             DFTA_CHECK_LAUNCH(ctx);
         }
         DFTA_HIP(ctx, hipMemsetAsync(d_ndone, 0, sizeof(int), st));
-        hipLaunchKernelGGL(k_walk, dim3((run_chains + 63) / 64), dim3(64), 0, st, d_jobs, d_chains, run_chains, d_count, d_u0, d_phi, d_istop, stats ? d_trip : nullptr, d_tab, N, d_ndone);
+        hipLaunchKernelGGL(k_walk, dim3((p.run_chains + 63) / 64), dim3(64), 0, st, d_jobs.p, p.d_chains, p.run_chains, d_count.p, d_u0.p, d_phi.p, d_istop.p, stats ? d_trip.p : nullptr, d_tab.p, N, d_ndone);
         DFTA_CHECK_LAUNCH(ctx);
         if (early) {
             DFTA_HIP(ctx, hipStreamWaitEvent(st, ev_taken, 0));      // the second stream has consumed the previous snapshot (no-op if none was taken)
-            hipLaunchKernelGGL(k_snapshot_done, dim3((njobs + 63) / 64), dim3(64), 0, st, d_jobs, njobs, d_snapE, d_snapReady);
+            hipLaunchKernelGGL(k_snapshot_done, dim3((njobs + 63) / 64), dim3(64), 0, st, d_jobs.p, njobs, d_snapE.p, d_snapReady.p);
             DFTA_CHECK_LAUNCH(ctx);
             DFTA_HIP(ctx, hipEventRecord(ev_walk, st));
         }
-        rc = plan();
+        rc = plan_round(p);
         if (rc) return rc;
         int ndone = 0;
         DFTA_HIP(ctx, hipMemcpyAsync(&ndone, d_ndone, sizeof(int), hipMemcpyDeviceToHost, st));
-        if (pk) DFTA_HIP(ctx, hipMemcpyAsync(pack_out, d_pack_out, sizeof(pack_out), hipMemcpyDeviceToHost, st));
+        if (pk) DFTA_HIP(ctx, hipMemcpyAsync(pack_out, d_pack_out, sizeof(p.pack_out), hipMemcpyDeviceToHost, st));
         DFTA_HIP(ctx, hipStreamSynchronize(st));
         const long this_round = round_trials;
         if (pk) round_trials = pack_out[0];
-        if (early && ndone > done_seen && ndone < njobs) {
-            // some levels have their eigenvalue while others still search: their match solves start now, on the second stream,
-            // under the next round's sweeps (two waves and 8 KB of LDS per level fit next to a sweep block)
+        if (early && ndone > done_seen && ndone < njobs) {     // some levels have their eigenvalue while others still search
             done_seen = ndone;
-            DFTA_HIP(ctx, hipStreamWaitEvent(st2, ev_walk, 0));
-            hipLaunchKernelGGL(k_take_ready, dim3((njobs + 63) / 64), dim3(64), 0, st2, d_snapE, d_snapReady, d_jmatched, njobs, d_jE, d_jtake);
-            DFTA_CHECK_LAUNCH(ctx);
-            DFTA_HIP(ctx, hipEventRecord(ev_taken, st2));
-            int erc = dfta_launch_boundary(ctx, g, d_jE, njobs, d_jstart, d_jus, d_jus1, 1, d_jl, d_Q, st2);
-            if (!erc) {
-                hipLaunchKernelGGL(k_mask_ready, dim3((njobs + 63) / 64), dim3(64), 0, st2, d_jtake, njobs, d_jstart, d_jmatched, d_jstart_keep);
-                DFTA_CHECK_LAUNCH(ctx);
-                erc = dfta_launch_match(ctx, g, njobs, d_tab, d_jslot, d_jE, d_jstart, d_jus, d_jus1, d_jl, d_Psi, d_Q, d_jmp, d_bounds, d_Q, st2);
-            }
-            if (erc) return erc;
-            DFTA_HIP(ctx, hipEventRecord(ev_early, st2));
-            early_pending = true;
+            rc = early_match_solves(p);
+            if (rc) return rc;
         }
         if (stats) {
             float ms = 0;
             DFTA_HIP(ctx, hipEventElapsedTime(&ms, ev[0], ev[1]));
-            ms_sweep += ms;
+            p.ms_sweep += ms;
             if (debug_rounds && pk)
-                fprintf(stderr, "   packed round %d: %ld trials in %.3f ms; next: %d trials, depth %d, %d jobs searching\n", rounds + 1, this_round, ms, pack_out[0], pack_out[1], pack_out[2]);
+                fprintf(stderr, "   packed round %d: %ld trials in %.3f ms; next: %d trials, depth %d, %d jobs searching\n", p.rounds + 1, this_round, ms, pack_out[0], pack_out[1], pack_out[2]);
         }
-        ++rounds;
-        if (debug_rounds) {      // per-round census of the jobs (phase/decisions taken), stderr
+        ++p.rounds;
+        if (debug_rounds) {
             std::vector<Job> dbg(njobs);
             DFTA_HIP(ctx, hipMemcpy(dbg.data(), d_jobs, sizeof(Job) * njobs, hipMemcpyDeviceToHost));
-            fprintf(stderr, "round %2d |", rounds);
-            for (int q = 0; q < njobs; ++q)
-                if (dbg[q].phase != PH_DONE) fprintf(stderr, " %d:%d/%d", q, dbg[q].phase, dbg[q].phase_done);
-            fprintf(stderr, "\n");
-            if (debug_rounds >= 3)
-                for (int q = 0; q < njobs; ++q) {
-                    const Job& J = dbg[q];
-                    fprintf(stderr, "   J %2d ph %d done %d l %d boe %.17g toe %.17g top %.17g sc_ok %d sc_lo %.17g sc_hi %.17g spine %d use_sp %d miss %d tcap %d\n",
-                            q, J.phase, J.phase_done, J.l, J.boe, J.toe, J.top, J.sc_ok, J.sc_lo, J.sc_hi, J.spine, J.use_sp, J.miss, J.tcap);
-                }
-            if (debug_rounds >= 2)
-                for (int q = 0; q < njobs; ++q) {
-                    const Job& J = dbg[q];
-                    if (J.phase != PH_TOP) continue;
-                    fprintf(stderr, "   job %2d l=%d w=%.3e ok=%d spine=%d use_sp=%d miss=%d | a: is=%d phi=%.4e  b: is=%s%d phi=%.4e  c: de=%.3e is=%s%d phi=%.4e | pred w/e=%.3e\n",
-                            q, J.l, J.toe - J.boe, J.sc_ok, J.spine, J.use_sp, J.miss, J.sc_is[0], J.sc_phi[0],
-                            (J.sc_is[1] >= 0 && (J.sc_is[1] & kStopOver)) ? "o" : "", J.sc_is[1] < 0 ? -1 : (J.sc_is[1] & ~kStopOver), J.sc_phi[1],
-                            J.sc_e[2] - J.sc_e[0], (J.sc_is[2] >= 0 && (J.sc_is[2] & kStopOver)) ? "o" : "", J.sc_is[2] < 0 ? -1 : (J.sc_is[2] & ~kStopOver), J.sc_phi[2],
-                            J.sc_ok ? (J.toe - J.boe) / (J.sc_hi - J.sc_lo) : 0.0);
-                }
+            print_census(dbg, p.rounds, debug_rounds);
         }
         if (ndone >= njobs) break;
     }
-    if (rounds >= max_rounds) { snprintf(ctx->err, sizeof(ctx->err), "level solver did not terminate"); return DFTA_ERR_NOT_CONVERGED; }
+    return DFTA_OK;
+}
 
-    // wavefunctions: match (the levels that were not matched while the others searched), normalise, accumulate
-    if (persisted) {
-        // every live level was matched and normalised by the workgroup that closed its search
-    } else if (scan && scan_match_mode) {
-        // k_scan_levels has matched (and, with Simpson 3/8, normalised) every live level
-        if (scan_match_mode == 1) {
-            hipLaunchKernelGGL(k_normalize, dim3(njobs), dim3(kNormThreads), 0, st, d_Psi, d_Q, N, g->d_eh, g->d_cnst, d_jstart_keep, g->uniform ? g->h : 1.0, integ_rule);
-            DFTA_CHECK_LAUNCH(ctx);
-        }
-    } else {
-        if (early_pending) DFTA_HIP(ctx, hipStreamWaitEvent(st, ev_early, 0));       // the early solves use the same per-job scratch arrays
-        hipLaunchKernelGGL(k_job_energies, dim3((njobs + 63) / 64), dim3(64), 0, st, d_jobs, njobs, d_jE, d_jslot, d_jl);
+// Wavefunctions: match (the levels that were not matched while the others searched), normalise, accumulate the density
+int LevelSolver::finish_wavefunctions(RunPlan& p)
+{
+    const int N = g->N;
+    hipStream_t st = ctx->stream;
+    bool normalise = true;
+    const int* keep = d_jstart_keep;       // the cut-off index of every job that was matched in this run (-1: frozen, its Psi stands)
+    if (p.layout == LAYOUT_PERSIST) normalise = false;       // every live level was matched and normalised by the workgroup that closed its search
+    else if (p.layout == LAYOUT_SCAN && p.scan_match_mode) normalise = p.scan_match_mode == 1;     // k_scan_levels has matched (and, with Simpson 3/8, normalised) every live level
+    else {
+        if (p.early_pending) DFTA_HIP(ctx, hipStreamWaitEvent(st, ev_early, 0));       // the early solves use the same per-job scratch arrays
+        hipLaunchKernelGGL(k_job_energies, dim3((njobs + 63) / 64), dim3(64), 0, st, d_jobs.p, njobs, d_jE.p, d_jslot.p, d_jl.p);
         DFTA_CHECK_LAUNCH(ctx);
-        rc = dfta_launch_boundary(ctx, g, d_jE, njobs, d_jstart, d_jus, d_jus1, 1, d_jl, d_Q /* uniform: start value at the first node, one per job */);
+        int rc = dfta_launch_boundary(ctx, g, d_jE, njobs, d_jstart, d_jus, d_jus1, 1, d_jl, d_Q /* uniform: start value at the first node, one per job */);
         if (rc) return rc;
         // cut-off index -1 = skipped by k_match: frozen jobs (the result of their last solve stands) and jobs matched already;
         // d_jstart_keep: the cut-off index of every job that was matched in this run (-1: frozen)
-        hipLaunchKernelGGL(k_mask_rest, dim3((njobs + 63) / 64), dim3(64), 0, st, d_jobs, njobs, d_jstart, d_jmatched, d_jstart_keep);
+        hipLaunchKernelGGL(k_mask_rest, dim3((njobs + 63) / 64), dim3(64), 0, st, d_jobs.p, njobs, d_jstart.p, d_jmatched.p, d_jstart_keep.p);
         DFTA_CHECK_LAUNCH(ctx);
-        rc = dfta_launch_match(ctx, g, njobs, d_tab, d_jslot, d_jE, d_jstart, d_jus, d_jus1, d_jl, d_Psi, d_Q, d_jmp, g->uniform ? nullptr : d_bounds,
+        rc = dfta_launch_match(ctx, g, njobs, d_tab, d_jslot, d_jE, d_jstart, d_jus, d_jus1, d_jl, d_Psi, d_Q, d_jmp, g->uniform ? nullptr : d_bounds.p,
                                d_Q);
         if (rc) return rc;
-        hipLaunchKernelGGL(k_store_match, dim3((njobs + 63) / 64), dim3(64), 0, st, d_jobs, njobs, d_jmp, d_jstart_keep);
+        hipLaunchKernelGGL(k_store_match, dim3((njobs + 63) / 64), dim3(64), 0, st, d_jobs.p, njobs, d_jmp.p, d_jstart_keep.p);
         DFTA_CHECK_LAUNCH(ctx);
-        hipLaunchKernelGGL(k_normalize, dim3(njobs), dim3(kNormThreads), 0, st, d_Psi, d_Q, N, g->d_eh, g->d_cnst, nfrozen ? d_jstart_keep : nullptr, g->uniform ? g->h : 1.0, integ_rule);
+        if (!p.nfrozen) keep = nullptr;
+    }
+    if (normalise) {
+        hipLaunchKernelGGL(k_normalize, dim3(njobs), dim3(kNormThreads), 0, st, d_Psi.p, d_Q.p, N, g->d_eh, g->d_cnst, keep, g->uniform ? g->h : 1.0, integ_rule);
         DFTA_CHECK_LAUNCH(ctx);
     }
-    if (dNewDensity) {
-        hipLaunchKernelGGL(k_accumulate_density, dim3(std::min(256, (N + 255) / 256), nV), dim3(256), 0, st, d_Psi, d_occ, d_v_off,
-                           N, dNewDensity);
+    if (p.dNewDensity) {
+        hipLaunchKernelGGL(k_accumulate_density, dim3(std::min(256, (N + 255) / 256), nV), dim3(256), 0, st, d_Psi.p, d_occ.p, d_v_off.p,
+                           N, p.dNewDensity);
         DFTA_CHECK_LAUNCH(ctx);
-    }
-    if (stats) {
-        unsigned long long cnt[3];
-        DFTA_HIP(ctx, hipMemcpyAsync(cnt, d_counters, sizeof(cnt), hipMemcpyDeviceToHost, st));
-        DFTA_HIP(ctx, hipStreamSynchronize(st));
-        if (owned) {
-            rounds = (int)(cnt[2] & 0xffffffffull);                 // the most rounds a level took
-            DFTA_HIP(ctx, hipEventElapsedTime(&ms_sweep, ev[0], ev[1]));
-        }
-        stats->rounds = rounds;
-        stats->sweeps_issued = static_cast<long>(cnt[0]) + 2L * (njobs - nfrozen);    // + inward/outward halves of the match solve
-        stats->points_traversed = static_cast<long>(cnt[1]);
-        stats->ms_sweep = ms_sweep;
-        stats->layout = owned ? 6 : (persisted ? 5 : (scan ? 4 : (sw ? 3 : (dynamic ? 1 : (pk ? 2 : 0)))));
     }
     return DFTA_OK;
+}
+
+int LevelSolver::fill_stats(RunPlan& p, LevelStats* stats)
+{
+    hipStream_t st = ctx->stream;
+    unsigned long long cnt[3];
+    DFTA_HIP(ctx, hipMemcpyAsync(cnt, d_counters, sizeof(cnt), hipMemcpyDeviceToHost, st));
+    DFTA_HIP(ctx, hipStreamSynchronize(st));
+    if (p.layout == LAYOUT_OWN) {
+        p.rounds = (int)(cnt[2] & 0xffffffffull);                 // the most rounds a level took
+        DFTA_HIP(ctx, hipEventElapsedTime(&p.ms_sweep, ev[0], ev[1]));
+    }
+    stats->rounds = p.rounds;
+    stats->sweeps_issued = static_cast<long>(cnt[0]) + 2L * (njobs - p.nfrozen);    // + inward/outward halves of the match solve
+    stats->points_traversed = static_cast<long>(cnt[1]);
+    stats->ms_sweep = p.ms_sweep;
+    stats->layout = p.layout;
+    return DFTA_OK;
+}
+
+// Solve all levels for the potentials dV (device, nV*N).
+//   job_bottom (host, njobs): BottomEnergy at entry of LocateInterval for every job.  CHAINED uses only the entry
+//   of the first job of each potential (-Z^2-1, DFTAtom.cpp:407) and hands E-3 from level to level (DFTAtom.cpp:541);
+//   BATCHED starts every level from its own entry (the caller's hint: E_{k-1} of the previous SCF step - 3).
+// The engines are tried in order; each either takes every live level to its eigenvalue (p.searched) or leaves the records ready for the
+// next one: the scan search (tolerance mode), [the scan predictor,] the device-side search, the own-pace search, the host rounds.
+int LevelSolver::run(const double* dV, const double* job_bottom, int run_mode, double* dNewDensity, LevelStats* stats,
+                     const unsigned char* frozen)
+{
+    if (njobs == 0) return DFTA_OK;
+    hipStream_t st = ctx->stream;
+    RunPlan p;                         // lives to the end of the solve: its vectors are the sources of asynchronous copies
+    p.dV = dV; p.dNewDensity = dNewDensity; p.stats = stats != nullptr;
+    make_plan(p, run_mode, frozen);
+    if (p.sw) {
+        DFTA_HIP(ctx, hipMemcpyAsync(d_live, p.live.data(), sizeof(int) * p.live.size(), hipMemcpyHostToDevice, st));
+        tables_dirty = true;
+    } else if (tables_dirty && !p.use_own) {           // back from latency mode / the own-pace search: the solver's own block tables
+        DFTA_HIP(ctx, hipMemcpyAsync(d_wave_job, h_wave_job.data(), sizeof(int) * h_wave_job.size(), hipMemcpyHostToDevice, st));
+        DFTA_HIP(ctx, hipMemcpyAsync(d_wave_slot, h_wave_slot.data(), sizeof(int) * h_wave_slot.size(), hipMemcpyHostToDevice, st));
+        tables_dirty = false;
+    }
+    prepare_jobs(p, job_bottom, frozen);
+    rank_feedback(p);
+    DFTA_HIP(ctx, hipMemcpyAsync(d_jobs, p.jobs.data(), sizeof(Job) * njobs, hipMemcpyHostToDevice, st));
+    DFTA_HIP(ctx, hipMemsetAsync(d_counters, 0, sizeof(unsigned long long) * 4, st));
+    DFTA_HIP(ctx, hipMemsetAsync(d_jmatched, 0, sizeof(int) * njobs, st));
+    if (p.nfrozen == njobs) {          // nothing to solve: Psi, density contributions and job records stand
+        DFTA_HIP(ctx, hipStreamSynchronize(st));      // p.jobs is the source of the copy above
+        if (stats) *stats = LevelStats();
+        return DFTA_OK;
+    }
+    int rc = dfta_launch_build_tab(ctx, g, d_tab, dV, d_slot_v, d_slot_l, nslots, d_bounds);
+    if (rc) return rc;
+    if (!p.chained && clamp_bottoms) {
+        hipLaunchKernelGGL(k_slot_min, dim3(nslots), dim3(1024), 0, st, d_tab.p, g->N, d_slot_min.p);
+        DFTA_CHECK_LAUNCH(ctx);
+    }
+    rc = clamp_job_bottoms(p);
+    if (rc) return rc;
+
+    if (sweep_mode == DFTA_SWEEPS_TOLERANCE && scan_tb.tabv != nullptr) rc = search_scan(p);
+    if (!rc && !p.searched) rc = predict_scan(p);
+    if (!rc && !p.searched && p.use_persist) rc = search_persist(p);
+    if (!rc && !p.searched && p.use_own) rc = search_own(p);
+    if (!rc && !p.searched) rc = search_rounds(p);
+    if (rc) return rc;
+    if (p.rounds >= kMaxRounds) { snprintf(ctx->err, sizeof(ctx->err), "level solver did not terminate"); return DFTA_ERR_NOT_CONVERGED; }
+
+    rc = finish_wavefunctions(p);
+    if (rc) return rc;
+    return stats ? fill_stats(p, stats) : DFTA_OK;
 }
 
 int LevelSolver::fetch_jobs(std::vector<Job>& out)
@@ -1438,19 +1514,16 @@ extern "C" int dfta_solve_levels(dfta_ctx* ctx, const dfta_grid* g, int mode, in
     rc = solver.fetch_jobs(jobs);
     if (rc) return rc;
     if (Eelectronic) for (int v = 0; v < nV; ++v) Eelectronic[v] = 0;
-    bool allconv = true;
     for (int k = 0; k < nlevels; ++k) {
         const dfta::Job& j = jobs[k];
         results[k].E = j.E; results[k].top = j.top; results[k].bottom = j.bottom; results[k].n_count = j.n_count;
         results[k].n_zero = j.n_zero; results[k].converged = j.converged; results[k].matchPoint = j.matchPoint;
         results[k].status = j.status;
         if (Eelectronic) Eelectronic[j.v] += solver.h_occ[k] * j.E;  // DFTAtom.cpp:561 (h_occ[k] == (double)j.occ)
-        allconv = allconv && j.converged;
     }
     if (newDensity) DFTA_HIP(ctx, hipMemcpyAsync(newDensity, dND.p, sizeof(double) * (size_t)nV * N, hipMemcpyDeviceToHost, st));
     if (Psi_out) DFTA_HIP(ctx, hipMemcpyAsync(Psi_out, solver.d_Psi, sizeof(double) * (size_t)nlevels * N, hipMemcpyDeviceToHost, st));
     DFTA_HIP(ctx, hipStreamSynchronize(st));
     if (issued_sweeps) *issued_sweeps = stats.sweeps_issued;
-    (void)allconv;
     return DFTA_OK;
 }

@@ -234,15 +234,17 @@ struct dfta_scf {
     struct LiveSolver { dfta_poisson* p = nullptr; int G = 0; bool tried = false; };
     LiveSolver live_solver[kLiveClasses];
     int live_cap = 0;                     // atoms the gather buffers hold
-    int* d_liveIdx = nullptr;             // live_cap skip flags, then live_cap atom indices
-    double *d_liveNe = nullptr, *d_liveRho = nullptr, *d_liveU = nullptr;   // d_liveNe: the live atoms' electron counts
+    DevBuf<int> d_liveIdx;                // live_cap skip flags, then live_cap atom indices
+    DevBuf<double> d_liveNe, d_liveRho, d_liveU;   // d_liveNe: the live atoms' electron counts
+    void free_live() { d_liveIdx.reset(); d_liveNe.reset(); d_liveRho.reset(); d_liveU.reset(); live_cap = 0; }
     std::vector<AtomState> h_atoms;
-    std::vector<double> h_liveNe;         // host staging of d_liveNe (the copy is asynchronous)
+    std::vector<int> h_liveIdx;           // host staging of d_liveIdx and d_liveNe (the copies are asynchronous: they live to the step's last
+    std::vector<double> h_liveNe;         // synchronisation at least)
     std::vector<double> h_bottom0;        // per potential: -Z^2-1 (DFTAtom.cpp:407)
     std::vector<double> h_job_bottom;     // per job: bracket start of the next level solve
     std::vector<dfta::Job> h_jobs;        // job results of the last step
     std::vector<unsigned char> h_frozen;  // per job: its atom has finished
-    int* d_fin = nullptr;                 // per atom: finished (device copy for the kernels that skip frozen atoms)
+    DevBuf<int> d_fin;                    // per atom: finished (device copy for the kernels that skip frozen atoms)
     bool debug_levels = false;            // $DFTA_DEBUG_LEVELS
     int integ_rule = DFTA_INT_SIMPSON38;  // dfta_scf_set_integrator
     int functional = DFTA_XC_VWN;         // dfta_scf_options::functional
@@ -250,12 +252,10 @@ struct dfta_scf {
     int levels_mode = DFTA_LEVELS_BATCHED;
     int steps_done = 0;
     std::vector<int> spin_nlev[2];      // per atom number of levels per spin
-    AtomState* d_atoms = nullptr;
-    double* d_Ne = nullptr;               // per atom: electrons, the multigrid's outer boundary U(Rmax)
-    double *d_density = nullptr, *d_dA = nullptr, *d_dB = nullptr, *d_V = nullptr, *d_U = nullptr, *d_Vexc = nullptr,
-           *d_va = nullptr, *d_vb = nullptr, *d_eexc = nullptr, *d_newDensity = nullptr, *d_integrands = nullptr,
-           *d_integrals = nullptr, *d_records = nullptr;
-    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    DevBuf<AtomState> d_atoms;
+    DevBuf<double> d_Ne;                  // per atom: electrons, the multigrid's outer boundary U(Rmax)
+    DevBuf<double> d_density, d_dA, d_dB, d_V, d_U, d_Vexc, d_va, d_vb, d_eexc, d_newDensity, d_integrands, d_integrals, d_records;
+    DevEvent ev[5];
 };
 
 static int scf_xc(dfta_scf* s)
@@ -263,7 +263,7 @@ static int scf_xc(dfta_scf* s)
     const size_t sz = (size_t)s->natoms * s->g->N;
     // PBE: one fused stencil + pointwise + divergence launch (gga.hip), frozen atoms skipped; PW92: pointwise, as VWN
     if (s->functional == DFTA_XC_PBE)
-        return dfta_launch_pbe_radial(s->ctx, s->g, s->natoms, s->lsda ? s->d_dA : s->d_density, s->lsda ? s->d_dB : nullptr, s->d_Vexc,
+        return dfta_launch_pbe_radial(s->ctx, s->g, s->natoms, s->lsda ? s->d_dA : s->d_density, s->lsda ? s->d_dB.p : nullptr, s->d_Vexc,
                                       s->d_va, s->d_vb, s->d_eexc, s->d_fin);
     if (s->functional == DFTA_XC_PW92)
         return s->lsda ? dfta_launch_pw92_lsda(s->ctx, s->d_dA, s->d_dB, sz, s->d_Vexc, s->d_va, s->d_vb, s->d_eexc)
@@ -279,13 +279,8 @@ extern "C" {
 void dfta_scf_destroy(dfta_scf* s)
 {
     if (!s) return;
-    void* ptrs[] = {s->d_fin, s->d_atoms, s->d_Ne, s->d_density, s->d_dA, s->d_dB, s->d_V, s->d_U, s->d_Vexc, s->d_va, s->d_vb, s->d_eexc,
-                    s->d_newDensity, s->d_integrands, s->d_integrals, s->d_records};
-    for (void* p : ptrs) if (p) (void)hipFree(p);
-    for (hipEvent_t e : s->ev) if (e) (void)hipEventDestroy(e);
     if (s->poisson) dfta_poisson_destroy(s->poisson);
     for (auto& ls : s->live_solver) if (ls.p) dfta_poisson_destroy(ls.p);
-    for (void* p : {(void*)s->d_liveIdx, (void*)s->d_liveNe, (void*)s->d_liveRho, (void*)s->d_liveU}) if (p) (void)hipFree(p);
     delete s;
 }
 
@@ -326,43 +321,13 @@ static bool config_channel(dfta_ctx* ctx, int a, int lsda, int cnt, const int* n
     return true;
 }
 
-int dfta_scf_create_config(dfta_ctx* ctx, const dfta_grid* g, int lsda, int natoms, const int* Z, const int* nlev, const int* cn,
-                           const int* cl, const double* cocc, double alpha, int levels_mode, int tree_depth,
-                           const dfta_scf_options* options, dfta_scf** out)
+// (Z, explicit configuration or Aufbau) of every atom -> its AtomState, the bracket bottoms, the levels per spin and the job list.
+// Host only; on an error the text is in ctx->err (and, for an explicit configuration, in dfta_config_last_error()).
+static int scf_configure(dfta_scf* s, const int* Z, const int* nlev, const int* cn, const int* cl, const double* cocc, int aufbau,
+                         std::vector<dfta::JobSpec>& specs)
 {
-    if (!ctx || !g || !out) return DFTA_ERR_INVALID;
-    DFTA_ENTER(ctx);
-    DFTA_REQUIRE(ctx, natoms >= 1 && Z && alpha >= 0 && alpha <= 1, "scf arguments");
-    DFTA_REQUIRE(ctx, !nlev || (cn && cl && cocc), "configuration: n, l and occ are needed with nlev");
-    dfta_scf_options opt = {(int)sizeof(dfta_scf_options), DFTA_INT_SIMPSON38, DFTA_XC_VWN, DFTA_AUFBAU_REFERENCE, -1, DFTA_SWEEPS_EXACT};
-    if (options) {
-        // the caller's struct may be shorter (an older header) or longer (a newer one) than this library's: read what both know
-        const int sz = options->struct_size;
-        DFTA_REQUIRE(ctx, sz >= (int)(2 * sizeof(int)) && sz % (int)sizeof(int) == 0 && sz <= 4096, "dfta_scf_options::struct_size (set it to sizeof(dfta_scf_options))");
-        dfta_scf_options in = {};
-        memcpy(&in, options, std::min<size_t>((size_t)sz, sizeof(in)));
-        // members the caller's struct does not have keep the defaults above; those it has are taken as they are (0 = the reference's behaviour)
-        const size_t have = std::min<size_t>((size_t)sz, sizeof(in));
-        memcpy(&opt, &in, have);
-        opt.struct_size = (int)sizeof(dfta_scf_options);
-    }
-    DFTA_REQUIRE(ctx, opt.poisson_mode >= -1 && opt.poisson_mode <= DFTA_POISSON_ADAPTIVE, "poisson mode");
-    DFTA_REQUIRE(ctx, dfta_integral_shape_ok(opt.integrator, g->N), "integration rule / grid size");
-    DFTA_REQUIRE(ctx, opt.functional >= DFTA_XC_VWN && opt.functional <= DFTA_XC_PBE, "functional (DFTA_XC_VWN .. DFTA_XC_PBE)");
-    DFTA_REQUIRE(ctx, (opt.functional != DFTA_XC_CHACHIYO && opt.functional != DFTA_XC_CHACHIYO_IMPROVED) || !lsda, "the Chachiyo functional is LDA only (ExcCor.h)");
-    DFTA_REQUIRE(ctx, opt.functional != DFTA_XC_PBE || !g->uniform, "the PBE functional needs a logarithmic grid (no GGA on the uniform grid)");
-    DFTA_REQUIRE(ctx, opt.aufbau == DFTA_AUFBAU_REFERENCE || opt.aufbau == DFTA_AUFBAU_TRANSITION_METALS, "aufbau");
-    DFTA_REQUIRE(ctx, opt.sweep_mode == DFTA_SWEEPS_EXACT || opt.sweep_mode == DFTA_SWEEPS_TOLERANCE, "sweep mode");
-    DFTA_REQUIRE(ctx, opt.sweep_mode == DFTA_SWEEPS_EXACT || dfta_scan_supported(g), "the tolerance mode of the sweeps needs a logarithmic grid of 12 .. 20 multigrid levels");
-    dfta_scf* s = new dfta_scf();
-    s->solver.sweep_mode = opt.sweep_mode;
-    s->integ_rule = opt.integrator;
-    s->solver.integ_rule = opt.integrator;
-    s->functional = opt.functional;
-    s->ctx = ctx; s->g = g; s->lsda = lsda ? 1 : 0; s->natoms = natoms; s->nspin = lsda ? 2 : 1; s->nV = natoms * s->nspin;
-    s->alpha = alpha;
-    const int N = g->N;
-    std::vector<dfta::JobSpec> specs;
+    dfta_ctx* ctx = s->ctx;
+    const int lsda = s->lsda, natoms = s->natoms;
     s->h_atoms.resize(natoms);
     s->h_bottom0.resize(s->nV);
     s->spin_nlev[0].resize(natoms); s->spin_nlev[1].assign(natoms, 0);
@@ -372,13 +337,13 @@ int dfta_scf_create_config(dfta_ctx* ctx, const dfta_grid* g, int lsda, int nato
         if (Z[a] < 1 || Z[a] > 118) {
             snprintf(ctx->err, sizeof(ctx->err), "Z out of range");
             if (nlev) dfta::config_set_error(ctx->err);
-            dfta_scf_destroy(s);
             return DFTA_ERR_INVALID;
         }
         AtomState& st = s->h_atoms[a];
         memset(&st, 0, sizeof(st));
         st.Z = Z[a];
         st.job_off = (int)specs.size();
+        for (int spin = 0; spin < s->nspin; ++spin) s->h_bottom0[s->nspin * a + spin] = -double(Z[a]) * Z[a] - 1.;     // DFTAtom.cpp:407 / 919,929
         int an[32], al[32], ao[32], bn[32], bl[32], bo[32], nA = 0, nB = 0;
         if (nlev) {                                            // explicit configuration (fractional occupations, cations)
             nA = nlev[2 * a];
@@ -401,83 +366,225 @@ int dfta_scf_create_config(dfta_ctx* ctx, const dfta_grid* g, int lsda, int nato
                 snprintf(ctx->err, sizeof(ctx->err), "atom %d: %g electrons for Z = %d (anions are not supported)", a, ne, Z[a]);
                 ok = false;
             }
-            if (!ok) { dfta::config_set_error(ctx->err); dfta_scf_destroy(s); return DFTA_ERR_INVALID; }
+            if (!ok) { dfta::config_set_error(ctx->err); return DFTA_ERR_INVALID; }
             st.nE = ne;
             st.nAlphaE = neA;
             st.nBetaE = ne - neA;
-            s->h_bottom0[lsda ? 2 * a : a] = -double(Z[a]) * Z[a] - 1.;
-            if (lsda) s->h_bottom0[2 * a + 1] = -double(Z[a]) * Z[a] - 1.;
         } else if (!lsda) {
-            nA = dfta_get_subshells_ex(Z[a], opt.aufbau, an, al, ao, 32);
-            if (nA < 0) { dfta_scf_destroy(s); return DFTA_ERR_INVALID; }
+            nA = dfta_get_subshells_ex(Z[a], aufbau, an, al, ao, 32);
+            if (nA < 0) return DFTA_ERR_INVALID;
             for (int k = 0; k < nA; ++k) specs.push_back({a, an[k], al[k], ao[k], static_cast<double>(ao[k])});
             st.nE = Z[a];
-            s->h_bottom0[a] = -double(Z[a]) * Z[a] - 1.;                                   // DFTAtom.cpp:407
         } else {
-            if (dfta_split_spin_ex(Z[a], opt.aufbau, &nA, &nB, an, al, ao, bn, bl, bo, 32) != DFTA_OK) { dfta_scf_destroy(s); return DFTA_ERR_INVALID; }
+            if (dfta_split_spin_ex(Z[a], aufbau, &nA, &nB, an, al, ao, bn, bl, bo, 32) != DFTA_OK) return DFTA_ERR_INVALID;
             int ne = 0;
             for (int k = 0; k < nA; ++k) { specs.push_back({2 * a, an[k], al[k], ao[k], static_cast<double>(ao[k])}); ne += ao[k]; }
             for (int k = 0; k < nB; ++k) specs.push_back({2 * a + 1, bn[k], bl[k], bo[k], static_cast<double>(bo[k])});
             st.nE = Z[a];
             st.nAlphaE = ne;
             st.nBetaE = Z[a] - ne;
-            s->h_bottom0[2 * a] = s->h_bottom0[2 * a + 1] = -double(Z[a]) * Z[a] - 1.;     // DFTAtom.cpp:919,929
         }
         s->spin_nlev[0][a] = nA;
         s->spin_nlev[1][a] = nB;
         st.job_end = (int)specs.size();
     }
+    return DFTA_OK;
+}
+
+int dfta_scf_create_config(dfta_ctx* ctx, const dfta_grid* g, int lsda, int natoms, const int* Z, const int* nlev, const int* cn,
+                           const int* cl, const double* cocc, double alpha, int levels_mode, int tree_depth,
+                           const dfta_scf_options* options, dfta_scf** out)
+{
+    if (!ctx || !g || !out) return DFTA_ERR_INVALID;
+    DFTA_ENTER(ctx);
+    DFTA_REQUIRE(ctx, natoms >= 1 && Z && alpha >= 0 && alpha <= 1, "scf arguments");
+    DFTA_REQUIRE(ctx, !nlev || (cn && cl && cocc), "configuration: n, l and occ are needed with nlev");
+    dfta_scf_options opt = {(int)sizeof(dfta_scf_options), DFTA_INT_SIMPSON38, DFTA_XC_VWN, DFTA_AUFBAU_REFERENCE, -1, DFTA_SWEEPS_EXACT};
+    if (options) {
+        // the caller's struct may be shorter (an older header) or longer (a newer one) than this library's: read what both know
+        const int sz = options->struct_size;
+        DFTA_REQUIRE(ctx, sz >= (int)(2 * sizeof(int)) && sz % (int)sizeof(int) == 0 && sz <= 4096, "dfta_scf_options::struct_size (set it to sizeof(dfta_scf_options))");
+        // members the caller's struct does not have keep the defaults above; those it has are taken as they are (0 = the reference's behaviour)
+        memcpy(&opt, options, std::min<size_t>((size_t)sz, sizeof(opt)));
+        opt.struct_size = (int)sizeof(dfta_scf_options);
+    }
+    DFTA_REQUIRE(ctx, opt.poisson_mode >= -1 && opt.poisson_mode <= DFTA_POISSON_ADAPTIVE, "poisson mode");
+    DFTA_REQUIRE(ctx, dfta_integral_shape_ok(opt.integrator, g->N), "integration rule / grid size");
+    DFTA_REQUIRE(ctx, opt.functional >= DFTA_XC_VWN && opt.functional <= DFTA_XC_PBE, "functional (DFTA_XC_VWN .. DFTA_XC_PBE)");
+    DFTA_REQUIRE(ctx, (opt.functional != DFTA_XC_CHACHIYO && opt.functional != DFTA_XC_CHACHIYO_IMPROVED) || !lsda, "the Chachiyo functional is LDA only (ExcCor.h)");
+    DFTA_REQUIRE(ctx, opt.functional != DFTA_XC_PBE || !g->uniform, "the PBE functional needs a logarithmic grid (no GGA on the uniform grid)");
+    DFTA_REQUIRE(ctx, opt.aufbau == DFTA_AUFBAU_REFERENCE || opt.aufbau == DFTA_AUFBAU_TRANSITION_METALS, "aufbau");
+    DFTA_REQUIRE(ctx, opt.sweep_mode == DFTA_SWEEPS_EXACT || opt.sweep_mode == DFTA_SWEEPS_TOLERANCE, "sweep mode");
+    DFTA_REQUIRE(ctx, opt.sweep_mode == DFTA_SWEEPS_EXACT || dfta_scan_supported(g), "the tolerance mode of the sweeps needs a logarithmic grid of 12 .. 20 multigrid levels");
+    dfta_scf* s = new dfta_scf();
+    struct Guard { dfta_scf* s; ~Guard() { dfta_scf_destroy(s); } } guard{s};      // every error return below destroys what has been made
+    s->solver.sweep_mode = opt.sweep_mode;
+    s->integ_rule = opt.integrator;
+    s->solver.integ_rule = opt.integrator;
+    s->functional = opt.functional;
+    s->ctx = ctx; s->g = g; s->lsda = lsda ? 1 : 0; s->natoms = natoms; s->nspin = lsda ? 2 : 1; s->nV = natoms * s->nspin;
+    s->alpha = alpha;
+    const int N = g->N;
+    std::vector<dfta::JobSpec> specs;
+    int rc = scf_configure(s, Z, nlev, cn, cl, cocc, opt.aufbau, specs);
+    if (rc) return rc;
     s->levels_mode = levels_mode;
     s->h_job_bottom.resize(specs.size());
     for (size_t k = 0; k < specs.size(); ++k) s->h_job_bottom[k] = s->h_bottom0[specs[k].v];
-    int rc = s->solver.setup(ctx, g, levels_mode, tree_depth, s->nV, specs);
-    if (rc) { dfta_scf_destroy(s); return rc; }
+    rc = s->solver.setup(ctx, g, levels_mode, tree_depth, s->nV, specs);
+    if (rc) return rc;
     rc = opt.poisson_mode < 0 ? dfta_poisson_create(ctx, g, natoms, &s->poisson) : dfta_poisson_create_ex(ctx, g, natoms, opt.poisson_mode, &s->poisson);
-    if (rc) { dfta_scf_destroy(s); return rc; }
+    if (rc) return rc;
 
     hipStream_t st = ctx->stream;
     const size_t aN = (size_t)natoms * N;
     hipError_t e = hipSuccess;
-    auto al = [&](double** p, size_t cnt) { if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(p), cnt * sizeof(double)); };
-    al(&s->d_density, aN); al(&s->d_dA, aN); al(&s->d_dB, aN); al(&s->d_V, aN * s->nspin); al(&s->d_U, aN); al(&s->d_Vexc, aN);
-    al(&s->d_va, aN); al(&s->d_vb, aN); al(&s->d_eexc, aN); al(&s->d_newDensity, aN * s->nspin); al(&s->d_integrands, aN * 5);
-    al(&s->d_integrals, (size_t)natoms * 5); al(&s->d_records, (size_t)natoms * DFTA_RECORD_DOUBLES);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&s->d_atoms), sizeof(AtomState) * natoms);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&s->d_Ne), sizeof(double) * natoms);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&s->d_fin), sizeof(int) * natoms);
+    auto al = [&](auto& buf, size_t cnt) { if (e == hipSuccess) e = buf.alloc(cnt); };
+    al(s->d_density, aN); al(s->d_dA, aN); al(s->d_dB, aN); al(s->d_V, aN * s->nspin); al(s->d_U, aN); al(s->d_Vexc, aN);
+    al(s->d_va, aN); al(s->d_vb, aN); al(s->d_eexc, aN); al(s->d_newDensity, aN * s->nspin); al(s->d_integrands, aN * 5);
+    al(s->d_integrals, (size_t)natoms * 5); al(s->d_records, (size_t)natoms * DFTA_RECORD_DOUBLES);
+    al(s->d_atoms, natoms); al(s->d_Ne, natoms); al(s->d_fin, natoms);
     if (e == hipSuccess) e = hipMemsetAsync(s->d_fin, 0, sizeof(int) * natoms, st);
-    for (auto& ev : s->ev) if (e == hipSuccess) e = hipEventCreate(&ev);
+    for (auto& ev : s->ev) if (e == hipSuccess) e = hipEventCreate(&ev.e);
     if (e == hipSuccess) e = hipMemcpyAsync(s->d_atoms, s->h_atoms.data(), sizeof(AtomState) * natoms, hipMemcpyHostToDevice, st);
     std::vector<double> h_ne(natoms);
     for (int a = 0; a < natoms; ++a) h_ne[a] = s->h_atoms[a].nE;
     if (e == hipSuccess) e = hipMemcpyAsync(s->d_Ne, h_ne.data(), sizeof(double) * natoms, hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemsetAsync(s->d_records, 0, sizeof(double) * natoms * DFTA_RECORD_DOUBLES, st);
-    if (e != hipSuccess) {
-        snprintf(ctx->err, sizeof(ctx->err), "scf alloc: %s", hipGetErrorString(e));
-        dfta_scf_destroy(s);
-        return DFTA_ERR_HIP;
-    }
+    if (e != hipSuccess) { snprintf(ctx->err, sizeof(ctx->err), "scf alloc: %s", hipGetErrorString(e)); return DFTA_ERR_HIP; }
     // DFTAtom.cpp:371-392 / 874-904: flat density, Poisson, v_xc, start potential
     const dim3 grid(std::min(64, (N + 255) / 256), natoms), block(256);
-    hipLaunchKernelGGL(k_init_density, grid, block, 0, st, s->d_atoms, s->lsda, N, g->Rmax, s->d_density, s->d_dA, s->d_dB);
+    hipLaunchKernelGGL(k_init_density, grid, block, 0, st, s->d_atoms.p, s->lsda, N, g->Rmax, s->d_density.p, s->d_dA.p, s->d_dB.p);
     rc = dfta_poisson_solve_launch(s->poisson, s->d_Ne, s->d_density, s->d_U, nullptr, nullptr, nullptr);
     if (!rc) rc = dfta_poisson_finish(s->poisson, s->d_Ne, s->d_density, s->d_U, nullptr, nullptr, nullptr);
     if (!rc) rc = scf_xc(s);
-    if (rc) { dfta_scf_destroy(s); return rc; }
-    hipLaunchKernelGGL(k_potential, grid, block, 0, st, s->d_atoms, s->lsda, N, g->d_r, s->d_U, s->d_Vexc, s->d_va, s->d_vb, s->d_V);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_potential, grid, block, 0, st, s->d_atoms.p, s->lsda, N, g->d_r, s->d_U.p, s->d_Vexc.p, s->d_va.p, s->d_vb.p, s->d_V.p);
     e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) {
-        snprintf(ctx->err, sizeof(ctx->err), "scf init: %s", hipGetErrorString(e));
-        dfta_scf_destroy(s);
-        return DFTA_ERR_HIP;
-    }
+    if (e != hipSuccess) { snprintf(ctx->err, sizeof(ctx->err), "scf init: %s", hipGetErrorString(e)); return DFTA_ERR_HIP; }
     unsigned long long dummy;
     rc = dfta_poisson_take_vcycles(s->poisson, &dummy);
-    if (rc) { dfta_scf_destroy(s); return rc; }
+    if (rc) return rc;
     s->debug_levels = dfta_knob("DEBUG_LEVELS") != nullptr;
     s->h_frozen.assign(specs.size(), 0);
+    guard.s = nullptr;
     *out = s;
+    return DFTA_OK;
+}
+
+// The multigrid solver of the live atoms' size class (made when first wanted) and that class's size, or null: the batch's own solver
+// does the work.  An optimisation only: the level solve and the mixing of this step have already run, so nothing may fail here
+static dfta_poisson* scf_live_solver(dfta_scf* s, int nlive, int* cls_atoms)
+{
+    if (nlive <= 0 || dfta_knob("SCF_NOLIVE") != nullptr) return nullptr;
+    for (int c = 0; c < kLiveClasses; ++c) {
+        if (kLiveClassAtoms[c] < nlive) continue;
+        if (kLiveClassAtoms[c] >= s->natoms) break;              // the batch's own solver is of that class already
+        dfta_scf::LiveSolver& ls = s->live_solver[c];
+        if (!ls.tried) {
+            ls.tried = true;
+            int Gbig = 0;
+            dfta_poisson_group_state(s->poisson, &Gbig, nullptr, nullptr);
+            // if the class solver cannot be made (memory), the batch's own solver does the work
+            if (dfta_poisson_create_ex(s->ctx, s->g, kLiveClassAtoms[c], dfta_poisson_mode(s->poisson), &ls.p)) { ls.p = nullptr; s->ctx->err[0] = 0; (void)hipGetLastError(); }
+            if (ls.p) {
+                dfta_poisson_group_state(ls.p, &ls.G, nullptr, nullptr);
+                if (ls.G <= Gbig) { dfta_poisson_destroy(ls.p); ls.p = nullptr; }     // nothing to gain on this grid
+            }
+        }
+        *cls_atoms = kLiveClassAtoms[c];
+        return ls.p;                                              // the smallest class that holds the live atoms, or the batch's solver
+    }
+    return nullptr;
+}
+
+// Gathered copies of the live atoms' densities for the solver of their size class: room for cls_atoms rows (grown when needed), skip flags,
+// atom indices and electron counts staged and uploaded, the rows gathered.  *gathered = false: no room, the batch's own solver (same bits).
+static int scf_gather_live(dfta_scf* s, const std::vector<int>& live_atoms, int cls_atoms, bool* gathered)
+{
+    dfta_ctx* ctx = s->ctx;
+    hipStream_t st = ctx->stream;
+    const int N = s->g->N, nlive = static_cast<int>(live_atoms.size());
+    *gathered = false;
+    if (s->live_cap < cls_atoms) {
+        s->free_live();
+        hipError_t e = s->d_liveIdx.alloc(2 * (size_t)cls_atoms);
+        if (e == hipSuccess) e = s->d_liveNe.alloc(cls_atoms);
+        if (e == hipSuccess) e = s->d_liveRho.alloc((size_t)cls_atoms * N);
+        if (e == hipSuccess) e = s->d_liveU.alloc((size_t)cls_atoms * N);
+        if (e != hipSuccess) {
+            s->free_live();
+            (void)hipGetLastError();
+            return DFTA_OK;
+        }
+        s->live_cap = cls_atoms;
+    }
+    const int cap = s->live_cap;
+    s->h_liveIdx.assign(2 * cap, 0);
+    s->h_liveNe.assign(cap, 1.);
+    for (int i = 0; i < cap; ++i) {
+        const bool on = i < nlive;
+        if (on) s->h_liveNe[i] = s->h_atoms[live_atoms[i]].nE;
+        s->h_liveIdx[i] = on ? 0 : 1;
+        s->h_liveIdx[cap + i] = on ? live_atoms[i] : 0;
+    }
+    DFTA_HIP(ctx, hipMemcpyAsync(s->d_liveIdx, s->h_liveIdx.data(), sizeof(int) * s->h_liveIdx.size(), hipMemcpyHostToDevice, st));
+    DFTA_HIP(ctx, hipMemcpyAsync(s->d_liveNe, s->h_liveNe.data(), sizeof(double) * cap, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_gather_rows, dim3(std::min(256, (N + 255) / 256), nlive), dim3(256), 0, st, s->d_density.p, s->d_liveIdx + cap, N, s->d_liveRho.p);
+    DFTA_CHECK_LAUNCH(ctx);
+    *gathered = true;
+    return DFTA_OK;
+}
+
+// The step's statistics into the caller's struct, which may be an older (shorter) or a newer (longer) one than this library's: fill this
+// library's, hand over what both know.  solved_by: the multigrid solver that ran in this step.
+static int scf_fill_stats(dfta_scf* s, const dfta::LevelStats& ls, dfta_poisson* solved_by, dfta_step_stats* user)
+{
+    dfta_ctx* ctx = s->ctx;
+    const int user_size = user->struct_size;
+    DFTA_REQUIRE(ctx, user_size >= (int)(4 * sizeof(int)) && user_size % (int)sizeof(int) == 0 && user_size <= 4096,
+                 "dfta_step_stats::struct_size (set it to sizeof(dfta_step_stats) before the call)");
+    dfta_step_stats mine;
+    dfta_step_stats* const stats = &mine;
+    DFTA_HIP(ctx, hipEventSynchronize(s->ev[3]));
+    memset(stats, 0, sizeof(*stats));
+    stats->struct_size = (int)sizeof(dfta_step_stats);
+    stats->levels_fallbacks = (s->solver.scan_fallbacks + s->solver.persist_fallbacks) - s->fallbacks_seen;
+    s->fallbacks_seen = s->solver.scan_fallbacks + s->solver.persist_fallbacks;
+    DFTA_HIP(ctx, hipEventElapsedTime(&stats->ms_levels, s->ev[0], s->ev[1]));
+    DFTA_HIP(ctx, hipEventElapsedTime(&stats->ms_poisson, s->ev[1], s->ev[2]));
+    DFTA_HIP(ctx, hipEventElapsedTime(&stats->ms_tail, s->ev[2], s->ev[3]));
+    stats->ms_poisson_kernel = stats->ms_poisson;
+    stats->ms_sweep_kernels = ls.ms_sweep;
+    stats->rounds = ls.rounds;
+    stats->levels_layout = ls.layout;
+    dfta_poisson_group_state(solved_by, &stats->poisson_groups, nullptr, nullptr);
+    stats->sweeps_issued = ls.sweeps_issued;
+    stats->points_traversed = ls.points_traversed;
+    long ref = 0;
+    long long pts = 0, skipped = 0;
+    for (const auto& j : s->h_jobs) if (!j.frozen) {
+        ref += j.n_count + j.n_zero + 1;   // + the matched solve of each level
+        pts += j.n_points;
+        if (j.nodes == 0) skipped += j.cur_len[1];     // the second bisection of a node-less level is pure arithmetic
+        skipped += j.n_fixed;                            // a third bisection on its fixed point (walk_job)
+    }
+    stats->sweeps_reference = ref;
+    stats->sweeps_reference_executed = ref - (long)skipped;
+    stats->points_reference = (long)pts;
+    unsigned long long vc = 0;
+    int rc = dfta_poisson_take_vcycles(s->poisson, &vc);
+    if (rc) return rc;
+    for (auto& lv : s->live_solver) if (lv.p) {
+        unsigned long long vl = 0;
+        rc = dfta_poisson_take_vcycles(lv.p, &vl);
+        if (rc) return rc;
+        vc += vl;
+    }
+    stats->vcycles = (long)vc;
+    memcpy(user, &mine, std::min<size_t>((size_t)user_size, sizeof(mine)));
+    user->struct_size = user_size;
     return DFTA_OK;
 }
 
@@ -496,7 +603,6 @@ int dfta_scf_step(dfta_scf* s, dfta_step_stats* stats)
     dfta::LevelStats ls;
     // bracket starts: CHAINED hands E-3 from level to level exactly as DFTAtom.cpp:541 (levels one after the other);
     // BATCHED starts every level concurrently from max(-Z^2-1, min Veff_l) (LevelSolver::clamp_bottoms)
-    const int run_mode = s->levels_mode;
     // atoms that have met the reference's stop test (DFTAtom.cpp:474-479) are frozen: no level search, no mixing, no
     // Poisson solve, no new energies -- every atom of a batch ends in the state of its own last step
     bool any_frozen = false;
@@ -505,18 +611,18 @@ int dfta_scf_step(dfta_scf* s, dfta_step_stats* stats)
         for (int k = as.job_off; k < as.job_end; ++k) s->h_frozen[k] = as.finished ? 1 : 0;
         any_frozen = any_frozen || as.finished;
     }
-    dfta_range* r_levels = new dfta_range("dfta: level search (LoopOverLevels: all subshells of the batch)");
-    int rc = s->solver.run(s->d_V, s->h_job_bottom.data(), run_mode, s->d_newDensity, stats ? &ls : nullptr,
+    int rc;
+    {
+        dfta_range r_levels("dfta: level search (LoopOverLevels: all subshells of the batch)");
+        rc = s->solver.run(s->d_V, s->h_job_bottom.data(), s->levels_mode, s->d_newDensity, stats ? &ls : nullptr,
                            any_frozen ? s->h_frozen.data() : nullptr);
-    delete r_levels;
+    }
     if (rc) return rc;
     {
         std::vector<dfta::Job>& jobs = s->h_jobs;
         rc = s->solver.fetch_jobs(jobs);
         if (rc) return rc;
-        for (size_t k = 0; k < jobs.size(); ++k) {
-            s->h_job_bottom[k] = s->h_bottom0[jobs[k].v];
-        }
+        for (size_t k = 0; k < jobs.size(); ++k) s->h_job_bottom[k] = s->h_bottom0[jobs[k].v];
         s->steps_done++;
         if (s->debug_levels) {
             for (size_t k = 0; k < jobs.size(); ++k)
@@ -525,75 +631,24 @@ int dfta_scf_step(dfta_scf* s, dfta_step_stats* stats)
                         jobs[k].cur_len[2], jobs[k].pred_len[0], jobs[k].pred_len[1], jobs[k].pred_len[2], jobs[k].n_count, jobs[k].n_zero);
         }
     }
-    hipLaunchKernelGGL(k_mix, grid, block, 0, st, s->lsda, N, s->alpha, 1. - s->alpha, g->d_fpr2, s->d_newDensity, s->d_density,
-                       s->d_dA, s->d_dB, s->d_fin);
+    hipLaunchKernelGGL(k_mix, grid, block, 0, st, s->lsda, N, s->alpha, 1. - s->alpha, g->d_fpr2, s->d_newDensity.p, s->d_density.p,
+                       s->d_dA.p, s->d_dB.p, s->d_fin.p);
     DFTA_CHECK_LAUNCH(ctx);
     DFTA_HIP(ctx, hipEventRecord(s->ev[1], st));
     // live atoms of this step (finished ones are frozen, see above) and the solver of their size class
     std::vector<int> live_atoms;
     for (int a = 0; a < natoms; ++a) if (!s->h_atoms[a].finished) live_atoms.push_back(a);
     const int nlive = static_cast<int>(live_atoms.size());
-    dfta_poisson* pl = nullptr;
     int cls_atoms = 0;
-    if (nlive > 0 && dfta_knob("SCF_NOLIVE") == nullptr) {
-        for (int c = 0; c < kLiveClasses && !pl; ++c) {
-            if (kLiveClassAtoms[c] < nlive) continue;
-            if (kLiveClassAtoms[c] >= natoms) break;              // the batch's own solver is of that class already
-            dfta_scf::LiveSolver& ls = s->live_solver[c];
-            if (!ls.tried) {
-                ls.tried = true;
-                int Gbig = 0;
-                dfta_poisson_group_state(s->poisson, &Gbig, nullptr, nullptr);
-                // an optimisation only: if the class solver cannot be made (memory), the batch's own solver does the work --
-                // the level solve and the mixing of this step have already run, so nothing may fail here
-                rc = dfta_poisson_create_ex(ctx, g, kLiveClassAtoms[c], dfta_poisson_mode(s->poisson), &ls.p);
-                if (rc) { ls.p = nullptr; ctx->err[0] = 0; (void)hipGetLastError(); rc = DFTA_OK; }
-                if (ls.p) {
-                    dfta_poisson_group_state(ls.p, &ls.G, nullptr, nullptr);
-                    if (ls.G <= Gbig) { dfta_poisson_destroy(ls.p); ls.p = nullptr; }     // nothing to gain on this grid
-                }
-            }
-            if (ls.p) { pl = ls.p; cls_atoms = kLiveClassAtoms[c]; }
-            break;                                                  // the smallest class that holds the live atoms, or the batch's solver
-        }
+    dfta_poisson* pl = scf_live_solver(s, nlive, &cls_atoms);
+    bool use_live = false;
+    if (pl) {
+        rc = scf_gather_live(s, live_atoms, cls_atoms, &use_live);
+        if (rc) return rc;
     }
-    bool use_live = pl != nullptr;
-    std::vector<int> h_live;
-    if (use_live && s->live_cap < cls_atoms) {
-        for (void* q : {(void*)s->d_liveIdx, (void*)s->d_liveNe, (void*)s->d_liveRho, (void*)s->d_liveU}) if (q) (void)hipFree(q);
-        s->d_liveIdx = nullptr; s->d_liveNe = nullptr; s->d_liveRho = nullptr; s->d_liveU = nullptr;
-        s->live_cap = 0;
-        hipError_t e = hipMalloc(reinterpret_cast<void**>(&s->d_liveIdx), sizeof(int) * 2 * cls_atoms);
-        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&s->d_liveNe), sizeof(double) * cls_atoms);
-        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&s->d_liveRho), sizeof(double) * (size_t)cls_atoms * N);
-        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&s->d_liveU), sizeof(double) * (size_t)cls_atoms * N);
-        if (e == hipSuccess) s->live_cap = cls_atoms;
-        else {                                             // no room for the gathered copies: the batch's own solver (same bits)
-            for (void* q : {(void*)s->d_liveIdx, (void*)s->d_liveNe, (void*)s->d_liveRho, (void*)s->d_liveU}) if (q) (void)hipFree(q);
-            s->d_liveIdx = nullptr; s->d_liveNe = nullptr; s->d_liveRho = nullptr; s->d_liveU = nullptr;
-            (void)hipGetLastError();
-            use_live = false;
-            pl = nullptr;
-        }
-    }
-    if (use_live) {
-        const int cap = s->live_cap;
-        h_live.assign(2 * cap, 0);
-        s->h_liveNe.assign(cap, 1.);
-        for (int i = 0; i < cap; ++i) {
-            const bool on = i < nlive;
-            if (on) s->h_liveNe[i] = s->h_atoms[live_atoms[i]].nE;
-            h_live[i] = on ? 0 : 1;
-            h_live[cap + i] = on ? live_atoms[i] : 0;
-        }
-        DFTA_HIP(ctx, hipMemcpyAsync(s->d_liveIdx, h_live.data(), sizeof(int) * h_live.size(), hipMemcpyHostToDevice, st));
-        DFTA_HIP(ctx, hipMemcpyAsync(s->d_liveNe, s->h_liveNe.data(), sizeof(double) * cap, hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(k_gather_rows, dim3(std::min(256, (N + 255) / 256), nlive), dim3(256), 0, st, s->d_density, s->d_liveIdx + cap, N, s->d_liveRho);
-        DFTA_CHECK_LAUNCH(ctx);
-    }
+    dfta_poisson* ps = use_live ? pl : s->poisson;
     {
         dfta_range r_poisson("dfta: multigrid Poisson solve (FullCycle)");
-        dfta_poisson* ps = use_live ? pl : s->poisson;
         const double* pNe = use_live ? s->d_liveNe : s->d_Ne;
         const double* pRho = use_live ? s->d_liveRho : s->d_density;
         double* pU = use_live ? s->d_liveU : s->d_U;
@@ -606,15 +661,15 @@ int dfta_scf_step(dfta_scf* s, dfta_step_stats* stats)
         rc = dfta_poisson_finish(ps, pNe, pRho, pU, nullptr, nullptr, pSkip);
         if (rc) return rc;
         if (use_live) {
-            hipLaunchKernelGGL(k_scatter_rows, dim3(std::min(256, (N + 255) / 256), nlive), dim3(256), 0, st, s->d_liveU, s->d_liveIdx + s->live_cap, N, s->d_U);
+            hipLaunchKernelGGL(k_scatter_rows, dim3(std::min(256, (N + 255) / 256), nlive), dim3(256), 0, st, s->d_liveU.p, s->d_liveIdx + s->live_cap, N, s->d_U.p);
             DFTA_CHECK_LAUNCH(ctx);
         }
     }
     dfta_range r_tail("dfta: XC + integrands + ordered integrals + energies");
     rc = scf_xc(s);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_tail, grid, block, 0, st, s->d_atoms, s->lsda, N, g->d_r, g->d_cnst, s->d_density, s->d_dA, s->d_dB, s->d_U,
-                       s->d_Vexc, s->d_va, s->d_vb, s->d_eexc, s->d_V, s->d_integrands, g->uniform);
+    hipLaunchKernelGGL(k_tail, grid, block, 0, st, s->d_atoms.p, s->lsda, N, g->d_r, g->d_cnst, s->d_density.p, s->d_dA.p, s->d_dB.p, s->d_U.p,
+                       s->d_Vexc.p, s->d_va.p, s->d_vb.p, s->d_eexc.p, s->d_V.p, s->d_integrands.p, g->uniform);
     DFTA_CHECK_LAUNCH(ctx);
     // Simpson38(1, .) on the logarithmic grid (DFTAtom.cpp:459-467), Simpson38(h, .) on the uniform one (DFTAtom.cpp:167-177)
     // (tolerance mode of the sweeps: the two sums of Simpson 3/8 in parallel, as the normalisation integral of scan_match takes them --
@@ -624,61 +679,14 @@ int dfta_scf_step(dfta_scf* s, dfta_step_stats* stats)
     else
         rc = dfta_launch_integrate_ordered(ctx, s->integ_rule, g->uniform ? g->h : 1.0, s->d_integrands, N, natoms * 5, (size_t)N, s->d_integrals);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_energies, dim3((natoms + 63) / 64), dim3(64), 0, st, s->d_atoms, natoms, s->solver.d_jobs, s->solver.d_occ, s->d_integrals,
-                       s->d_records, s->d_fin);
+    hipLaunchKernelGGL(k_energies, dim3((natoms + 63) / 64), dim3(64), 0, st, s->d_atoms.p, natoms, s->solver.d_jobs.p, s->solver.d_occ.p, s->d_integrals.p,
+                       s->d_records.p, s->d_fin.p);
     DFTA_CHECK_LAUNCH(ctx);
     DFTA_HIP(ctx, hipEventRecord(s->ev[3], st));
     // the step ends synchronised with the atoms' state on the host: the next step freezes what has finished
     DFTA_HIP(ctx, hipMemcpyAsync(s->h_atoms.data(), s->d_atoms, sizeof(AtomState) * natoms, hipMemcpyDeviceToHost, st));
     DFTA_HIP(ctx, hipStreamSynchronize(st));
-    if (stats) {
-        // the caller's struct may be an older (shorter) or a newer (longer) one: fill this library's, hand over what both know
-        dfta_step_stats* const user = stats;
-        const int user_size = user->struct_size;
-        DFTA_REQUIRE(ctx, user_size >= (int)(4 * sizeof(int)) && user_size % (int)sizeof(int) == 0 && user_size <= 4096,
-                     "dfta_step_stats::struct_size (set it to sizeof(dfta_step_stats) before the call)");
-        dfta_step_stats mine;
-        stats = &mine;
-        DFTA_HIP(ctx, hipEventSynchronize(s->ev[3]));
-        memset(stats, 0, sizeof(*stats));
-        stats->struct_size = (int)sizeof(dfta_step_stats);
-        stats->levels_fallbacks = (s->solver.scan_fallbacks + s->solver.persist_fallbacks) - s->fallbacks_seen;
-        s->fallbacks_seen = s->solver.scan_fallbacks + s->solver.persist_fallbacks;
-        DFTA_HIP(ctx, hipEventElapsedTime(&stats->ms_levels, s->ev[0], s->ev[1]));
-        DFTA_HIP(ctx, hipEventElapsedTime(&stats->ms_poisson, s->ev[1], s->ev[2]));
-        DFTA_HIP(ctx, hipEventElapsedTime(&stats->ms_tail, s->ev[2], s->ev[3]));
-        stats->ms_poisson_kernel = stats->ms_poisson;
-        stats->ms_sweep_kernels = ls.ms_sweep;
-        stats->rounds = ls.rounds;
-        stats->levels_layout = ls.layout;
-        dfta_poisson_group_state(use_live ? pl : s->poisson, &stats->poisson_groups, nullptr, nullptr);
-        stats->sweeps_issued = ls.sweeps_issued;
-        stats->points_traversed = ls.points_traversed;
-        long ref = 0;
-        long long pts = 0, skipped = 0;
-        for (const auto& j : s->h_jobs) if (!j.frozen) {
-            ref += j.n_count + j.n_zero + 1;   // + the matched solve of each level
-            pts += j.n_points;
-            if (j.nodes == 0) skipped += j.cur_len[1];     // the second bisection of a node-less level is pure arithmetic
-            skipped += j.n_fixed;                            // a third bisection on its fixed point (walk_job)
-        }
-        stats->sweeps_reference = ref;
-        stats->sweeps_reference_executed = ref - (long)skipped;
-        stats->points_reference = (long)pts;
-        unsigned long long vc = 0;
-        rc = dfta_poisson_take_vcycles(s->poisson, &vc);
-        if (rc) return rc;
-        for (auto& ls : s->live_solver) if (ls.p) {
-            unsigned long long vl = 0;
-            rc = dfta_poisson_take_vcycles(ls.p, &vl);
-            if (rc) return rc;
-            vc += vl;
-        }
-        stats->vcycles = (long)vc;
-        memcpy(user, &mine, std::min<size_t>((size_t)user_size, sizeof(mine)));
-        user->struct_size = user_size;
-    }
-    return DFTA_OK;
+    return stats ? scf_fill_stats(s, ls, ps, stats) : DFTA_OK;
 }
 
 int dfta_scf_get_energies(dfta_scf* s, dfta_energies* e, int* finished)
