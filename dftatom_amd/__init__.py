@@ -28,6 +28,7 @@ POISSON_DEFAULT, POISSON_EXACT, POISSON_TOLERANCE, POISSON_ADAPTIVE = -1, 0, 1, 
 INT_TRAPEZOID, INT_SIMPSON13, INT_SIMPSON38, INT_BOOLE, INT_ROMBERG = range(5)
 XC_VWN, XC_CHACHIYO, XC_CHACHIYO_IMPROVED, XC_PW92, XC_PBE = range(5)
 AUFBAU_REFERENCE, AUFBAU_TRANSITION_METALS = range(2)
+MIX_LINEAR, MIX_ANDERSON = range(2)    # dfta_scf_options::mixing
 RECORD_DOUBLES = 64
 
 c_dp = C.POINTER(C.c_double)
@@ -54,7 +55,8 @@ class Energies(C.Structure):
 
 
 class ScfOptions(C.Structure):
-    _fields_ = [("struct_size", C.c_int), ("integrator", C.c_int), ("functional", C.c_int), ("aufbau", C.c_int), ("poisson_mode", C.c_int), ("sweep_mode", C.c_int)]
+    _fields_ = [("struct_size", C.c_int), ("integrator", C.c_int), ("functional", C.c_int), ("aufbau", C.c_int), ("poisson_mode", C.c_int), ("sweep_mode", C.c_int),
+                ("mixing", C.c_int), ("mix_history", C.c_int), ("mix_warmup", C.c_int)]
 
 
 class StepStats(C.Structure):
@@ -552,8 +554,10 @@ class Scf:
 
     def __init__(self, ctx, grid, Z, lsda=False, alpha=0.5, levels_mode=LEVELS_BATCHED, tree_depth=0, integrator=INT_SIMPSON38,
                  functional=XC_VWN, aufbau=AUFBAU_REFERENCE, poisson_mode=POISSON_DEFAULT, sweep_mode=SWEEPS_EXACT, config=None,
-                 charge=None):
-        """config: an electron configuration (parse_config's text, or its result) for every atom, or a list of them, one per atom;
+                 charge=None, mixing=MIX_LINEAR, mix_history=0, mix_warmup=0):
+        """mixing: MIX_LINEAR (the reference's) or MIX_ANDERSON (include/dftatom_hip.h: about half the steps); mix_history: pairs kept per
+        atom (1 .. 8, 0: 4); mix_warmup: linear steps before the first accelerated one (0: 3).
+        config: an electron configuration (parse_config's text, or its result) for every atom, or a list of them, one per atom;
         charge: an int for every atom, or a list of ints (ion_config: cations).  Neither: the Aufbau configuration of each Z.
         The nuclear charge stays Z; the electron count sets the start density and the Poisson boundary U(Rmax)."""
         self.ctx, self.grid = ctx, grid
@@ -561,7 +565,8 @@ class Scf:
         self.natoms = len(self.Z)
         self.lsda = bool(lsda)
         h = vp()
-        opt = ScfOptions(C.sizeof(ScfOptions), integrator, functional, aufbau, poisson_mode, sweep_mode)
+        opt = ScfOptions(C.sizeof(ScfOptions), integrator, functional, aufbau, poisson_mode, sweep_mode, int(mixing), int(mix_history),
+                         int(mix_warmup))
         if config is not None and charge is not None:
             raise ValueError("give config or charge, not both")
         self.configs = None

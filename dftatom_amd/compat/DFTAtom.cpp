@@ -18,6 +18,7 @@ int DFTAtom::functional = DFTA_XC_VWN;
 int DFTAtom::charge = 0;
 std::string DFTAtom::config;
 int DFTAtom::poissonMode = -1;      // as dfta_poisson_create: exact unless $DFTA_DEBUG POISSON_MODE (--poisson= overrides)
+int DFTAtom::mixing = DFTA_MIX_LINEAR;     // --mixing=anderson: Anderson density mixing, default history and warm-up
 std::ostream* DFTAtom::jsonOut = nullptr;
 
 namespace {
@@ -105,7 +106,7 @@ void DFTAtom::Run(bool lsda, bool uniform, int Z, int MultigridLevels, double al
     dfta_scf_options opt = {};                    // zero = what the reference runs
     opt.struct_size = (int)sizeof(opt);
     opt.integrator = integrator; opt.functional = functional; opt.aufbau = DFTA_AUFBAU_REFERENCE;
-    opt.poisson_mode = poissonMode; opt.sweep_mode = sweepMode;
+    opt.poisson_mode = poissonMode; opt.sweep_mode = sweepMode; opt.mixing = mixing;
     if (charge == 0 && config.empty()) {
         dfta_compat::check(dfta_scf_create_ex(rt.ctx(), grid, lsda ? 1 : 0, 1, &Z, alpha, levelsMode, 0, &opt, &scf), rt.ctx(), "dfta_scf_create");
     } else {

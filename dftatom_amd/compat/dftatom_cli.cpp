@@ -13,6 +13,7 @@
 // --json[=FILE]: one JSON line per SCF step (17-digit energies and eigenvalues, per-level status bits and sweep counts, rounds, V-cycles,
 //                phase times) to FILE, or to stderr -- the console protocol on stdout stays the reference's.
 // --sweeps=exact|tolerance, --poisson=exact|tolerance|adaptive: the opt-in tolerance modes of the device path (include/dftatom_hip.h).
+// --mixing=linear (default, the reference's density mixing) | anderson (Anderson acceleration: about half the SCF steps, same protocol).
 // --xc=vwn (default, what the reference runs) | chachiyo | chachiyo-improved (LDA only) | pw92 | pbe (logarithmic grid only).
 // --charge=q: the cation X^q+ (electrons leave the subshell of highest n, then highest l: Fe+ = [Ar] 3d6 4s1);
 // --config="[Ne] 3s2 3p5.5": an explicit, possibly fractional configuration ("2p3/1": LSDA alpha / beta split).  An invalid
@@ -89,6 +90,11 @@ int main(int argc, char** argv)
             DFT::DFTAtom::sweepMode = a == "--sweeps=tolerance" ? DFTA_SWEEPS_TOLERANCE : DFTA_SWEEPS_EXACT;
         } else if (a == "--poisson=tolerance" || a == "--poisson=adaptive" || a == "--poisson=exact") {
             DFT::DFTAtom::poissonMode = a == "--poisson=tolerance" ? DFTA_POISSON_TOLERANCE : (a == "--poisson=adaptive" ? DFTA_POISSON_ADAPTIVE : DFTA_POISSON_EXACT);
+        } else if (a == "--mixing=linear" || a == "--mixing=anderson") {
+            DFT::DFTAtom::mixing = a == "--mixing=anderson" ? DFTA_MIX_ANDERSON : DFTA_MIX_LINEAR;
+        } else if (a.rfind("--mixing=", 0) == 0) {
+            std::cerr << "unknown mixing " << a.substr(9) << std::endl;
+            bad = true;
         } else if (a.rfind("--xc=", 0) == 0) {
             const std::string n = a.substr(5);
             const char* names[] = {"vwn", "chachiyo", "chachiyo-improved", "pw92", "pbe"};      // DFTA_XC_VWN .. DFTA_XC_PBE
@@ -128,6 +134,7 @@ int main(int argc, char** argv)
                   << "           [--charge=q | --config=\"[Ne] 3s2 3p5.5\"]\n"
                   << "       " << argv[0] << " --ini DFTAtom.ini [--uniform] [chained] [--integrator=NAME] [--xc=NAME] [--charge=q | --config=TEXT]\n"
                   << "       --xc=vwn (default) | chachiyo | chachiyo-improved | pw92 | pbe\n"
+                  << "       --mixing=linear (default) | anderson: Anderson density mixing, fewer SCF steps\n"
                   << "       --charge=q: the cation (q > 0); --config: an electron configuration, fractional occupations allowed\n";
         return 2;
     }

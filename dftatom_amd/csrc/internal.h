@@ -90,3 +90,23 @@ int dfta_launch_integrate_ordered(dfta_ctx* ctx, int rule /* DFTA_INT_* */, doub
 // scan_match is summed that way too); same weights, a different order of additions
 int dfta_launch_integrate_simpson38_parallel(dfta_ctx* ctx, double delta, const double* dVals, int n, int nvec, size_t stride, double* dOut);
 int dfta_integral_shape_ok(int rule, int sz);
+
+// mixing.hip: Anderson density mixing (dfta_scf_options::mixing), three ordinary launches in place of k_mix
+constexpr int kAndersonMaxHistory = 8;
+constexpr int kAndersonDots = kAndersonMaxHistory * (kAndersonMaxHistory + 1) / 2 + kAndersonMaxHistory;   // A's upper triangle, then b
+constexpr int kAndersonChunk = 1024;       // nodes per workgroup of k_anderson_gram: the chunking is a function of N alone
+constexpr int kAndersonStateInts = 8;      // per atom: ring head, length, steps taken | this step's head, length, use flag
+constexpr int kAndersonCoefDoubles = kAndersonMaxHistory;
+struct dfta_anderson {
+    int m = 0, warmup = 0;                 // pairs kept per atom, linear steps before the first accelerated one
+    DevBuf<double> ring;                   // [potential][slot < m][x, f][N]
+    DevBuf<double> slab;                   // [atom][chunk][kAndersonDots]: the chunks' partial dot products
+    DevBuf<double> gamma;                  // [atom][kAndersonCoefDoubles]
+    DevBuf<int> state;                     // [atom][kAndersonStateInts]
+};
+inline int dfta_anderson_chunks(int N) { return (N + kAndersonChunk - 1) / kAndersonChunk; }
+int dfta_anderson_create(dfta_ctx* ctx, const dfta_grid* g, int natoms, int nspin, int history, int warmup, dfta_anderson* an);
+// newDensity: the level search's Sum f Psi^2 of every potential (in), the output density g (out); density / dA / dB: the step's input
+// density (in), the mixed one (out); fin: per atom, finished (skipped)
+int dfta_launch_anderson_mix(dfta_ctx* ctx, const dfta_grid* g, dfta_anderson* an, int lsda, int natoms, double alpha, double oneMinusAlpha,
+                             double* newDensity, double* density, double* dA, double* dB, const int* fin);

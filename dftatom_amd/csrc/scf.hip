@@ -251,6 +251,8 @@ struct dfta_scf {
     int fallbacks_seen = 0;               // level-search fallbacks already reported in a step's statistics
     int levels_mode = DFTA_LEVELS_BATCHED;
     int steps_done = 0;
+    int mixing = DFTA_MIX_LINEAR;         // dfta_scf_options::mixing
+    dfta_anderson anderson;               // DFTA_MIX_ANDERSON: the atoms' history and the solve's scratch (mixing.hip); empty otherwise
     std::vector<int> spin_nlev[2];      // per atom number of levels per spin
     DevBuf<AtomState> d_atoms;
     DevBuf<double> d_Ne;                  // per atom: electrons, the multigrid's outer boundary U(Rmax)
@@ -399,7 +401,7 @@ int dfta_scf_create_config(dfta_ctx* ctx, const dfta_grid* g, int lsda, int nato
     DFTA_ENTER(ctx);
     DFTA_REQUIRE(ctx, natoms >= 1 && Z && alpha >= 0 && alpha <= 1, "scf arguments");
     DFTA_REQUIRE(ctx, !nlev || (cn && cl && cocc), "configuration: n, l and occ are needed with nlev");
-    dfta_scf_options opt = {(int)sizeof(dfta_scf_options), DFTA_INT_SIMPSON38, DFTA_XC_VWN, DFTA_AUFBAU_REFERENCE, -1, DFTA_SWEEPS_EXACT};
+    dfta_scf_options opt = {(int)sizeof(dfta_scf_options), DFTA_INT_SIMPSON38, DFTA_XC_VWN, DFTA_AUFBAU_REFERENCE, -1, DFTA_SWEEPS_EXACT, DFTA_MIX_LINEAR, 0, 0};
     if (options) {
         // the caller's struct may be shorter (an older header) or longer (a newer one) than this library's: read what both know
         const int sz = options->struct_size;
@@ -416,6 +418,9 @@ int dfta_scf_create_config(dfta_ctx* ctx, const dfta_grid* g, int lsda, int nato
     DFTA_REQUIRE(ctx, opt.aufbau == DFTA_AUFBAU_REFERENCE || opt.aufbau == DFTA_AUFBAU_TRANSITION_METALS, "aufbau");
     DFTA_REQUIRE(ctx, opt.sweep_mode == DFTA_SWEEPS_EXACT || opt.sweep_mode == DFTA_SWEEPS_TOLERANCE, "sweep mode");
     DFTA_REQUIRE(ctx, opt.sweep_mode == DFTA_SWEEPS_EXACT || dfta_scan_supported(g), "the tolerance mode of the sweeps needs a logarithmic grid of 12 .. 20 multigrid levels");
+    DFTA_REQUIRE(ctx, opt.mixing == DFTA_MIX_LINEAR || opt.mixing == DFTA_MIX_ANDERSON, "mixing (DFTA_MIX_LINEAR / DFTA_MIX_ANDERSON)");
+    DFTA_REQUIRE(ctx, opt.mix_history >= 0 && opt.mix_history <= kAndersonMaxHistory, "mix_history (1 .. 8; 0: the default, 4)");
+    DFTA_REQUIRE(ctx, opt.mix_warmup >= 0 && opt.mix_warmup <= 100, "mix_warmup (1 .. 100; 0: the default, 3)");
     dfta_scf* s = new dfta_scf();
     struct Guard { dfta_scf* s; ~Guard() { dfta_scf_destroy(s); } } guard{s};      // every error return below destroys what has been made
     s->solver.sweep_mode = opt.sweep_mode;
@@ -444,6 +449,11 @@ int dfta_scf_create_config(dfta_ctx* ctx, const dfta_grid* g, int lsda, int nato
     al(s->d_va, aN); al(s->d_vb, aN); al(s->d_eexc, aN); al(s->d_newDensity, aN * s->nspin); al(s->d_integrands, aN * 5);
     al(s->d_integrals, (size_t)natoms * 5); al(s->d_records, (size_t)natoms * DFTA_RECORD_DOUBLES);
     al(s->d_atoms, natoms); al(s->d_Ne, natoms); al(s->d_fin, natoms);
+    s->mixing = opt.mixing;
+    if (e == hipSuccess && s->mixing == DFTA_MIX_ANDERSON) {       // the history ring: 2 mix_history doubles per node and spin channel
+        rc = dfta_anderson_create(ctx, g, natoms, s->nspin, opt.mix_history ? opt.mix_history : 4, opt.mix_warmup ? opt.mix_warmup : 3, &s->anderson);
+        if (rc) return rc;
+    }
     if (e == hipSuccess) e = hipMemsetAsync(s->d_fin, 0, sizeof(int) * natoms, st);
     for (auto& ev : s->ev) if (e == hipSuccess) e = hipEventCreate(&ev.e);
     if (e == hipSuccess) e = hipMemcpyAsync(s->d_atoms, s->h_atoms.data(), sizeof(AtomState) * natoms, hipMemcpyHostToDevice, st);
@@ -631,9 +641,15 @@ int dfta_scf_step(dfta_scf* s, dfta_step_stats* stats)
                         jobs[k].cur_len[2], jobs[k].pred_len[0], jobs[k].pred_len[1], jobs[k].pred_len[2], jobs[k].n_count, jobs[k].n_zero);
         }
     }
-    hipLaunchKernelGGL(k_mix, grid, block, 0, st, s->lsda, N, s->alpha, 1. - s->alpha, g->d_fpr2, s->d_newDensity.p, s->d_density.p,
-                       s->d_dA.p, s->d_dB.p, s->d_fin.p);
-    DFTA_CHECK_LAUNCH(ctx);
+    if (s->mixing == DFTA_MIX_ANDERSON) {
+        rc = dfta_launch_anderson_mix(ctx, g, &s->anderson, s->lsda, natoms, s->alpha, 1. - s->alpha, s->d_newDensity.p, s->d_density.p, s->d_dA.p,
+                                      s->d_dB.p, s->d_fin.p);
+        if (rc) return rc;
+    } else {
+        hipLaunchKernelGGL(k_mix, grid, block, 0, st, s->lsda, N, s->alpha, 1. - s->alpha, g->d_fpr2, s->d_newDensity.p, s->d_density.p,
+                           s->d_dA.p, s->d_dB.p, s->d_fin.p);
+        DFTA_CHECK_LAUNCH(ctx);
+    }
     DFTA_HIP(ctx, hipEventRecord(s->ev[1], st));
     // live atoms of this step (finished ones are frozen, see above) and the solver of their size class
     std::vector<int> live_atoms;

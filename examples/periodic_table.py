@@ -7,6 +7,7 @@ costs nothing more (dfta_scf_step).  The fixed-size result records are gathered 
 
     python examples/periodic_table.py                       # one GPU
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 examples/periodic_table.py
+    python examples/periodic_table.py --mixing anderson     # Anderson density mixing: about half the SCF steps
     python examples/periodic_table.py --charge 1            # the cations X+ (Z > charge)
     python examples/periodic_table.py --ionization          # IE = E(X+) - E(X): neutral atom and cation of every Z in ONE batch per rank
 """
@@ -37,6 +38,8 @@ def main():
     ap.add_argument("--sweeps", choices=("exact", "tolerance"), default="exact", help="tolerance: the scan sweeps (DFTA_SWEEPS_TOLERANCE)")
     ap.add_argument("--poisson", choices=("exact", "tolerance", "adaptive"), default="exact",
                     help="tolerance: the multigrid's tolerance mode; adaptive: that, and the V-cycles stop at the round-off floor")
+    ap.add_argument("--mixing", choices=("linear", "anderson"), default="linear",
+                    help="anderson: Anderson density mixing (DFTA_MIX_ANDERSON), about half the SCF steps per atom")
     ap.add_argument("--emulate-ranks", type=int, default=0,
                     help="one GPU, no launcher: run each of the N shards of an N-rank sweep alone, one after the other, and report the "
                          "per-shard wall times; their maximum PREDICTS the N-GPU wall time (shards never interact; the only collective "
@@ -73,7 +76,8 @@ def main():
     cost = sweep.atom_cost if args.partition == "work" else None
     modes = dict(sweep_mode=D.SWEEPS_TOLERANCE if args.sweeps == "tolerance" else D.SWEEPS_EXACT,
                  poisson_mode={"tolerance": D.POISSON_TOLERANCE, "adaptive": D.POISSON_ADAPTIVE}.get(args.poisson, D.POISSON_EXACT),
-                 functional={"vwn": D.XC_VWN, "pw92": D.XC_PW92, "pbe": D.XC_PBE}[args.xc])
+                 functional={"vwn": D.XC_VWN, "pw92": D.XC_PW92, "pbe": D.XC_PBE}[args.xc],
+                 mixing=D.MIX_ANDERSON if args.mixing == "anderson" else D.MIX_LINEAR)
     model = "tolerance" if args.sweeps == "tolerance" else "exact"
     if cost is None and model != "exact":
         cost_model = model

