@@ -145,6 +145,10 @@ SIGNATURES = {
     "dfta_scf_create_config": (C.c_int, [vp, vp, C.c_int, C.c_int, c_ip, c_ip, c_ip, c_ip, c_dp, C.c_double, C.c_int, C.c_int, vp,
                                          C.POINTER(vp)]),
     "dfta_scf_get_occupations": (C.c_int, [vp, C.c_int, C.c_int, c_dp]),
+    "dfta_mixer_create": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]),
+    "dfta_mixer_step": (C.c_int, [vp, C.c_double, c_dp, c_dp, c_dp, c_dp, c_ip]),
+    "dfta_mixer_get": (C.c_int, [vp, C.c_int, c_ip, c_dp, c_dp, c_dp]),
+    "dfta_mixer_destroy": (None, [vp]),
 }
 
 _lib = None
@@ -547,6 +551,43 @@ def xc_radial(ctx, grid, functional, na, nb=None):
     va, vb = np.zeros_like(na), np.zeros_like(na)
     ctx.check(ctx.lib.dfta_xc_radial(ctx.h, grid.h, int(functional), natoms, _dp(na), _dp(nb), _dp(res), _dp(va), _dp(vb), _dp(eexc)))
     return res.reshape(shape), va.reshape(shape), vb.reshape(shape), eexc.reshape(shape)
+
+
+class Mixer:
+    """The SCF's density-mixing stage on its own (dfta_mixer): the launches dfta_scf_step issues for `mixing`, on the caller's arrays."""
+
+    def __init__(self, ctx, grid, lsda=False, natoms=1, mixing=MIX_ANDERSON, history=4, warmup=3):
+        self.ctx, self.grid, self.lsda, self.natoms, self.mixing, self.history = ctx, grid, bool(lsda), int(natoms), int(mixing), int(history)
+        self.nspin = 2 if lsda else 1
+        h = vp()
+        ctx.check(ctx.lib.dfta_mixer_create(ctx.h, grid.h, int(self.lsda), self.natoms, self.mixing, self.history, int(warmup), C.byref(h)))
+        self.h = h
+
+    def step(self, alpha, acc, density, dA=None, dB=None, fin=None):
+        """acc: Sum f Psi^2, (natoms, nspin, N); density, dA, dB: (natoms, N), the step's input; fin: (natoms,) frozen flags.
+        Returns copies: (g as stored over acc, density, dA, dB) -- LDA: dA, dB are None."""
+        n, N = self.natoms, self.grid.N
+        acc = _f64(acc).reshape(n, self.nspin, N).copy()
+        density = _f64(density).reshape(n, N).copy()
+        fin = _i32(np.zeros(n) if fin is None else fin).reshape(n)
+        if self.lsda:
+            dA, dB = _f64(dA).reshape(n, N).copy(), _f64(dB).reshape(n, N).copy()
+        self.ctx.check(self.ctx.lib.dfta_mixer_step(self.h, float(alpha), _dp(acc), _dp(density), _dp(dA) if self.lsda else None,
+                                                    _dp(dB) if self.lsda else None, _ip(fin)))
+        return acc, density, (dA if self.lsda else None), (dB if self.lsda else None)
+
+    def get(self, atom):
+        """MIX_ANDERSON: dict(state (8 ints), gamma (8), slab (chunks, 44), ring (nspin, history, 2, N)) of one atom after the last step"""
+        N = self.grid.N
+        state, gamma = np.zeros(8, np.int32), np.zeros(8)
+        slab, ring = np.zeros(((N + 1023) // 1024, 44)), np.zeros((self.nspin, self.history, 2, N))
+        self.ctx.check(self.ctx.lib.dfta_mixer_get(self.h, int(atom), _ip(state), _dp(gamma), _dp(slab), _dp(ring)))
+        return {"state": state, "gamma": gamma, "slab": slab, "ring": ring}
+
+    def close(self):
+        if self.h:
+            self.ctx.lib.dfta_mixer_destroy(self.h)
+            self.h = None
 
 
 class Scf:

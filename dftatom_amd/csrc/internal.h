@@ -110,3 +110,6 @@ int dfta_anderson_create(dfta_ctx* ctx, const dfta_grid* g, int natoms, int nspi
 // density (in), the mixed one (out); fin: per atom, finished (skipped)
 int dfta_launch_anderson_mix(dfta_ctx* ctx, const dfta_grid* g, dfta_anderson* an, int lsda, int natoms, double alpha, double oneMinusAlpha,
                              double* newDensity, double* density, double* dA, double* dB, const int* fin);
+// scf.hip: the k_mix launch (DFTA_MIX_LINEAR), same arguments
+int dfta_launch_linear_mix(dfta_ctx* ctx, const dfta_grid* g, int lsda, int natoms, double alpha, double oneMinusAlpha, double* newDensity,
+                           double* density, double* dA, double* dB, const int* fin);

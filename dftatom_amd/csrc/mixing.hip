@@ -251,3 +251,105 @@ int dfta_launch_anderson_mix(dfta_ctx* ctx, const dfta_grid* g, dfta_anderson* a
     DFTA_CHECK_LAUNCH(ctx);
     return DFTA_OK;
 }
+
+// ---- the mixing stage on its own (include/dftatom_hip.h: dfta_mixer) --------------------------------------------------------------
+// No second implementation: a step uploads the caller's arrays into buffers laid out as dfta_scf's and calls the launch function
+// dfta_scf_step calls for the same `mixing`.
+struct dfta_mixer {
+    dfta_ctx* ctx = nullptr;
+    const dfta_grid* g = nullptr;
+    int lsda = 0, natoms = 0, nspin = 1, mixing = DFTA_MIX_LINEAR;
+    dfta_anderson anderson;
+    DevBuf<double> newDensity, density, dA, dB;
+    DevBuf<int> fin;
+};
+
+extern "C" {
+
+void dfta_mixer_destroy(dfta_mixer* mx) { delete mx; }
+
+int dfta_mixer_create(dfta_ctx* ctx, const dfta_grid* g, int lsda, int natoms, int mixing, int history, int warmup, dfta_mixer** out)
+{
+    if (!ctx || !g || !out) return DFTA_ERR_INVALID;
+    DFTA_ENTER(ctx);
+    DFTA_REQUIRE(ctx, natoms >= 1 && natoms <= 65535, "dfta_mixer_create: natoms");
+    DFTA_REQUIRE(ctx, mixing == DFTA_MIX_LINEAR || mixing == DFTA_MIX_ANDERSON, "mixing (DFTA_MIX_LINEAR / DFTA_MIX_ANDERSON)");
+    dfta_mixer* mx = new dfta_mixer();
+    mx->ctx = ctx;
+    mx->g = g;
+    mx->lsda = lsda ? 1 : 0;
+    mx->natoms = natoms;
+    mx->nspin = lsda ? 2 : 1;
+    mx->mixing = mixing;
+    const size_t sz = (size_t)natoms * g->N;
+    hipError_t e = mx->newDensity.alloc(sz * mx->nspin);
+    if (e == hipSuccess) e = mx->density.alloc(sz);
+    if (e == hipSuccess && lsda) e = mx->dA.alloc(sz);
+    if (e == hipSuccess && lsda) e = mx->dB.alloc(sz);
+    if (e == hipSuccess) e = mx->fin.alloc(natoms);
+    int rc = DFTA_OK;
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        snprintf(ctx->err, sizeof(ctx->err), "dfta_mixer_create: %s", hipGetErrorString(e));
+        rc = e == hipErrorOutOfMemory ? DFTA_ERR_NOMEM : DFTA_ERR_HIP;
+    } else if (mixing == DFTA_MIX_ANDERSON) {
+        rc = dfta_anderson_create(ctx, g, natoms, mx->nspin, history, warmup, &mx->anderson);
+        if (rc == DFTA_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = DFTA_ERR_HIP;
+    }
+    if (rc) { delete mx; return rc; }
+    *out = mx;
+    return DFTA_OK;
+}
+
+int dfta_mixer_step(dfta_mixer* mx, double alpha, double* acc, double* density, double* dA, double* dB, const int* fin)
+{
+    if (!mx) return DFTA_ERR_INVALID;
+    dfta_ctx* ctx = mx->ctx;
+    DFTA_ENTER(ctx);
+    DFTA_REQUIRE(ctx, acc && density && fin && (!mx->lsda || (dA && dB)), "dfta_mixer_step arguments");
+    hipStream_t st = ctx->stream;
+    const size_t row = sizeof(double) * (size_t)mx->natoms * mx->g->N;
+    DFTA_HIP(ctx, hipMemcpyAsync(mx->newDensity.p, acc, row * mx->nspin, hipMemcpyHostToDevice, st));
+    DFTA_HIP(ctx, hipMemcpyAsync(mx->density.p, density, row, hipMemcpyHostToDevice, st));
+    if (mx->lsda) {
+        DFTA_HIP(ctx, hipMemcpyAsync(mx->dA.p, dA, row, hipMemcpyHostToDevice, st));
+        DFTA_HIP(ctx, hipMemcpyAsync(mx->dB.p, dB, row, hipMemcpyHostToDevice, st));
+    }
+    DFTA_HIP(ctx, hipMemcpyAsync(mx->fin.p, fin, sizeof(int) * mx->natoms, hipMemcpyHostToDevice, st));
+    int rc;
+    if (mx->mixing == DFTA_MIX_ANDERSON)
+        rc = dfta_launch_anderson_mix(ctx, mx->g, &mx->anderson, mx->lsda, mx->natoms, alpha, 1. - alpha, mx->newDensity.p, mx->density.p, mx->dA.p,
+                                      mx->dB.p, mx->fin.p);
+    else
+        rc = dfta_launch_linear_mix(ctx, mx->g, mx->lsda, mx->natoms, alpha, 1. - alpha, mx->newDensity.p, mx->density.p, mx->dA.p, mx->dB.p,
+                                    mx->fin.p);
+    if (rc) return rc;
+    DFTA_HIP(ctx, hipMemcpyAsync(acc, mx->newDensity.p, row * mx->nspin, hipMemcpyDeviceToHost, st));
+    DFTA_HIP(ctx, hipMemcpyAsync(density, mx->density.p, row, hipMemcpyDeviceToHost, st));
+    if (mx->lsda) {
+        DFTA_HIP(ctx, hipMemcpyAsync(dA, mx->dA.p, row, hipMemcpyDeviceToHost, st));
+        DFTA_HIP(ctx, hipMemcpyAsync(dB, mx->dB.p, row, hipMemcpyDeviceToHost, st));
+    }
+    DFTA_HIP(ctx, hipStreamSynchronize(st));
+    return DFTA_OK;
+}
+
+int dfta_mixer_get(dfta_mixer* mx, int atom, int* state, double* gamma, double* slab, double* ring)
+{
+    if (!mx) return DFTA_ERR_INVALID;
+    dfta_ctx* ctx = mx->ctx;
+    DFTA_ENTER(ctx);
+    DFTA_REQUIRE(ctx, mx->mixing == DFTA_MIX_ANDERSON, "dfta_mixer_get: a DFTA_MIX_LINEAR mixer keeps no history");
+    DFTA_REQUIRE(ctx, atom >= 0 && atom < mx->natoms, "dfta_mixer_get: atom");
+    hipStream_t st = ctx->stream;
+    const dfta_anderson& an = mx->anderson;
+    const size_t a = atom, nslab = (size_t)dfta_anderson_chunks(mx->g->N) * kAndersonDots, nring = (size_t)mx->nspin * an.m * 2 * mx->g->N;
+    if (state) DFTA_HIP(ctx, hipMemcpyAsync(state, an.state.p + a * kAndersonStateInts, sizeof(int) * kAndersonStateInts, hipMemcpyDeviceToHost, st));
+    if (gamma) DFTA_HIP(ctx, hipMemcpyAsync(gamma, an.gamma.p + a * kAndersonCoefDoubles, sizeof(double) * kAndersonCoefDoubles, hipMemcpyDeviceToHost, st));
+    if (slab) DFTA_HIP(ctx, hipMemcpyAsync(slab, an.slab.p + a * nslab, sizeof(double) * nslab, hipMemcpyDeviceToHost, st));
+    if (ring) DFTA_HIP(ctx, hipMemcpyAsync(ring, an.ring.p + a * nring, sizeof(double) * nring, hipMemcpyDeviceToHost, st));
+    DFTA_HIP(ctx, hipStreamSynchronize(st));
+    return DFTA_OK;
+}
+
+}  // extern "C"

@@ -203,6 +203,17 @@ __global__ void k_energies(AtomState* __restrict__ atoms, int natoms, const dfta
 
 }  // namespace
 
+// the linear mix of a step as its one launch: dfta_scf_step's, and dfta_mixer_step's (mixing.hip) with DFTA_MIX_LINEAR
+int dfta_launch_linear_mix(dfta_ctx* ctx, const dfta_grid* g, int lsda, int natoms, double alpha, double oneMinusAlpha, double* newDensity,
+                           double* density, double* dA, double* dB, const int* fin)
+{
+    const int N = g->N;
+    hipLaunchKernelGGL(k_mix, dim3(std::min(64, (N + 255) / 256), natoms), dim3(256), 0, ctx->stream, lsda, N, alpha, oneMinusAlpha, g->d_fpr2,
+                       newDensity, density, dA, dB, fin);
+    DFTA_CHECK_LAUNCH(ctx);
+    return DFTA_OK;
+}
+
 // rows idx[y] of src -> row y of dst, and back (the live atoms of a batch, see dfta_scf::live_solver)
 __global__ void k_gather_rows(const double* __restrict__ src, const int* __restrict__ idx, int N, double* __restrict__ dst)
 {
@@ -646,9 +657,9 @@ int dfta_scf_step(dfta_scf* s, dfta_step_stats* stats)
                                       s->d_dB.p, s->d_fin.p);
         if (rc) return rc;
     } else {
-        hipLaunchKernelGGL(k_mix, grid, block, 0, st, s->lsda, N, s->alpha, 1. - s->alpha, g->d_fpr2, s->d_newDensity.p, s->d_density.p,
-                           s->d_dA.p, s->d_dB.p, s->d_fin.p);
-        DFTA_CHECK_LAUNCH(ctx);
+        rc = dfta_launch_linear_mix(ctx, g, s->lsda, natoms, s->alpha, 1. - s->alpha, s->d_newDensity.p, s->d_density.p, s->d_dA.p, s->d_dB.p,
+                                    s->d_fin.p);
+        if (rc) return rc;
     }
     DFTA_HIP(ctx, hipEventRecord(s->ev[1], st));
     // live atoms of this step (finished ones are frozen, see above) and the solver of their size class

@@ -352,6 +352,19 @@ int  dfta_scf_create(dfta_ctx* ctx, const dfta_grid* g, int lsda, int natoms, co
  * Costs 2 mix_history doubles per node and spin channel of device memory.  A typical atom finishes in 17-21 steps instead of 28-36. */
 #define DFTA_MIX_LINEAR   0
 #define DFTA_MIX_ANDERSON 1
+/* The mixing launches on their own (tests and tools; dfta_scf_step does not go through this).  A dfta_mixer owns what the SCF owns for its
+ * mixing stage -- device copies of newDensity (natoms x nspin x N), density, dA, dB (natoms x N) and, with DFTA_MIX_ANDERSON, the atoms'
+ * history -- and one dfta_mixer_step issues exactly the launches dfta_scf_step issues at that stage for the same `mixing`.  Host pointers.
+ * step: acc is Sum f Psi^2 of every potential (in) and the output density g as the kernels store it (out); density / dA / dB are the
+ * step's input density (in; LDA: dA = dB = NULL) and the mixed one (out); fin: per atom, != 0: frozen.  The caller supplies the input
+ * density of every step.  get, Anderson only, any pointer may be NULL: state[8] = ring head, length, steps taken | the last step's head,
+ * pairs used, use flag, 0, 0; gamma[8]; slab[chunks of 1024 nodes][44]: the chunks' shares of A's upper triangle row by row (the newest 8
+ * pairs: 36), then b (8), of the last step; ring[nspin][history][2][N]: the (x, f) pairs by slot. */
+typedef struct dfta_mixer dfta_mixer;
+int  dfta_mixer_create(dfta_ctx* ctx, const dfta_grid* g, int lsda, int natoms, int mixing, int history, int warmup, dfta_mixer** out);
+int  dfta_mixer_step(dfta_mixer* mx, double alpha, double* acc, double* density, double* dA, double* dB, const int* fin);
+int  dfta_mixer_get(dfta_mixer* mx, int atom, int* state, double* gamma, double* slab, double* ring);
+void dfta_mixer_destroy(dfta_mixer* mx);
 typedef struct dfta_scf_options {
     int struct_size;  /* sizeof(dfta_scf_options) of the CALLER's header: members beyond it keep their defaults, a value that is no valid
                          size of this struct (0, or what an older header had in this place) is rejected with DFTA_ERR_INVALID          */

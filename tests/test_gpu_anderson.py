@@ -10,7 +10,7 @@ count; its final Etotal is within 1e-9 relative of the GPU's linear one.  "Eigen
 taken against AndersonRef at the SAME step number (the reference is stepped two steps past its own finish for that): the two
 mixings stop at different distances from the fixed point, so their final eigenvalues are not comparable at 1e-8 Ha.
 
-Every test prints what it observed.
+Every test prints what it observed.  The kernels themselves, stage by stage against an extended reference: tests/test_gpu_mixing_kernels.py.
 """
 import ctypes as C
 import functools
