@@ -138,34 +138,6 @@ struct dfta_range {
     dfta_range& operator=(const dfta_range&) = delete;
 };
 
-// Device-resident tables of one logarithmic grid r_i = Rp (exp(i delta) - 1), i = 0..N-1.
-// All exp() values are produced on the host with libm in the reference's expression order
-// (Numerov.h:79-101,183; DFTAtom.cpp:42,47,334,439-442; PoissonSolver.h:66-74) and uploaded once.
-struct dfta_grid {
-    dfta_ctx* ctx = nullptr;
-    int levels = 0;
-    int N = 0;
-    double delta = 0, Rmax = 0, Rp = 0, twodelta = 0, Rp2delta2 = 0, delta2p4 = 0;
-    // uniform grid r_i = i h (NumerovFunctionRegularGrid, Numerov.h:16-70): delta = 0, h = Rmax / (N - 1); the tables
-    // keep their meaning with exp(...) == 1 (d_eh, d_cnst are all ones), so the SCF kernels need no second flavour
-    int uniform = 0;
-    double h = 1, h2 = 1, h2p12 = 1. / 12.;   // step of the Numerov recurrence (1 on the logarithmic grid, Numerov.h:285-287)
-    double far_arg_threshold = 0;   // exp(a) < 1e-200  <=>  a < far_arg_threshold (host libm, monotone)
-    double zero1[4] = {0, 0, 0, 0};  // GetBoundaryValueZero(1, l), l = 0..3 (Numerov.h:110-116)
-    // host copies
-    std::vector<double> h_r, h_e1, h_e2, h_eh;
-    // device tables (N doubles each unless noted)
-    double* d_r = nullptr;      // r_i
-    double* d_e1 = nullptr;     // exp(i delta)
-    double* d_e2 = nullptr;     // exp(i 2delta)
-    double* d_eh = nullptr;     // exp(i delta / 2)
-    double* d_cl = nullptr;     // 4*N: l(l+1.)/(r_i r_i)*0.5 for l = 0..3 (row 0 is all zeros)
-    double* d_cnst = nullptr;   // (Rp delta) exp(delta i)            (DFTAtom.cpp:47,442)
-    double* d_psrc = nullptr;   // (4 pi Rp^2 delta^2) exp(i 2delta)  (PoissonSolver.h:66-74)
-    double* d_fpr2 = nullptr;   // (4 pi r_i) r_i                     (DFTAtom.cpp:340)
-    double* d_rsrc = nullptr;   // the r factor of the Poisson source: d_r, or FillR's (Rmax i) / (N-1) on a uniform grid (PoissonSolver.cpp:200-210)
-};
-
 // RAII device buffer: call-scoped scratch and the solvers' members (passes where a T* is expected; null while empty)
 template <typename T>
 struct DevBuf {
@@ -201,6 +173,35 @@ struct DevStream {
     DevStream& operator=(const DevStream&) = delete;
     ~DevStream() { if (s) (void)hipStreamDestroy(s); }
     operator hipStream_t() const { return s; }
+};
+
+// Device-resident tables of one logarithmic grid r_i = Rp (exp(i delta) - 1), i = 0..N-1.
+// All exp() values are produced on the host with libm in the reference's expression order
+// (Numerov.h:79-101,183; DFTAtom.cpp:42,47,334,439-442; PoissonSolver.h:66-74) and uploaded once.
+struct dfta_grid {
+    dfta_ctx* ctx = nullptr;
+    int levels = 0;
+    int N = 0;
+    double delta = 0, Rmax = 0, Rp = 0, twodelta = 0, Rp2delta2 = 0, delta2p4 = 0;
+    // uniform grid r_i = i h (NumerovFunctionRegularGrid, Numerov.h:16-70): delta = 0, h = Rmax / (N - 1); the tables
+    // keep their meaning with exp(...) == 1 (d_eh, d_cnst are all ones), so the SCF kernels need no second flavour
+    int uniform = 0;
+    double h = 1, h2 = 1, h2p12 = 1. / 12.;   // step of the Numerov recurrence (1 on the logarithmic grid, Numerov.h:285-287)
+    double far_arg_threshold = 0;   // exp(a) < 1e-200  <=>  a < far_arg_threshold (host libm, monotone)
+    double zero1[4] = {0, 0, 0, 0};  // GetBoundaryValueZero(1, l), l = 0..3 (Numerov.h:110-116)
+    // host copies
+    std::vector<double> h_r, h_e1, h_e2, h_eh;
+    // device tables (N doubles each unless noted)
+    DevBuf<double> d_r;         // r_i
+    DevBuf<double> d_e1;        // exp(i delta)
+    DevBuf<double> d_e2;        // exp(i 2delta)
+    DevBuf<double> d_eh;        // exp(i delta / 2)
+    DevBuf<double> d_cl;        // 4*N: l(l+1.)/(r_i r_i)*0.5 for l = 0..3 (row 0 is all zeros)
+    DevBuf<double> d_cnst;      // (Rp delta) exp(delta i)            (DFTAtom.cpp:47,442)
+    DevBuf<double> d_psrc;      // (4 pi Rp^2 delta^2) exp(i 2delta)  (PoissonSolver.h:66-74)
+    DevBuf<double> d_fpr2;      // (4 pi r_i) r_i                     (DFTAtom.cpp:340)
+    DevBuf<double> d_rsrc_own;  // uniform grid: FillR's (Rmax i) / (N-1) (PoissonSolver.cpp:200-210)
+    const double* d_rsrc = nullptr;   // the r factor of the Poisson source: d_r, or d_rsrc_own on a uniform grid
 };
 
 // A pointer that reaches a non-inlined device function has no known address space: the compiler emits FLAT loads and stores, which count

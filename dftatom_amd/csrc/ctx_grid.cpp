@@ -12,6 +12,7 @@
 #include <cstdio>
 #include <cstring>
 #include <string>
+#include <memory>
 #include <vector>
 
 #include "common.h"
@@ -117,12 +118,29 @@ static double far_threshold()
     return unkey(hi);
 }
 
+// the grid's device tables: allocated and filled in the order given
+struct Upload { DevBuf<double>* d; const double* h; size_t n; };
+static int upload_tables(dfta_ctx* ctx, const Upload* ups, size_t count)
+{
+    for (size_t i = 0; i < count; ++i) {
+        hipError_t e = ups[i].d->alloc(ups[i].n);
+        if (e == hipSuccess) e = hipMemcpyAsync(ups[i].d->p, ups[i].h, ups[i].n * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
+        if (e != hipSuccess) {
+            snprintf(ctx->err, sizeof(ctx->err), "grid upload: %s", hipGetErrorString(e));
+            return DFTA_ERR_HIP;
+        }
+    }
+    DFTA_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return DFTA_OK;
+}
+
 int dfta_grid_create(dfta_ctx* ctx, int mg_levels, double delta, double Rmax, dfta_grid** out)
 {
     if (!ctx || !out) return DFTA_ERR_INVALID;
     DFTA_ENTER(ctx);
     DFTA_REQUIRE(ctx, mg_levels >= 3 && mg_levels <= 24 && delta > 0 && Rmax > 0, "grid parameters");
-    dfta_grid* g = new dfta_grid();
+    std::unique_ptr<dfta_grid> owner(new dfta_grid());
+    dfta_grid* g = owner.get();
     g->ctx = ctx;
     g->levels = mg_levels;
     const int N = dfta_num_nodes(mg_levels);
@@ -158,22 +176,13 @@ int dfta_grid_create(dfta_ctx* ctx, int mg_levels, double delta, double Rmax, df
     for (unsigned l = 0; l < 4; ++l)   // Numerov.h:110-116 at position = 1
         g->zero1[l] = pow(r[1], static_cast<double>(l) + 1) * exp(-1.0 * delta * 0.5);
 
-    struct Up { double** d; const double* h; size_t n; } ups[] = {
+    const Upload ups[] = {
         {&g->d_r, r.data(), (size_t)N}, {&g->d_e1, e1.data(), (size_t)N}, {&g->d_e2, e2.data(), (size_t)N},
         {&g->d_eh, eh.data(), (size_t)N}, {&g->d_cl, cl.data(), (size_t)4 * N}, {&g->d_cnst, cnst.data(), (size_t)N},
         {&g->d_psrc, psrc.data(), (size_t)N}, {&g->d_fpr2, fpr2.data(), (size_t)N}};
-    for (auto& u : ups) {
-        hipError_t e = hipMalloc(reinterpret_cast<void**>(u.d), u.n * sizeof(double));
-        if (e == hipSuccess) e = hipMemcpyAsync(*u.d, u.h, u.n * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
-        if (e != hipSuccess) {
-            snprintf(ctx->err, sizeof(ctx->err), "grid upload: %s", hipGetErrorString(e));
-            dfta_grid_destroy(g);
-            return DFTA_ERR_HIP;
-        }
-    }
-    DFTA_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (int rc = upload_tables(ctx, ups, sizeof(ups) / sizeof(ups[0]))) return rc;
     g->d_rsrc = g->d_r;
-    *out = g;
+    *out = owner.release();
     return DFTA_OK;
 }
 
@@ -183,7 +192,8 @@ int dfta_grid_create_uniform(dfta_ctx* ctx, int mg_levels, double Rmax, dfta_gri
     if (!ctx || !out) return DFTA_ERR_INVALID;
     DFTA_ENTER(ctx);
     DFTA_REQUIRE(ctx, mg_levels >= 3 && mg_levels <= 24 && Rmax > 0, "grid parameters");
-    dfta_grid* g = new dfta_grid();
+    std::unique_ptr<dfta_grid> owner(new dfta_grid());
+    dfta_grid* g = owner.get();
     g->ctx = ctx;
     g->levels = mg_levels;
     const int N = dfta_num_nodes(mg_levels);
@@ -218,30 +228,19 @@ int dfta_grid_create_uniform(dfta_ctx* ctx, int mg_levels, double Rmax, dfta_gri
                 cl[static_cast<size_t>(l) * N + i] = l * (l + 1.) / (r[i] * r[i]) * 0.5;   // Numerov.h:23
     }
     for (unsigned l = 0; l < 4; ++l) g->zero1[l] = pow(g->h, static_cast<double>(l) + 1.);   // Numerov.h:38-41 at position = h (sweeps keep h; the match solve re-derives it)
-    struct Up { double** d; const double* h; size_t n; } ups[] = {
+    const Upload ups[] = {
         {&g->d_r, r.data(), (size_t)N}, {&g->d_e1, e1.data(), (size_t)N}, {&g->d_e2, e2.data(), (size_t)N},
         {&g->d_eh, eh.data(), (size_t)N}, {&g->d_cl, cl.data(), (size_t)4 * N}, {&g->d_cnst, cnst.data(), (size_t)N},
-        {&g->d_psrc, psrc.data(), (size_t)N}, {&g->d_fpr2, fpr2.data(), (size_t)N}, {&g->d_rsrc, rsrc.data(), (size_t)N}};
-    for (auto& u : ups) {
-        hipError_t e = hipMalloc(reinterpret_cast<void**>(u.d), u.n * sizeof(double));
-        if (e == hipSuccess) e = hipMemcpyAsync(*u.d, u.h, u.n * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
-        if (e != hipSuccess) {
-            snprintf(ctx->err, sizeof(ctx->err), "grid upload: %s", hipGetErrorString(e));
-            dfta_grid_destroy(g);
-            return DFTA_ERR_HIP;
-        }
-    }
-    DFTA_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    *out = g;
+        {&g->d_psrc, psrc.data(), (size_t)N}, {&g->d_fpr2, fpr2.data(), (size_t)N}, {&g->d_rsrc_own, rsrc.data(), (size_t)N}};
+    if (int rc = upload_tables(ctx, ups, sizeof(ups) / sizeof(ups[0]))) return rc;
+    g->d_rsrc = g->d_rsrc_own;
+    *out = owner.release();
     return DFTA_OK;
 }
 
 void dfta_grid_destroy(dfta_grid* g)
 {
     if (!g) return;
-    if (g->d_rsrc == g->d_r) g->d_rsrc = nullptr;
-    double* ptrs[] = {g->d_r, g->d_e1, g->d_e2, g->d_eh, g->d_cl, g->d_cnst, g->d_psrc, g->d_fpr2, g->d_rsrc};
-    for (double* p : ptrs) if (p) (void)hipFree(p);
     delete g;
 }
 

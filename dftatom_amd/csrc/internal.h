@@ -34,12 +34,12 @@ int dfta_launch_match(dfta_ctx* ctx, const dfta_grid* g, int ntrials, const doub
 // persist.inc (compiled with numerov.hip): the exact level search of up to 64 levels on the device, every level at its own pace
 namespace dfta { struct Job; }
 struct dfta_persist_buffers {
-    void* d_ctl = nullptr;         // control block, mailboxes, per-level workgroup lists, trace
+    DevBuf<unsigned char> d_ctl;   // control block, mailboxes, per-level workgroup lists, trace
     size_t ctl_bytes = 0;
-    double *E = nullptr, *us = nullptr, *us1 = nullptr, *u0 = nullptr, *phi = nullptr;      // trial arrays: nlive_cap x tmax
-    int *limit = nullptr, *start = nullptr, *count = nullptr, *istop = nullptr, *trip = nullptr;
-    double *candP = nullptr, *candQ = nullptr;     // per workgroup: wavefunction + scratch of a speculative match (null: none)
-    int* blk = nullptr;            // per workgroup: table slot, first trial, trial count of its running block
+    DevBuf<double> E, us, us1, u0, phi;            // trial arrays: nlive_cap x tmax
+    DevBuf<int> limit, start, count, istop, trip;
+    DevBuf<double> candP, candQ;   // per workgroup: wavefunction + scratch of a speculative match (null: none)
+    DevBuf<int> blk;               // per workgroup: table slot, first trial, trial count of its running block
     int nblocks = 0, tmax = 0, nlive_cap = 0, trace_cap = 0;
     // $DFTA_DEBUG knobs, read when the buffers are made (as every other knob of a solver)
     int fault_block = -1;          // FAULT_PERSIST_WORKER: this workgroup drops its first block (tests)
@@ -48,9 +48,17 @@ struct dfta_persist_buffers {
     bool equal_shares = false;     // LEVELS_PERSIST_EQUAL: node-less levels keep their whole share
     bool want_trace = false;       // LEVELS_PERSIST_TRACE
     std::vector<unsigned char> h_stage;
+    void reset()                   // frees the buffers; sizes and knobs as constructed
+    {
+        for (DevBuf<double>* b : {&E, &us, &us1, &u0, &phi, &candP, &candQ}) b->reset();
+        for (DevBuf<int>* b : {&limit, &start, &count, &istop, &trip, &blk}) b->reset();
+        d_ctl.reset();
+        ctl_bytes = 0; nblocks = tmax = nlive_cap = trace_cap = 0;
+        fault_block = -1; timeout_ms = 0; plain_launch = equal_shares = want_trace = false;
+        h_stage.clear();
+    }
 };
-int dfta_persist_create(dfta_ctx* ctx, const dfta_grid* g, int nlive_cap, dfta_persist_buffers* pb);
-void dfta_persist_destroy(dfta_persist_buffers* pb);
+int dfta_persist_create(dfta_ctx* ctx, const dfta_grid* g, int nlive_cap, dfta_persist_buffers* pb);     // (re)creates: frees what pb held
 int dfta_launch_levels_persist(dfta_ctx* ctx, const dfta_grid* g, dfta_persist_buffers* pb, dfta::Job* d_jobs, const int* live, int nlive,
                                const double2* d_tab, const double2* d_bounds, double* d_Psi, double* d_Q, int* d_jstart_keep,
                                unsigned long long* d_counters, bool stats, int nopredict, int integ_rule, const double* tuning, int fixed_point,
@@ -66,18 +74,17 @@ int dfta_launch_levels_own(dfta_ctx* ctx, const dfta_grid* g, dfta::Job* d_jobs,
 // scan.hip: the tolerance mode of the sweeps (transfer-matrix scan: one workgroup per trial)
 struct dfta_scan_tables {
     double* tabv = nullptr;    // nslots * N: veff = V + c_l per slot, lane-interleaved (row i = t C + k at k 512 + t, row N-1 at N-1)
-    double2* mm = nullptr;     // nslots * 512: {min, max} of veff over a lane's rows
-    double* Atop = nullptr;    // 513: A = 2 Rp^2 delta^2 exp(2 i delta) of every lane's top row (and of row N-1)
+    DevBuf<double2> mm;        // nslots * 512: {min, max} of veff over a lane's rows
+    DevBuf<double> Atop;       // 513: A = 2 Rp^2 delta^2 exp(2 i delta) of every lane's top row (and of row N-1)
     double* T = nullptr;       // C: exp(-2 delta (C-1-k))
     // tabv and T point kScanPadRows rows / 8 entries INTO their allocations: the row loops issue the loads of the next batches
     // unconditionally (rows below row 0 of slot 0, entries below T[0]: read, never used) -- no clamps, no branches in the loops
-    double* tabv_alloc = nullptr;
-    double* T_alloc = nullptr;
+    DevBuf<double> tabv_alloc, T_alloc;
     int nslots = 0;
+    void reset() { tabv_alloc.reset(); T_alloc.reset(); mm.reset(); Atop.reset(); tabv = T = nullptr; nslots = 0; }
 };
 int dfta_scan_supported(const dfta_grid* g);
-int dfta_scan_tables_create(dfta_ctx* ctx, const dfta_grid* g, int nslots, dfta_scan_tables* tb);
-void dfta_scan_tables_destroy(dfta_scan_tables* tb);
+int dfta_scan_tables_create(dfta_ctx* ctx, const dfta_grid* g, int nslots, dfta_scan_tables* tb);     // tb: empty (as constructed)
 int dfta_launch_scan_build_tab(dfta_ctx* ctx, const dfta_grid* g, const dfta_scan_tables& tb, const double* dV, const int* d_slot_v, const int* d_slot_l);
 int dfta_launch_scan_sweeps(dfta_ctx* ctx, const dfta_grid* g, int kind, int ntrials, const dfta_scan_tables& tb, const int* d_trial_slot,
                             const double* dE, const int* dLimit, int* dCount, double* dU0, int* dStart, int* dTrip, int* dBad);

@@ -186,10 +186,9 @@ struct LevelSolver {
     double hist_kA = 0.2, hist_kB = 4.0;
     std::vector<unsigned long long> persist_trace;          // $DFTA_DEBUG LEVELS_PERSIST_TRACE: 4 words per closed round of the last run
 
-    LevelSolver() = default;
+    LevelSolver() = default;    // the device buffers, the stream, the events, scan_tb and pb own themselves
     LevelSolver(const LevelSolver&) = delete;
     LevelSolver& operator=(const LevelSolver&) = delete;
-    ~LevelSolver();             // the device buffers, the stream and the events own themselves; scan_tb and pb are destroyed here
     int persist_cap = 256;      // live levels the device-side search takes (LEVELS_PERSIST_WIDE=n: 64 .. 256)
     // once per solver
     int setup(dfta_ctx* c, const dfta_grid* grid, int mode, int tree_depth, int nV, const std::vector<JobSpec>& specs);

@@ -704,12 +704,6 @@ void print_census(const std::vector<Job>& dbg, int rounds, int debug_rounds)
 
 }  // namespace
 
-LevelSolver::~LevelSolver()
-{
-    dfta_scan_tables_destroy(&scan_tb);
-    dfta_persist_destroy(&pb);
-}
-
 // Once per solver.  jobs must be ordered by potential index v (levels of one potential contiguous, in the reference's (N,L) order)
 int LevelSolver::setup(dfta_ctx* c, const dfta_grid* grid, int mode_, int tree_depth, int nV_, const std::vector<JobSpec>& specs)
 {

@@ -23,6 +23,7 @@
 #include <mutex>
 #include <numeric>
 #include <type_traits>
+#include <memory>
 #include <vector>
 
 #include "internal.h"
@@ -1679,17 +1680,9 @@ int dfta_launch_levels_own(dfta_ctx* ctx, const dfta_grid* g, dfta::Job* d_jobs,
 }
 
 // ---- device-side level search (persist.inc): buffers and launch ------------------------------------------------------------------
-void dfta_persist_destroy(dfta_persist_buffers* pb)
-{
-    if (!pb) return;
-    for (void* q : {(void*)pb->d_ctl, (void*)pb->E, (void*)pb->us, (void*)pb->us1, (void*)pb->u0, (void*)pb->phi, (void*)pb->limit, (void*)pb->start,
-                    (void*)pb->count, (void*)pb->istop, (void*)pb->trip, (void*)pb->blk, (void*)pb->candP, (void*)pb->candQ}) if (q) (void)hipFree(q);
-    *pb = dfta_persist_buffers();
-}
-
 int dfta_persist_create(dfta_ctx* ctx, const dfta_grid* g, int nlive_cap, dfta_persist_buffers* pb)
 {
-    dfta_persist_destroy(pb);
+    pb->reset();
     int nblocks = std::min(ctx->num_cu, kPersistMaxBlocks);
     if (const char* e = dfta_knob("LEVELS_PERSIST_BLOCKS")) nblocks = std::max(2, std::min(atoi(e), nblocks));     // measurements
     pb->nblocks = nblocks;
@@ -1703,8 +1696,8 @@ int dfta_persist_create(dfta_ctx* ctx, const dfta_grid* g, int nlive_cap, dfta_p
     pb->want_trace = dfta_knob("LEVELS_PERSIST_TRACE") != nullptr;
     const size_t nt = (size_t)pb->nlive_cap * pb->tmax;
     pb->ctl_bytes = sizeof(PersistCtl) + sizeof(unsigned long long) * kPersistMaxBlocks + sizeof(PersistJob) * kPersistMaxJobs;
-    hipError_t e = hipMalloc(&pb->d_ctl, pb->ctl_bytes + sizeof(unsigned long long) * 4 * pb->trace_cap);
-    auto alloc = [&](auto& ptr, size_t count) { if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&ptr), sizeof(*ptr) * count); };
+    hipError_t e = pb->d_ctl.alloc(pb->ctl_bytes + sizeof(unsigned long long) * 4 * pb->trace_cap);
+    auto alloc = [&](auto& buf, size_t count) { if (e == hipSuccess) e = buf.alloc(count); };
     alloc(pb->E, nt); alloc(pb->us, nt); alloc(pb->us1, nt); alloc(pb->u0, nt); alloc(pb->phi, nt);
     alloc(pb->limit, nt); alloc(pb->start, nt); alloc(pb->count, nt); alloc(pb->istop, nt); alloc(pb->trip, nt);
     alloc(pb->blk, (size_t)3 * kPersistMaxBlocks);
@@ -1715,7 +1708,7 @@ int dfta_persist_create(dfta_ctx* ctx, const dfta_grid* g, int nlive_cap, dfta_p
     if (e == hipSuccess) e = hipMemset(pb->trip, 0, sizeof(int) * nt);
     if (e != hipSuccess) {
         snprintf(ctx->err, sizeof(ctx->err), "device-side level search: %s", hipGetErrorString(e));
-        dfta_persist_destroy(pb);
+        pb->reset();
         return DFTA_ERR_HIP;
     }
     return DFTA_OK;
@@ -1772,7 +1765,7 @@ int dfta_launch_levels_persist(dfta_ctx* ctx, const dfta_grid* g, dfta_persist_b
     }
     if (next > nblocks) return DFTA_ERR_INVALID;
     for (int q = next; q < nblocks; ++q) hc->pool[q >> 6] |= 1ull << (q & 63);
-    unsigned char* dctl = static_cast<unsigned char*>(pb->d_ctl);
+    unsigned char* dctl = pb->d_ctl;
     DFTA_HIP(ctx, hipMemcpyAsync(dctl, hb.data(), ctl_used, hipMemcpyHostToDevice, st));
 
     SweepArgs a;
@@ -2180,18 +2173,17 @@ struct dfta_potential {
     dfta_ctx* ctx = nullptr;
     const dfta_grid* g = nullptr;
     std::vector<double> h_V;
-    double* dV = nullptr;
-    double2* dTab = nullptr;        // 4 slots: l = 0..3
-    double2* dBounds = nullptr;
-    int* dSlots = nullptr;          // slot_v (4 zeros), slot_l (0..3)
+    DevBuf<double> dV;
+    DevBuf<double2> dTab;           // 4 slots: l = 0..3
+    DevBuf<double2> dBounds;
+    DevBuf<int> dSlots;             // slot_v (4 zeros), slot_l (0..3)
     dfta_scan_tables scan;          // tolerance mode: built on first use
     bool scan_built = false;
     // per-call scratch, grown on demand: one staging block in, one out
     size_t cap = 0;
-    char* dIn = nullptr;
-    char* dOut = nullptr;
+    DevBuf<char> dIn, dOut;
     std::vector<char> hIn, hOut;
-    double *dPsi = nullptr, *dQ = nullptr;
+    DevBuf<double> dPsi, dQ;
     size_t psi_cap = 0;
 };
 
@@ -2211,11 +2203,9 @@ int potential_scratch(dfta_potential* p, int ntrials)
     dfta_ctx* ctx = p->ctx;
     const size_t need = (size_t)std::max(ntrials, 64) * 64;      // 64 bytes per trial either way
     if (need <= p->cap) return DFTA_OK;
-    if (p->dIn) (void)hipFree(p->dIn);
-    if (p->dOut) (void)hipFree(p->dOut);
-    p->dIn = p->dOut = nullptr; p->cap = 0;
-    DFTA_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&p->dIn), need));
-    DFTA_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&p->dOut), need));
+    p->dIn.reset(); p->dOut.reset(); p->cap = 0;
+    DFTA_HIP(ctx, p->dIn.alloc(need));
+    DFTA_HIP(ctx, p->dOut.alloc(need));
     p->hIn.resize(need); p->hOut.resize(need);
     p->cap = need;
     return DFTA_OK;
@@ -2224,9 +2214,6 @@ int potential_scratch(dfta_potential* p, int ntrials)
 
 extern "C" void dfta_potential_destroy(dfta_potential* p)
 {
-    if (!p) return;
-    for (void* q : {(void*)p->dV, (void*)p->dTab, (void*)p->dBounds, (void*)p->dSlots, (void*)p->dIn, (void*)p->dOut, (void*)p->dPsi, (void*)p->dQ}) if (q) (void)hipFree(q);
-    dfta_scan_tables_destroy(&p->scan);
     delete p;
 }
 
@@ -2235,19 +2222,19 @@ extern "C" int dfta_potential_create(dfta_ctx* ctx, const dfta_grid* g, const do
     if (!ctx || !g || !V || !out) return DFTA_ERR_INVALID;
     DFTA_ENTER(ctx);
     const int N = g->N;
-    dfta_potential* p = new dfta_potential();
+    std::unique_ptr<dfta_potential> p(new dfta_potential());
     p->ctx = ctx; p->g = g;
     p->h_V.assign(V, V + N);
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&p->dV), sizeof(double) * N);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&p->dTab), sizeof(double2) * 4 * (size_t)N);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&p->dBounds), sizeof(double2) * 4 * (size_t)dfta_bounds_stride(g));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&p->dSlots), sizeof(int) * 8);
+    hipError_t e = p->dV.alloc(N);
+    if (e == hipSuccess) e = p->dTab.alloc(4 * (size_t)N);
+    if (e == hipSuccess) e = p->dBounds.alloc(4 * (size_t)dfta_bounds_stride(g));
+    if (e == hipSuccess) e = p->dSlots.alloc(8);
     const int slots[8] = {0, 0, 0, 0, 0, 1, 2, 3};
     if (e == hipSuccess) e = hipMemcpy(p->dSlots, slots, sizeof(slots), hipMemcpyHostToDevice);
-    if (e != hipSuccess) { snprintf(ctx->err, sizeof(ctx->err), "dfta_potential_create: %s", hipGetErrorString(e)); dfta_potential_destroy(p); return DFTA_ERR_HIP; }
-    const int rc = potential_build(p);
-    if (rc) { dfta_potential_destroy(p); return rc; }
-    *out = p;
+    if (e != hipSuccess) { snprintf(ctx->err, sizeof(ctx->err), "dfta_potential_create: %s", hipGetErrorString(e)); return DFTA_ERR_HIP; }
+    const int rc = potential_build(p.get());
+    if (rc) return rc;
+    *out = p.release();
     return DFTA_OK;
 }
 
@@ -2283,11 +2270,11 @@ extern "C" int dfta_potential_sweeps(dfta_potential* p, int kind, int sweep_mode
     double *hUs = hE + nt, *hUs1 = hUs + nt;
     int* hLim = reinterpret_cast<int*>(hUs1 + nt);
     int *hStart = hLim + nt, *hBs = hStart + nt, *hBf = hBs + nt, *hBc = hBf + nt;
-    double* dE = reinterpret_cast<double*>(p->dIn);
+    double* dE = reinterpret_cast<double*>(p->dIn.p);
     double *dUs = dE + nt, *dUs1 = dUs + nt;
     int* dLim = reinterpret_cast<int*>(dUs1 + nt);
     int *dStart = dLim + nt, *dBs = dStart + nt, *dBf = dBs + nt, *dBc = dBf + nt;
-    double* dU0 = reinterpret_cast<double*>(p->dOut);
+    double* dU0 = reinterpret_cast<double*>(p->dOut.p);
     int* dCount = reinterpret_cast<int*>(dU0 + nt);
     int *dTrip = dCount + nt, *dStartOut = dTrip + nt, *dBad = dStartOut + nt;
     if (sweep_mode == DFTA_SWEEPS_TOLERANCE) {
@@ -2370,11 +2357,9 @@ extern "C" int dfta_potential_match(dfta_potential* p, int ntrials, const int* l
     int rc = potential_scratch(p, ntrials);
     if (rc) return rc;
     if ((size_t)ntrials > p->psi_cap) {
-        if (p->dPsi) (void)hipFree(p->dPsi);
-        if (p->dQ) (void)hipFree(p->dQ);
-        p->dPsi = p->dQ = nullptr; p->psi_cap = 0;
-        DFTA_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&p->dPsi), sizeof(double) * (size_t)ntrials * N));
-        DFTA_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&p->dQ), sizeof(double) * (size_t)ntrials * N));
+        p->dPsi.reset(); p->dQ.reset(); p->psi_cap = 0;
+        DFTA_HIP(ctx, p->dPsi.alloc((size_t)ntrials * N));
+        DFTA_HIP(ctx, p->dQ.alloc((size_t)ntrials * N));
         p->psi_cap = ntrials;
     }
     const size_t nt = ntrials;
@@ -2382,11 +2367,11 @@ extern "C" int dfta_potential_match(dfta_potential* p, int ntrials, const int* l
     double *hUs = hE + nt, *hUs1 = hUs + nt, *hUz = hUs1 + nt;
     int* hStart = reinterpret_cast<int*>(hUz + nt);
     int *hL = hStart + nt, *hTs = hL + nt;
-    double* dE = reinterpret_cast<double*>(p->dIn);
+    double* dE = reinterpret_cast<double*>(p->dIn.p);
     double *dUs = dE + nt, *dUs1 = dUs + nt, *dUz = dUs1 + nt;
     int* dStart = reinterpret_cast<int*>(dUz + nt);
     int *dL = dStart + nt, *dTs = dL + nt;
-    int* dMp = reinterpret_cast<int*>(p->dOut);
+    int* dMp = reinterpret_cast<int*>(p->dOut.p);
     for (size_t t = 0; t < nt; ++t) {
         DFTA_REQUIRE(ctx, l[t] >= 0 && l[t] <= 3, "l");
         hE[t] = E[t]; hL[t] = l[t]; hTs[t] = l[t]; hUz[t] = 0;

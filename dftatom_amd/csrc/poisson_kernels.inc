@@ -1897,7 +1897,7 @@ __device__ __forceinline__ double cs_iterate(const MgDesc& D, Atom& A, int l, do
     const int lc = D.cs_lc[l];
     double err = 1E10;
 #ifndef DFTA_MG_SCAN_COARSE
-    const bool half = lc == 2 && L.n == 129;           // the 129-node level on 32 lanes x 4 nodes (poisson.hip: exact mode)
+    const bool half = lc == 2 && L.n == 129;           // the 129-node level on 32 lanes x 4 nodes (poisson_plan.cpp, plan_coarse_section: exact mode)
     if (D.fuse3w && iterno == 3 && lc >= 2 && lc <= 4) {
         bool done;
         switch (lc) {
@@ -2192,7 +2192,7 @@ __device__ __forceinline__ void coarse_section(const MgDesc& D, Atom& A, double 
 // their Phi in registers through the recursion (the sources in LDS, written and read by their owner only): restriction and prolongation
 // are thread-local up to one neighbour value (DPP lane shifts; across the four waves through 8 doubles of LDS), and a Gauss-Seidel sweep
 // is the affine scan of cs_sweep_scan: the chunk's recurrence from zero, a wave scan of the chunk ends with ratio r = a^C in DPP steps, the
-// value in front of the wave (the end of the wave in front: r^64 of anything further back is < 1e-18, poisson.hip checks) added to lane t's
+// value in front of the wave (the end of the wave in front: r^64 of anything further back is < 1e-18, poisson_plan.cpp: plan_rc checks) added to lane t's
 // input with r^t, the carry into the chunk with running powers of a -- 2 C + 6 dependent steps and ONE workgroup barrier per sweep (rc_iterate).
 // The levels with <= 129 nodes run in one wave, every level in registers (rw_cycle).  Same operations, stop rules and sweep counts as the
 // level-by-level code, a different order of roundings (tolerance mode; gates: tests/test_gpu_resident.py -- the uniform grid, where only
@@ -2717,7 +2717,7 @@ __device__ unsigned long long g_rprof[2 * 8 * 8];    // [role][category][level &
 #define RPROF_ADD(cat, lvl)
 #endif
 #ifdef DFTA_MG_RES16
-// Second configuration of the resident group (namespace mg_exact16; these shadow poisson.hip's constants for everything below): 16
+// Second configuration of the resident group (namespace mg_exact16; these shadow poisson_plan.h's constants for everything below): 16
 // members of 256 sweeping lanes per atom -- the same 4096 lanes, the same nodes per lane, the same levels and passes -- on 17 compute
 // units per atom instead of 33, i.e. up to 15 atoms per launch (the shards of an 8-rank periodic table).  A member's stretch is twice
 // as long, and all its shared levels no longer fit its LDS at once (254 KB): level 0 and levels 1 .. kres-1 take TURNS in the same

@@ -1249,16 +1249,8 @@ ScanGrid scan_grid_of(const dfta_grid* g, const dfta_scan_tables& tb)
 
 int dfta_scan_supported(const dfta_grid* g) { return g && !g->uniform && g->levels >= 12 && g->levels <= 20; }
 
-void dfta_scan_tables_destroy(dfta_scan_tables* tb)
-{
-    if (!tb) return;
-    for (void* q : {(void*)tb->tabv_alloc, (void*)tb->mm, (void*)tb->Atop, (void*)tb->T_alloc}) if (q) (void)hipFree(q);
-    *tb = dfta_scan_tables();
-}
-
 int dfta_scan_tables_create(dfta_ctx* ctx, const dfta_grid* g, int nslots, dfta_scan_tables* tb)
 {
-    *tb = dfta_scan_tables();
     tb->nslots = nslots;
     const int N = g->N, logC = g->levels - kLogT, C = 1 << logC;
     // A_i = 2 Rp^2 delta^2 exp(2 i delta) (Numerov.h:100) = Atop[t] T[k] for i = t C + k: the top row of every lane from the grid's own
@@ -1268,19 +1260,19 @@ int dfta_scan_tables_create(dfta_ctx* ctx, const dfta_grid* g, int nslots, dfta_
     Atop[kT] = 2. * g->Rp2delta2 * g->h_e2[N - 1];
     for (int k = 0; k < C; ++k) T[k] = exp(-g->twodelta * static_cast<double>(C - 1 - k));
     constexpr size_t kPadTab = (size_t)kScanPadRows * kT, kPadT = 8;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&tb->tabv_alloc), sizeof(double) * ((size_t)nslots * N + kPadTab));
+    hipError_t e = tb->tabv_alloc.alloc((size_t)nslots * N + kPadTab);
     if (e == hipSuccess) e = hipMemset(tb->tabv_alloc, 0, sizeof(double) * kPadTab);
     if (e == hipSuccess) tb->tabv = tb->tabv_alloc + kPadTab;
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&tb->mm), sizeof(double2) * (size_t)nslots * kT);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&tb->Atop), sizeof(double) * (kT + 1));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&tb->T_alloc), sizeof(double) * (C + kPadT));
+    if (e == hipSuccess) e = tb->mm.alloc((size_t)nslots * kT);
+    if (e == hipSuccess) e = tb->Atop.alloc(kT + 1);
+    if (e == hipSuccess) e = tb->T_alloc.alloc(C + kPadT);
     if (e == hipSuccess) e = hipMemset(tb->T_alloc, 0, sizeof(double) * kPadT);
     if (e == hipSuccess) tb->T = tb->T_alloc + kPadT;
     if (e == hipSuccess) e = hipMemcpy(tb->Atop, Atop.data(), sizeof(double) * (kT + 1), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(tb->T, T.data(), sizeof(double) * C, hipMemcpyHostToDevice);
     if (e != hipSuccess) {
         snprintf(ctx->err, sizeof(ctx->err), "scan tables: %s", hipGetErrorString(e));
-        dfta_scan_tables_destroy(tb);
+        tb->reset();
         return DFTA_ERR_HIP;
     }
     return DFTA_OK;
@@ -1379,8 +1371,8 @@ extern "C" int dfta_numerov_sweeps_scan(dfta_ctx* ctx, const dfta_grid* g, int k
     DevBuf<double> dV, dE, dU0;
     DevBuf<int> dSv, dSl, dTs, dLim, dCount, dStart, dTrip, dBad;
     DFTA_HIP(ctx, dV.alloc((size_t)nV * N));
-    struct Tables { dfta_scan_tables t; ~Tables() { dfta_scan_tables_destroy(&t); } } tb;
-    int rc = dfta_scan_tables_create(ctx, g, nslots, &tb.t);
+    dfta_scan_tables tb;
+    int rc = dfta_scan_tables_create(ctx, g, nslots, &tb);
     if (rc) return rc;
     DFTA_HIP(ctx, hipMemcpyAsync(dV.p, V, (size_t)nV * N * sizeof(double), hipMemcpyHostToDevice, st));
     DFTA_HIP(ctx, dE.alloc(ntrials)); DFTA_HIP(ctx, dU0.alloc(ntrials));
@@ -1391,10 +1383,10 @@ extern "C" int dfta_numerov_sweeps_scan(dfta_ctx* ctx, const dfta_grid* g, int k
     DFTA_HIP(ctx, hipMemcpyAsync(dSl.p, slot_l.data(), sizeof(int) * nslots, hipMemcpyHostToDevice, st));
     DFTA_HIP(ctx, hipMemcpyAsync(dTs.p, tslot.data(), sizeof(int) * ntrials, hipMemcpyHostToDevice, st));
     DFTA_HIP(ctx, hipMemcpyAsync(dLim.p, lim.data(), sizeof(int) * ntrials, hipMemcpyHostToDevice, st));
-    rc = dfta_launch_scan_build_tab(ctx, g, tb.t, dV.p, dSv.p, dSl.p);
+    rc = dfta_launch_scan_build_tab(ctx, g, tb, dV.p, dSv.p, dSl.p);
     if (rc) return rc;
     DFTA_HIP(ctx, hipEventRecord(ctx->ev[0], st));
-    rc = dfta_launch_scan_sweeps(ctx, g, kind, ntrials, tb.t, dTs.p, dE.p, dLim.p, dCount.p, dU0.p, dStart.p, dTrip.p, dBad.p);
+    rc = dfta_launch_scan_sweeps(ctx, g, kind, ntrials, tb, dTs.p, dE.p, dLim.p, dCount.p, dU0.p, dStart.p, dTrip.p, dBad.p);
     if (rc) return rc;
     DFTA_HIP(ctx, hipEventRecord(ctx->ev[1], st));
     ctx->have_kernel_time = true;
