@@ -30,6 +30,9 @@ XC_VWN, XC_CHACHIYO, XC_CHACHIYO_IMPROVED, XC_PW92, XC_PBE = range(5)
 AUFBAU_REFERENCE, AUFBAU_TRANSITION_METALS = range(2)
 MIX_LINEAR, MIX_ANDERSON = range(2)    # dfta_scf_options::mixing
 RECORD_DOUBLES = 64
+# columns of an orbital-property row (DFTA_ORB_*): NORM, <1/r>, <r>, <r^2>, <r^4>, T, r at the largest |u|, <1/r^3> (l >= 1, else 0)
+ORB_PROPS = 8
+ORB_NORM, ORB_RM1, ORB_R1, ORB_R2, ORB_R4, ORB_T, ORB_RPEAK, ORB_RM3 = range(8)
 
 c_dp = C.POINTER(C.c_double)
 c_ip = C.POINTER(C.c_int)
@@ -149,6 +152,11 @@ SIGNATURES = {
     "dfta_mixer_step": (C.c_int, [vp, C.c_double, c_dp, c_dp, c_dp, c_dp, c_ip]),
     "dfta_mixer_get": (C.c_int, [vp, C.c_int, c_ip, c_dp, c_dp, c_dp]),
     "dfta_mixer_destroy": (None, [vp]),
+    "dfta_scf_get_orbitals": (C.c_int, [vp, C.c_int, C.c_int, c_dp]),
+    "dfta_scf_orbital_properties": (C.c_int, [vp, c_dp]),
+    "dfta_scf_orbital_matrix": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, c_dp]),
+    "dfta_orbital_properties": (C.c_int, [vp, vp, C.c_int, c_ip, c_dp, c_dp]),
+    "dfta_orbital_matrix": (C.c_int, [vp, vp, C.c_int, c_dp, C.c_int, c_dp]),
 }
 
 _lib = None
@@ -553,6 +561,26 @@ def xc_radial(ctx, grid, functional, na, nb=None):
     return res.reshape(shape), va.reshape(shape), vb.reshape(shape), eexc.reshape(shape)
 
 
+def orbital_properties(ctx, grid, l, u):
+    """dfta_orbital_properties on caller-supplied orbitals u = r R of shape (norb, N) with angular momenta l: (norb, ORB_PROPS), columns
+    ORB_NORM .. ORB_RM3 (include/dftatom_hip.h has the definitions)."""
+    u = _f64(u).reshape(-1, grid.N)
+    l = _i32(np.atleast_1d(l))
+    if len(l) != u.shape[0]:
+        raise ValueError("%d angular momenta for %d orbitals" % (len(l), u.shape[0]))
+    props = np.zeros((u.shape[0], ORB_PROPS))
+    ctx.check(ctx.lib.dfta_orbital_properties(ctx.h, grid.h, u.shape[0], _ip(l), _dp(u), _dp(props)))
+    return props
+
+
+def orbital_matrix(ctx, grid, u, k):
+    """dfta_orbital_matrix: M_ab = Q[u_a u_b r^k dr/di] (k = 0, 1, 2) for u of shape (norb <= 32, N): (norb, norb), symmetric bit for bit."""
+    u = _f64(u).reshape(-1, grid.N)
+    M = np.zeros((u.shape[0], u.shape[0]))
+    ctx.check(ctx.lib.dfta_orbital_matrix(ctx.h, grid.h, u.shape[0], _dp(u), int(k), _dp(M)))
+    return M
+
+
 class Mixer:
     """The SCF's density-mixing stage on its own (dfta_mixer): the launches dfta_scf_step issues for `mixing`, on the caller's arrays."""
 
@@ -674,6 +702,36 @@ class Scf:
         out = np.zeros(self.grid.N)
         self.ctx.check(self.ctx.lib.dfta_scf_get_array(self.h, atom, which, _dp(out)))
         return out
+
+    def orbitals(self, atom=0, spin=0):
+        """u = r R_nl of every level of (atom, spin), (nlev, N), in the order of levels(): the orbitals of the last step in which the atom
+        was live -- eigenfunctions of that step's input potential (array(3 / 4) after the step is already the next one)."""
+        cnt = self.ctx.lib.dfta_scf_num_levels(self.h, atom, spin)
+        u = np.zeros((max(cnt, 0), self.grid.N))
+        self.ctx.check(self.ctx.lib.dfta_scf_get_orbitals(self.h, int(atom), int(spin), _dp(u)))
+        return u
+
+    def orbital_jobs(self):
+        """the rows of orbital_properties(): [(atom, spin, n, l), ...], atom-major, alpha then beta; n as levels() counts it"""
+        rows = []
+        for a in range(self.natoms):
+            for spin in range(2 if self.lsda else 1):
+                lv = self.levels(a, spin)
+                rows += [(a, spin, int(n), int(l)) for n, l in zip(lv["n"], lv["l"])]
+        return rows
+
+    def orbital_properties(self):
+        """(props, jobs): props (njobs, ORB_PROPS) of every orbital of the batch from one launch, jobs = orbital_jobs()"""
+        props = np.zeros((self.njobs, ORB_PROPS))
+        self.ctx.check(self.ctx.lib.dfta_scf_orbital_properties(self.h, _dp(props)))
+        return props, self.orbital_jobs()
+
+    def orbital_matrix(self, atom=0, spin=0, k=0):
+        """M_ab = Q[u_a u_b r^k dr/di] over the levels of (atom, spin), k = 0 (overlap), 1 (dipole) or 2"""
+        cnt = max(self.ctx.lib.dfta_scf_num_levels(self.h, atom, spin), 0)
+        M = np.zeros((cnt, cnt))
+        self.ctx.check(self.ctx.lib.dfta_scf_orbital_matrix(self.h, int(atom), int(spin), int(k), _dp(M)))
+        return M
 
     def set_integrator(self, rule):
         """INT_TRAPEZOID .. INT_ROMBERG: quadrature of the energy integrals and of the orbitals' normalisation."""

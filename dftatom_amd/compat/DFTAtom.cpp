@@ -20,6 +20,7 @@ std::string DFTAtom::config;
 int DFTAtom::poissonMode = -1;      // as dfta_poisson_create: exact unless $DFTA_DEBUG POISSON_MODE (--poisson= overrides)
 int DFTAtom::mixing = DFTA_MIX_LINEAR;     // --mixing=anderson: Anderson density mixing, default history and warm-up
 std::ostream* DFTAtom::jsonOut = nullptr;
+bool DFTAtom::orbitalTable = false;        // --orbital-table
 
 namespace {
 struct LevelLine { int n, l; double occ, E; int status, n_count, n_zero; };
@@ -81,6 +82,26 @@ void json_step(std::ostream& js, int sp, int Z, bool lsda, dfta_scf* scf, const 
        << "}" << std::endl;
 }
 
+// --orbital-table: one line per level from the device's orbital properties (dfta_scf_orbital_properties: one launch for all levels)
+void print_orbital_table(dfta_scf* scf, bool lsda)
+{
+    int njobs = 0;
+    if (dfta_scf_info(scf, nullptr, &njobs, nullptr) != DFTA_OK) throw std::runtime_error("dfta_scf_info");
+    std::vector<double> props(static_cast<size_t>(njobs) * DFTA_ORB_PROPS);
+    if (dfta_scf_orbital_properties(scf, props.data()) != DFTA_OK) throw std::runtime_error("dfta_scf_orbital_properties");
+    size_t row = 0;                                         // rows: the alpha levels, then the beta levels
+    for (int spin = 0; spin < (lsda ? 2 : 1); ++spin)
+        for (const auto& lv : fetch_levels(scf, spin)) {
+            const double* p = props.data() + DFTA_ORB_PROPS * row++;
+            std::cout << "Orbital " << (lsda ? (spin == 0 ? "alpha " : "beta ") : "") << lv.n + 1 << DFTAtom::orb[lv.l] << ": n = " << lv.n + 1 << " l = " << lv.l
+                      << " occ = ";
+            print_occupation(std::cout, lv.occ);
+            std::cout << " E = " << std::fixed << std::setprecision(6) << lv.E << " <r> = " << p[DFTA_ORB_R1] << " <r^2> = " << p[DFTA_ORB_R2]
+                      << " T = " << p[DFTA_ORB_T] << " r_peak = " << p[DFTA_ORB_RPEAK] << std::endl;
+        }
+    std::cout << std::endl;
+}
+
 void print_configuration(std::vector<LevelLine> levels)
 {
     // levels sorted by energy for the final configuration line (DFTAtom.cpp:487-490)
@@ -138,6 +159,7 @@ void DFTAtom::Run(bool lsda, bool uniform, int Z, int MultigridLevels, double al
         if (jsonOut) json_step(*jsonOut, sp, Z, lsda, scf, e, finished, stats);
         if (finished) {
             std::cout << std::endl << "Finished!" << std::endl << std::endl;
+            if (orbitalTable) print_orbital_table(scf, lsda);
             break;
         }
         std::cout << "********************************************************************************" << std::endl;

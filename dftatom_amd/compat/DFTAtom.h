@@ -43,6 +43,8 @@ public:
     // per-step machine-readable output (metrics): when set, every SCF step appends ONE JSON line with 17-digit
     // energies and eigenvalues, per-level status bits (DFTA_LEVEL_*) and sweep counts, rounds, V-cycles and the phases' HIP-event times
     static std::ostream* jsonOut;
+    // after "Finished!", one line per level: n, l, occupation, E and <r>, <r^2>, T, r_peak of its orbital (dfta_scf_orbital_properties)
+    static bool orbitalTable;
 
 private:
     static constexpr double fourM_PI = 4. * M_PI;

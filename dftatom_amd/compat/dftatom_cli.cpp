@@ -12,6 +12,8 @@
 // --integrator: trapezoid | simpson13 | simpson38 (default, what the reference calls) | boole | romberg (README.md:81).
 // --json[=FILE]: one JSON line per SCF step (17-digit energies and eigenvalues, per-level status bits and sweep counts, rounds, V-cycles,
 //                phase times) to FILE, or to stderr -- the console protocol on stdout stays the reference's.
+// --orbital-table: after "Finished!", one line per level with n, l, occupation, E and <r>, <r^2>, the kinetic energy T and r_peak of its
+//                orbital (atomic units; include/dftatom_hip.h: dfta_scf_orbital_properties).  Without it the output is unchanged.
 // --sweeps=exact|tolerance, --poisson=exact|tolerance|adaptive: the opt-in tolerance modes of the device path (include/dftatom_hip.h).
 // --mixing=linear (default, the reference's density mixing) | anderson (Anderson acceleration: about half the SCF steps, same protocol).
 // --xc=vwn (default, what the reference runs) | chachiyo | chachiyo-improved (LDA only) | pw92 | pbe (logarithmic grid only).
@@ -86,6 +88,8 @@ int main(int argc, char** argv)
             jf.open(a.substr(7));
             if (!jf) { std::cerr << "cannot write " << a.substr(7) << std::endl; return 2; }
             DFT::DFTAtom::jsonOut = &jf;
+        } else if (a == "--orbital-table") {
+            DFT::DFTAtom::orbitalTable = true;
         } else if (a == "--sweeps=tolerance" || a == "--sweeps=exact") {
             DFT::DFTAtom::sweepMode = a == "--sweeps=tolerance" ? DFTA_SWEEPS_TOLERANCE : DFTA_SWEEPS_EXACT;
         } else if (a == "--poisson=tolerance" || a == "--poisson=adaptive" || a == "--poisson=exact") {
@@ -135,6 +139,7 @@ int main(int argc, char** argv)
                   << "       " << argv[0] << " --ini DFTAtom.ini [--uniform] [chained] [--integrator=NAME] [--xc=NAME] [--charge=q | --config=TEXT]\n"
                   << "       --xc=vwn (default) | chachiyo | chachiyo-improved | pw92 | pbe\n"
                   << "       --mixing=linear (default) | anderson: Anderson density mixing, fewer SCF steps\n"
+                  << "       --orbital-table: after Finished!, one line per level with <r>, <r^2>, T and r_peak of its orbital\n"
                   << "       --charge=q: the cation (q > 0); --config: an electron configuration, fractional occupations allowed\n";
         return 2;
     }

@@ -117,6 +117,18 @@ int dfta_anderson_create(dfta_ctx* ctx, const dfta_grid* g, int natoms, int nspi
 // density (in), the mixed one (out); fin: per atom, finished (skipped)
 int dfta_launch_anderson_mix(dfta_ctx* ctx, const dfta_grid* g, dfta_anderson* an, int lsda, int natoms, double alpha, double oneMinusAlpha,
                              double* newDensity, double* density, double* dA, double* dB, const int* fin);
+// orbitals.hip: expectation values and r^k matrix elements of orbitals u = r R (device pointers; include/dftatom_hip.h has the definitions)
+constexpr int kOrbitalMatrixMax = 32;      // orbitals of one matrix: the levels of a spin channel (scf_configure allows 32)
+struct dfta_orbital_scratch {              // of dfta_launch_orbital_matrix, for up to norb_max orbitals
+    int norb_max = 0;
+    DevBuf<double> slab;                   // [chunk][pair a <= b]: the chunks' partial sums
+    DevBuf<double> M;                      // norb x norb
+    DevBuf<unsigned> ticket;               // 0 between launches
+};
+int dfta_orbital_scratch_create(dfta_ctx* ctx, const dfta_grid* g, int norb_max, dfta_orbital_scratch* sc);
+// props: norb x DFTA_ORB_PROPS; records the launch's time for dfta_ctx_last_kernel_ms
+int dfta_launch_orbital_properties(dfta_ctx* ctx, const dfta_grid* g, int norb, const int* dL, const double* dU, double* dProps);
+int dfta_launch_orbital_matrix(dfta_ctx* ctx, const dfta_grid* g, int norb, const double* dU, int k, double* dSlab, unsigned* dTicket, double* dM);
 // scf.hip: the k_mix launch (DFTA_MIX_LINEAR), same arguments
 int dfta_launch_linear_mix(dfta_ctx* ctx, const dfta_grid* g, int lsda, int natoms, double alpha, double oneMinusAlpha, double* newDensity,
                            double* density, double* dA, double* dB, const int* fin);

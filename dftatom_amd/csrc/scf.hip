@@ -269,6 +269,10 @@ struct dfta_scf {
     DevBuf<double> d_Ne;                  // per atom: electrons, the multigrid's outer boundary U(Rmax)
     DevBuf<double> d_density, d_dA, d_dB, d_V, d_U, d_Vexc, d_va, d_vb, d_eexc, d_newDensity, d_integrands, d_integrals, d_records;
     DevEvent ev[5];
+    // orbital expectation values and matrix elements (orbitals.hip): nothing is allocated before the first such call
+    DevBuf<int> d_orb_l;                  // per job: l
+    DevBuf<double> d_orb_props;           // njobs x DFTA_ORB_PROPS
+    dfta_orbital_scratch orb_scratch;     // of dfta_scf_orbital_matrix, sized for the longest channel of the batch
 };
 
 static int scf_xc(dfta_scf* s)
@@ -833,6 +837,75 @@ int dfta_scf_get_array(dfta_scf* s, int atom, int which, double* out)
     DFTA_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return DFTA_OK;
 }
+
+// first job and number of levels of (atom, spin); the orbitals exist once a step has run
+#define DFTA_SCF_CHANNEL(s, ctx, atom, spin, k0, cnt)                                                              \
+    DFTA_REQUIRE(ctx, s->steps_done > 0, "no SCF step has run yet: there are no orbitals");                        \
+    DFTA_REQUIRE(ctx, atom >= 0 && atom < s->natoms && spin >= 0 && spin < s->nspin, "atom/spin");                 \
+    const int k0 = s->h_atoms[atom].job_off + (spin ? s->spin_nlev[0][atom] : 0), cnt = s->spin_nlev[spin][atom]
+
+int dfta_scf_get_orbitals(dfta_scf* s, int atom, int spin, double* u)
+{
+    if (!s) return DFTA_ERR_INVALID;
+    dfta_ctx* ctx = s->ctx;
+    DFTA_ENTER(ctx);
+    DFTA_SCF_CHANNEL(s, ctx, atom, spin, k0, cnt);
+    DFTA_REQUIRE(ctx, u || cnt == 0, "u");
+    if (cnt == 0) return DFTA_OK;
+    const size_t N = s->g->N;
+    DFTA_HIP(ctx, hipMemcpyAsync(u, s->solver.d_Psi + (size_t)k0 * N, sizeof(double) * cnt * N, hipMemcpyDeviceToHost, ctx->stream));
+    DFTA_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return DFTA_OK;
+}
+
+int dfta_scf_orbital_properties(dfta_scf* s, double* props)
+{
+    if (!s) return DFTA_ERR_INVALID;
+    dfta_ctx* ctx = s->ctx;
+    DFTA_ENTER(ctx);
+    DFTA_REQUIRE(ctx, s->steps_done > 0, "no SCF step has run yet: there are no orbitals");
+    DFTA_REQUIRE(ctx, props, "props");
+    const int njobs = s->solver.njobs;
+    hipStream_t st = ctx->stream;
+    if (!s->d_orb_props.p) {                  // first use: the levels' l and the result rows
+        std::vector<int> hl(njobs);
+        for (int k = 0; k < njobs; ++k) hl[k] = s->h_jobs[k].l;
+        DFTA_HIP(ctx, s->d_orb_l.alloc(njobs));
+        DFTA_HIP(ctx, hipMemcpyAsync(s->d_orb_l.p, hl.data(), sizeof(int) * njobs, hipMemcpyHostToDevice, st));
+        DFTA_HIP(ctx, hipStreamSynchronize(st));          // hl is the source of the copy
+        DFTA_HIP(ctx, s->d_orb_props.alloc((size_t)njobs * DFTA_ORB_PROPS));
+    }
+    const int rc = dfta_launch_orbital_properties(ctx, s->g, njobs, s->d_orb_l.p, s->solver.d_Psi.p, s->d_orb_props.p);
+    if (rc) return rc;
+    DFTA_HIP(ctx, hipMemcpyAsync(props, s->d_orb_props.p, sizeof(double) * njobs * DFTA_ORB_PROPS, hipMemcpyDeviceToHost, st));
+    DFTA_HIP(ctx, hipStreamSynchronize(st));
+    return DFTA_OK;
+}
+
+int dfta_scf_orbital_matrix(dfta_scf* s, int atom, int spin, int k, double* M)
+{
+    if (!s) return DFTA_ERR_INVALID;
+    dfta_ctx* ctx = s->ctx;
+    DFTA_ENTER(ctx);
+    DFTA_SCF_CHANNEL(s, ctx, atom, spin, k0, cnt);
+    DFTA_REQUIRE(ctx, k >= 0 && k <= 2, "k (0, 1 or 2)");
+    DFTA_REQUIRE(ctx, M || cnt == 0, "M");
+    if (cnt == 0) return DFTA_OK;
+    if (!s->orb_scratch.norb_max) {           // first use: scratch for the longest channel of the batch
+        int most = 1;
+        for (int a = 0; a < s->natoms; ++a) most = std::max(most, std::max(s->spin_nlev[0][a], s->spin_nlev[1][a]));
+        const int rc = dfta_orbital_scratch_create(ctx, s->g, most, &s->orb_scratch);
+        if (rc) return rc;
+    }
+    hipStream_t st = ctx->stream;
+    const int rc = dfta_launch_orbital_matrix(ctx, s->g, cnt, s->solver.d_Psi + (size_t)k0 * s->g->N, k, s->orb_scratch.slab.p,
+                                              s->orb_scratch.ticket.p, s->orb_scratch.M.p);
+    if (rc) return rc;
+    DFTA_HIP(ctx, hipMemcpyAsync(M, s->orb_scratch.M.p, sizeof(double) * cnt * cnt, hipMemcpyDeviceToHost, st));
+    DFTA_HIP(ctx, hipStreamSynchronize(st));
+    return DFTA_OK;
+}
+#undef DFTA_SCF_CHANNEL
 
 int dfta_scf_get_records_dev(dfta_scf* s, double* dRecords)
 {

@@ -45,6 +45,8 @@ def main():
                          "per-shard wall times; their maximum PREDICTS the N-GPU wall time (shards never interact; the only collective "
                          "is a gather of 64 doubles per atom)")
     ap.add_argument("--charge", type=int, default=0, help="ionic charge of every atom (cations: dftatom_amd.ion_config); atoms with Z <= charge are skipped")
+    ap.add_argument("--orbitals", action="store_true",
+                    help="add <r> and r_peak of every atom's outermost level (the last of its alpha levels) to its row: Scf.orbital_properties()")
     ap.add_argument("--lsda", action="store_true", help="spin-polarised (LSDA) instead of LDA")
     ap.add_argument("--ionization", action="store_true",
                     help="first ionization energies: the neutral atom and the +1 cation of every Z of a rank's shard advance in one batch; "
@@ -132,6 +134,16 @@ def main():
         _, fin = scf.energies()
         if fin.all():
             break
+    outer = {}
+    if args.orbitals:                           # one launch for every orbital of this rank's batch; the row of each atom's outermost level
+        props, jobs = scf.orbital_properties()
+        for row, (a, spin, n, l) in enumerate(jobs):
+            if spin == 0:                       # jobs are sorted by (n, l) within a channel: the last alpha row of an atom stays
+                outer[int(mine[a])] = {"n": n + 1, "l": l, "r_mean": float(props[row, D.ORB_R1]), "r_peak": float(props[row, D.ORB_RPEAK])}
+        if world > 1:
+            parts = [None] * world
+            dist.all_gather_object(parts, outer)
+            outer = {z: v for p in parts for z, v in p.items()}
     block = torch.zeros((cap, D.RECORD_DOUBLES), dtype=torch.float64, device="cuda")
     scf.records_into(block.data_ptr())          # rows beyond len(mine) stay zero (Z = 0: no atom)
     ctx.synchronize()
@@ -141,14 +153,17 @@ def main():
         rows = [sweep.record_fields(table[z]) for z in sorted(table)]
         for r in rows:
             ref = NIST_LDA.get(r["Z"])
-            print("Z %3d  Etotal %16.6f  steps %3d  finished %d%s" % (r["Z"], r["Etotal"], r["steps"], r["finished"],
+            o = outer.get(r["Z"])
+            print("Z %3d  Etotal %16.6f  steps %3d  finished %d%s%s" % (r["Z"], r["Etotal"], r["steps"], r["finished"],
+                  "   %d%s <r> %.4f r_peak %.4f" % (o["n"], "spdf"[o["l"]], o["r_mean"], o["r_peak"]) if o else "",
                   "   NIST LDA %.6f (diff %.1e)" % (ref, r["Etotal"] - ref) if ref else ""))
         print("%d atoms, %d GPU(s), %d SCF steps of the longest-running atom of rank 0, %d atom-steps in all, %d finished, %.1f s"
               % (len(rows), world, steps, sum(r["steps"] for r in rows), sum(r["finished"] for r in rows), elapsed))
         if args.out:
             with open(args.out, "w") as f:
                 json.dump({"n_gpus": world, "levels": args.levels, "steps": steps, "seconds": elapsed,
-                           "atoms": [{"Z": r["Z"], "Etotal": r["Etotal"], "steps": r["steps"], "finished": r["finished"]} for r in rows]},
+                           "atoms": [dict({"Z": r["Z"], "Etotal": r["Etotal"], "steps": r["steps"], "finished": r["finished"]},
+                                          **({"outermost": outer[r["Z"]]} if r["Z"] in outer else {})) for r in rows]},
                           f, indent=1)
     scf.close()
     grid.close()

@@ -407,6 +407,48 @@ int  dfta_scf_get_array(dfta_scf* s, int atom, int which, double* out /* N */); 
 #define DFTA_RECORD_DOUBLES 64
 int  dfta_scf_get_records_dev(dfta_scf* s, double* dRecords /* natoms*64, device */);
 
+/* ---- orbitals of the SCF, their expectation values and r^k matrix elements (beyond the reference, which prints eigenvalues only) ----
+ * An orbital is the array u[i] = r_i R_nl(r_i), N doubles, exactly as the level search holds it after the step: normalised so that the
+ * SCF's quadrature of u^2 (dr/di) is 1 (DFTAtom.cpp:36-56), with the sign the match solve left, zero beyond the level's cut-off index;
+ * Sum_levels occ u^2 over the nodes i < N-1 is the step's output density times 4 pi r^2 (DFTAtom.cpp:558-559, 332-342).  The orbitals
+ * of an atom are those of the LAST STEP IN WHICH IT WAS LIVE: eigenfunctions of that step's INPUT potential, not of the potential
+ * dfta_scf_get_array(.., 3 / 4) returns after the step (that one is the next step's input).  A frozen atom keeps its orbitals.  Before
+ * the first dfta_scf_step every dfta_scf_* call of this block returns DFTA_ERR_INVALID.
+ *
+ * Quadrature: with s_i = dr/di (Rp delta exp(i delta) on the logarithmic grid, h on the uniform one),
+ *   Q[f] = (3/8) (f_0 + f_{N-1} + 3 Sum_{0<i<N-1, i%3 != 0} f_i + 2 Sum_{0<i<N-1, i%3 == 0} f_i),
+ * the weights of Integral::Simpson38 (Integral.h:50-73) -- whatever dfta_scf_options::integrator the SCF runs with (NORM shows the
+ * difference).  Columns of a property row:
+ *   NORM = Q[u^2 s];  <r^m> = Q[u^2 r^m s], m = -1, 1, 2, 4 and, for l >= 1, m = -3 (0.0 for l = 0); negative powers add 0 at r_0 = 0;
+ *   T = 1/2 Q[(du/di)^2 / s + l(l+1) u^2 / r^2 s] (second term 0 at node 0): the kinetic energy from the orbital alone; du/di is
+ *       (8 (u_{i+1} - u_{i-1}) - (u_{i+2} - u_{i-2})) / 12 inside and (-3 u_0 + 4 u_1 - u_2) / 2, (u_2 - u_0) / 2,
+ *       (u_{N-1} - u_{N-3}) / 2, (3 u_{N-1} - 4 u_{N-2} + u_{N-3}) / 2 at the nodes 0, 1, N-2, N-1;
+ *   RPEAK = r at the node of largest |u| (lowest index on ties; no interpolation).
+ * M^(k)_ab = Q[u_a u_b r^k s], k = 0, 1, 2: computed once per pair and mirrored, symmetric bit for bit.
+ * In the closed forms of a hydrogen-like atom (<r> = (3 n^2 - l(l+1)) / (2 Z), ...) n is the principal quantum number; the level
+ * arrays of this header hold the reference's m_N = n - 1.  Sums have a fixed shape that depends on N alone (no floating-point
+ * atomics): an orbital's values do not depend on the batch it sits in, nor on the run. */
+#define DFTA_ORB_PROPS 8
+#define DFTA_ORB_NORM  0
+#define DFTA_ORB_RM1   1   /* <1/r>   */
+#define DFTA_ORB_R1    2   /* <r>     */
+#define DFTA_ORB_R2    3   /* <r^2>   */
+#define DFTA_ORB_R4    4   /* <r^4>   */
+#define DFTA_ORB_T     5
+#define DFTA_ORB_RPEAK 6
+#define DFTA_ORB_RM3   7   /* <1/r^3>, l >= 1 */
+/* u: nlev x N (host), levels in the order of dfta_scf_get_levels */
+int  dfta_scf_get_orbitals(dfta_scf* s, int atom, int spin, double* u);
+/* props: njobs x DFTA_ORB_PROPS (host), every orbital of the batch in one launch; jobs atom-major, an atom's alpha levels then its
+ * beta levels (njobs of dfta_scf_info).  Records the launch's time for dfta_ctx_last_kernel_ms. */
+int  dfta_scf_orbital_properties(dfta_scf* s, double* props);
+/* M: nlev x nlev, row-major (host); k = 0, 1 or 2 */
+int  dfta_scf_orbital_matrix(dfta_scf* s, int atom, int spin, int k, double* M);
+/* the same two launches on caller-supplied orbitals (tests and tools); host pointers.  u: norb x N; props: norb x DFTA_ORB_PROPS;
+ * M: norb x norb, norb <= 32.  norb == 0: DFTA_OK, nothing is written. */
+int  dfta_orbital_properties(dfta_ctx* ctx, const dfta_grid* g, int norb, const int* l, const double* u, double* props);
+int  dfta_orbital_matrix(dfta_ctx* ctx, const dfta_grid* g, int norb, const double* u, int k, double* M);
+
 /* ---- Aufbau -------------------------------------------------------------------------------------------------
  * AufbauPrinciple::GetSubshells + sort (AufbauPrinciple.h:36-75, DFTAtom.cpp:367); integer-only host code. */
 int dfta_get_subshells(int Z, int* n, int* l, int* occ, int cap);
