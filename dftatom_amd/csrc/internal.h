@@ -7,29 +7,62 @@
 int dfta_bounds_stride(const dfta_grid* g);
 int dfta_launch_build_tab(dfta_ctx* ctx, const dfta_grid* g, double2* tab, const double* dV, const int* d_slot_v,
                           const int* d_slot_l, int nslots, double2* bounds /* nslots, may be null */);
-// for_match / dL / dUz: uniform grid only -- the match solve re-derives its step from the truncated step count, so its
-// second start value differs from a sweep's, and it needs GetBoundaryValueZero(h', l) per trial (Numerov.h:430,475)
+// Views the launch helpers take: device pointers only, nothing owned; filled member by member at the call site.
+struct SlotTables {                // the tables of the slots
+    const double2* tab;
+    const double2* bounds;         // per slot (dfta_bounds_stride), may be null
+    const int* slot_l;             // l per table slot (the uniform grid's sweeps need it)
+};
+struct WaveBlocks {                // the 64-trial blocks of a launch
+    const int* slot; const int* first; const int* cnt;
+    const int* kind;               // per block DFTA_SWEEP_COUNT / _ZERO, or null: the launch's kind
+    int n;
+};
+struct WaveBlocksRW {              // ... of the searches that write them on the device (own pace: the slots; device-side: all three)
+    int* slot; int* first; int* cnt;
+    int n;
+    WaveBlocks view(const int* kind = nullptr) const { WaveBlocks b; b.slot = slot; b.first = first; b.cnt = cnt; b.kind = kind; b.n = n; return b; }
+};
+struct SweepTrials {               // per trial, as a sweep launch uses them: inputs read, results written (u0, phi, istop, trip may be null)
+    const double *E, *us, *us1; const int *limit, *start;
+    double *u0, *phi; int *count, *istop, *trip;
+};
+struct TrialArrays {               // per trial, all writable: the own-pace and device-side searches fill the inputs themselves
+    double *E, *us, *us1, *u0, *phi;
+    int *limit, *start, *count, *istop, *trip;
+    SweepTrials sweep() const
+    {
+        SweepTrials t;
+        t.E = E; t.us = us; t.us1 = us1; t.limit = limit; t.start = start;
+        t.u0 = u0; t.phi = phi; t.count = count; t.istop = istop; t.trip = trip;
+        return t;
+    }
+};
+// uniform grid only: for_match, l and uz -- the match solve re-derives its step from the truncated step count, so its second start value
+// differs from a sweep's, and it needs GetBoundaryValueZero(h', l) per trial (Numerov.h:430,475); l and uz null: none
+struct BoundaryTrials {
+    const double* E; int n;
+    int* start; double *us, *us1;
+    int for_match; const int* l; double* uz;
+};
+struct MatchTrials {
+    const int* slot; const double* E; const int* start; const double *us, *us1; const int* l;
+    const double* uz;              // uniform grid: start value at the first node per trial
+    double *Psi, *Q; int* match_point;
+    int n;
+};
 // stream: nullptr = the context's stream (the early match solves of levels.hip run on a second one)
-int dfta_launch_boundary(dfta_ctx* ctx, const dfta_grid* g, const double* dE, int ntrials, int* dStart, double* dUs,
-                         double* dUs1, int for_match = 0, const int* dL = nullptr, double* dUz = nullptr, hipStream_t stream = nullptr);
+int dfta_launch_boundary(dfta_ctx* ctx, const dfta_grid* g, const BoundaryTrials& t, hipStream_t stream);
+int dfta_launch_match(dfta_ctx* ctx, const dfta_grid* g, const SlotTables& tables, const MatchTrials& t, hipStream_t stream);
 // flag in SweepArgs::istop (numerov.hip): the sweep left CountNodes because the count exceeded the limit
 constexpr int kStopOver = 0x40000000;
-
-int dfta_launch_sweep(dfta_ctx* ctx, const dfta_grid* g, int kind, const int* blk_kind, int nblocks, const double2* tab,
-                      const int* blk_slot, const int* blk_first, const int* blk_cnt, const double* dE, const int* dLimit,
-                      const int* dStart, const double* dUs, const double* dUs1, int* dCount, double* dU0, int* dTrip,
-                      unsigned long long* dTotalTrips, const double2* bounds /* per slot, may be null */,
-                      double* dPhi = nullptr, int* dIstop = nullptr /* SweepArgs::phi / istop, may be null */,
-                      const int* d_slot_l = nullptr /* uniform grid: l per table slot */,
-                      const int* d_queue = nullptr /* fused kernel: the round's work queue (k_expand of levels.hip), lists of qcap blocks */, int qcap = 0);
 // Balanced launch of the fused sweeps: the blocks of a round are entered into kSweepQueueClasses lists by expected length, and the launch's
 // waves (two per SIMD, all resident) take them longest first through one ticket counter -- see k_sweep_queue
 constexpr int kSweepQueueClasses = 16;
+// total_trips: optional global counter (points traversed); queue: the round's work queue (k_expand of levels.hip), lists of qcap blocks, or null
+int dfta_launch_sweep(dfta_ctx* ctx, const dfta_grid* g, int kind, const SlotTables& tables, const WaveBlocks& blocks, const SweepTrials& trials,
+                      unsigned long long* total_trips, const int* queue, int qcap);
 bool dfta_sweep_is_fused(const dfta_ctx* ctx, int nblocks);
-int dfta_launch_match(dfta_ctx* ctx, const dfta_grid* g, int ntrials, const double2* tab, const int* d_trial_slot,
-                      const double* dE, const int* dStart, const double* dUs, const double* dUs1, const int* dL,
-                      double* dPsi, double* dQ, int* dMatch, const double2* bounds /* per slot (dfta_bounds_stride), may be null */,
-                      const double* dUz = nullptr /* uniform grid: start value at the first node per trial */, hipStream_t stream = nullptr);
 
 // persist.inc (compiled with numerov.hip): the exact level search of up to 64 levels on the device, every level at its own pace
 namespace dfta { struct Job; }
@@ -57,19 +90,46 @@ struct dfta_persist_buffers {
         fault_block = -1; timeout_ms = 0; plain_launch = equal_shares = want_trace = false;
         h_stage.clear();
     }
+    TrialArrays trials() const
+    {
+        TrialArrays t;
+        t.E = E; t.us = us; t.us1 = us1; t.u0 = u0; t.phi = phi;
+        t.limit = limit; t.start = start; t.count = count; t.istop = istop; t.trip = trip;
+        return t;
+    }
+    WaveBlocksRW blocks() const;   // the three parts of blk (numerov.hip)
 };
 int dfta_persist_create(dfta_ctx* ctx, const dfta_grid* g, int nlive_cap, dfta_persist_buffers* pb);     // (re)creates: frees what pb held
-int dfta_launch_levels_persist(dfta_ctx* ctx, const dfta_grid* g, dfta_persist_buffers* pb, dfta::Job* d_jobs, const int* live, int nlive,
-                               const double2* d_tab, const double2* d_bounds, double* d_Psi, double* d_Q, int* d_jstart_keep,
-                               unsigned long long* d_counters, bool stats, int nopredict, int integ_rule, const double* tuning, int fixed_point,
-                               int* rounds, int* aborted, std::vector<unsigned long long>* trace_out, const int* share = nullptr /* host, nlive: workgroups per level */,
-                               int deep_reserve = 0 /* workgroups the pool keeps for the levels marked Job::deep == 2 */);
+struct PersistRun {
+    double *Psi, *Q; int* jstart_keep;
+    unsigned long long* counters;
+    bool stats; int nopredict, integ_rule;
+    const double* tuning;          // host: noise rel, abs, secant, kappa
+    int fixed_point;
+    const int* share;              // host, nlive: workgroups per level (null: equal shares)
+    int deep_reserve;              // workgroups the pool keeps for the levels marked Job::deep == 2
+    bool want_trace;
+};
+struct PersistResult {
+    int rounds = 0;
+    int aborted = 0;               // 1: a worker was lost (time-out) -- nothing is valid, the caller repeats the solve with host rounds
+    std::vector<unsigned long long> trace;      // want_trace: 4 words per closed round
+};
+// live (host): indices into jobs, whose records carry phase = first bisection, tbase = position in `live` x pb->tmax
+int dfta_launch_levels_persist(dfta_ctx* ctx, const dfta_grid* g, dfta_persist_buffers* pb, dfta::Job* jobs, const int* live, int nlive,
+                               const SlotTables& tables, const PersistRun& run, PersistResult* out);
 
 // own.inc (compiled with numerov.hip): the exact level search of a batch on the device, one workgroup of W waves per live level, one
-// ordinary launch; d_counters[0] += issued trials, [1] += traversed points (stats), [2] = max rounds of a level (as unsigned int)
-int dfta_launch_levels_own(dfta_ctx* ctx, const dfta_grid* g, dfta::Job* d_jobs, const int* d_live, int nlive, int W, const double2* d_tab, const double2* d_bounds,
-                           int* blk_slot, const int* blk_first, const int* blk_cnt, double* dE, int* dLimit, int* dStart, double* dUs, double* dUs1, int* dCount,
-                           double* dU0, double* dPhi, int* dIstop, int* dTrip, unsigned long long* d_counters, bool stats, int nopredict, int spine_cap);
+// ordinary launch; counters[0] += issued trials, [1] += traversed points (stats), [2] = max rounds of a level (as unsigned int)
+struct OwnOptions { bool stats; int nopredict, spine_cap; };
+struct OwnLevels {
+    dfta::Job* jobs;
+    const int* live;               // device, may be null: level q = job q; the records carry phase = first bisection, tbase = q * 64 W
+    int nlive, W;
+};
+// the trial arrays are the level solver's own (room for nlive * 64 W trials; blocks.first[b] = 64 b, blocks.cnt[b] = 64)
+int dfta_launch_levels_own(dfta_ctx* ctx, const dfta_grid* g, const OwnLevels& levels, const SlotTables& tables, const WaveBlocksRW& blocks,
+                           const TrialArrays& trials, unsigned long long* counters, const OwnOptions& opt);
 
 // scan.hip: the tolerance mode of the sweeps (transfer-matrix scan: one workgroup per trial)
 struct dfta_scan_tables {

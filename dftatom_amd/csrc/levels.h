@@ -197,6 +197,41 @@ struct LevelSolver {
             const unsigned char* frozen = nullptr);
     int fetch_jobs(std::vector<Job>& out);
 
+    // views of the solver's buffers for the launch helpers (internal.h): every buffer is named here, once
+    SlotTables tables() const
+    {
+        SlotTables t;
+        t.tab = d_tab; t.bounds = g->uniform ? nullptr : d_bounds.p; t.slot_l = d_slot_l;
+        return t;
+    }
+    WaveBlocksRW blocks(int n) const
+    {
+        WaveBlocksRW b;
+        b.slot = d_wave_slot; b.first = d_wave_first; b.cnt = d_wave_cnt; b.n = n;
+        return b;
+    }
+    TrialArrays trials(bool with_trips) const          // (the loop iterations per trial are diagnostics: written with the statistics only)
+    {
+        TrialArrays t;
+        t.E = d_E; t.us = d_us; t.us1 = d_us1; t.u0 = d_u0; t.phi = d_phi;
+        t.limit = d_limit; t.start = d_start; t.count = d_count; t.istop = d_istop; t.trip = with_trips ? d_trip.p : nullptr;
+        return t;
+    }
+    // the match solves' per-job arrays (uniform grid: the start value at the first node, one per job, lies in d_Q)
+    BoundaryTrials job_boundary() const
+    {
+        BoundaryTrials t;
+        t.E = d_jE; t.n = njobs; t.start = d_jstart; t.us = d_jus; t.us1 = d_jus1; t.for_match = 1; t.l = d_jl; t.uz = d_Q;
+        return t;
+    }
+    MatchTrials job_match() const
+    {
+        MatchTrials t;
+        t.slot = d_jslot; t.E = d_jE; t.start = d_jstart; t.us = d_jus; t.us1 = d_jus1; t.l = d_jl; t.uz = d_Q;
+        t.Psi = d_Psi; t.Q = d_Q; t.match_point = d_jmp; t.n = njobs;
+        return t;
+    }
+
 private:
     // the phases of run(), in their order (levels.hip)
     void make_plan(RunPlan& p, int run_mode, const unsigned char* frozen) const;

@@ -1164,7 +1164,6 @@ int LevelSolver::search_persist(RunPlan& p)
     dfta_range r_p("dfta: level search on the device (persistent kernel: sweeps, walk, match, normalisation)");
     DFTA_HIP(ctx, hipMemsetAsync(d_jstart_keep, 0xff, sizeof(int) * njobs, st));      // -1: frozen (the live levels write their cut-off index)
     if (p.stats) DFTA_HIP(ctx, hipEventRecord(ev[0], st));
-    int aborted = 0, persist_rounds = 0;
     float ms_persist = 0;
     const bool want_trace = pb.want_trace;
     // A level without nodes has no second bisection (walk_job takes it without a sweep): a third of the search less, so half of its equal
@@ -1179,16 +1178,20 @@ int LevelSolver::search_persist(RunPlan& p)
         if (p.second_share.empty()) for (size_t q = 0; q < plive.size() && (int)q < pb.nblocks - (int)plive.size(); ++q) share[q] = 2;
         else for (int k : p.second_share) share[p.plevel[k]] = 2;
     }
-    const int rc = dfta_launch_levels_persist(ctx, g, &pb, d_jobs, plive.data(), (int)plive.size(), d_tab, d_bounds, d_Psi, d_Q, d_jstart_keep, d_counters, p.stats,
-                                              use_prediction ? 0 : 1, integ_rule, tuning, fixed_point, &persist_rounds, &aborted, want_trace ? &persist_trace : nullptr, share.data(), persist_deep_reserve);
+    PersistRun run;
+    run.Psi = d_Psi; run.Q = d_Q; run.jstart_keep = d_jstart_keep; run.counters = d_counters;
+    run.stats = p.stats; run.nopredict = use_prediction ? 0 : 1; run.integ_rule = integ_rule; run.tuning = tuning; run.fixed_point = fixed_point;
+    run.share = share.data(); run.deep_reserve = persist_deep_reserve; run.want_trace = want_trace;
+    PersistResult res;
+    const int rc = dfta_launch_levels_persist(ctx, g, &pb, d_jobs, plive.data(), (int)plive.size(), tables(), run, &res);
     if (rc) return rc;
     if (p.stats) { DFTA_HIP(ctx, hipEventRecord(ev[1], st)); DFTA_HIP(ctx, hipEventSynchronize(ev[1])); DFTA_HIP(ctx, hipEventElapsedTime(&ms_persist, ev[0], ev[1])); }
     ++persist_runs;
-    if (!aborted) {
-        if (want_trace) print_persist_trace(persist_trace, ms_persist);
+    if (!res.aborted) {
+        if (want_trace) { persist_trace.swap(res.trace); print_persist_trace(persist_trace, ms_persist); }
         p.searched = true;            // every live level was matched and normalised by the workgroup that closed its search
         p.layout = LAYOUT_PERSIST;
-        p.rounds = persist_rounds;
+        p.rounds = res.rounds;
         p.ms_sweep = ms_persist;
         return DFTA_OK;
     }
@@ -1212,8 +1215,11 @@ int LevelSolver::search_own(RunPlan& p)
     dfta_range r_o("dfta: level search on the device (own pace: one workgroup per level, sweeps + walk)");
     DFTA_HIP(ctx, hipMemcpyAsync(d_own_live, p.plive.data(), sizeof(int) * p.plive.size(), hipMemcpyHostToDevice, st));
     if (p.stats) DFTA_HIP(ctx, hipEventRecord(ev[0], st));
-    const int rc = dfta_launch_levels_own(ctx, g, d_jobs, d_own_live, (int)p.plive.size(), p.own_W, d_tab, d_bounds, d_wave_slot, d_wave_first, d_wave_cnt, d_E, d_limit, d_start,
-                                          d_us, d_us1, d_count, d_u0, d_phi, d_istop, d_trip, d_counters, p.stats, use_prediction ? 0 : 1, own_spine_cap);
+    OwnLevels lv;
+    lv.jobs = d_jobs; lv.live = d_own_live; lv.nlive = (int)p.plive.size(); lv.W = p.own_W;
+    OwnOptions opt;
+    opt.stats = p.stats; opt.nopredict = use_prediction ? 0 : 1; opt.spine_cap = own_spine_cap;
+    const int rc = dfta_launch_levels_own(ctx, g, lv, tables(), blocks(lv.nlive * lv.W), trials(p.stats), d_counters, opt);
     if (rc) return rc;
     if (p.stats) DFTA_HIP(ctx, hipEventRecord(ev[1], st));
     tables_dirty = true;             // the kernel wrote its blocks' table slots
@@ -1251,11 +1257,11 @@ int LevelSolver::early_match_solves(RunPlan& p)
     hipLaunchKernelGGL(k_take_ready, dim3((njobs + 63) / 64), dim3(64), 0, st2.s, d_snapE.p, d_snapReady.p, d_jmatched.p, njobs, d_jE.p, d_jtake.p);
     DFTA_CHECK_LAUNCH(ctx);
     DFTA_HIP(ctx, hipEventRecord(ev_taken, st2));
-    int erc = dfta_launch_boundary(ctx, g, d_jE, njobs, d_jstart, d_jus, d_jus1, 1, d_jl, d_Q, st2);
+    int erc = dfta_launch_boundary(ctx, g, job_boundary(), st2);
     if (!erc) {
         hipLaunchKernelGGL(k_mask_ready, dim3((njobs + 63) / 64), dim3(64), 0, st2.s, d_jtake.p, njobs, d_jstart.p, d_jmatched.p, d_jstart_keep.p);
         DFTA_CHECK_LAUNCH(ctx);
-        erc = dfta_launch_match(ctx, g, njobs, d_tab, d_jslot, d_jE, d_jstart, d_jus, d_jus1, d_jl, d_Psi, d_Q, d_jmp, d_bounds, d_Q, st2);
+        erc = dfta_launch_match(ctx, g, tables(), job_match(), st2);
     }
     if (erc) return erc;
     DFTA_HIP(ctx, hipEventRecord(ev_early, st2));
@@ -1299,9 +1305,8 @@ int LevelSolver::search_rounds(RunPlan& p)
                            g->Rmax, g->h, queued ? d_queue.p : nullptr, queued ? d_queue + kSweepQueueClasses + 1 : nullptr, nwaves);
         DFTA_CHECK_LAUNCH(ctx);
         if (stats) DFTA_HIP(ctx, hipEventRecord(ev[0], st));
-        rc = dfta_launch_sweep(ctx, g, DFTA_SWEEP_COUNT, d_wave_kind, round_waves, d_tab, d_wave_slot, d_wave_first, d_wave_cnt, d_E,
-                               d_limit, d_start, d_us, d_us1, d_count, d_u0, stats ? d_trip.p : nullptr, stats ? d_counters + 1 : nullptr, g->uniform ? nullptr : d_bounds.p, d_phi,
-                               d_istop, d_slot_l, queued ? d_queue.p : nullptr, nwaves);
+        rc = dfta_launch_sweep(ctx, g, DFTA_SWEEP_COUNT, tables(), blocks(round_waves).view(d_wave_kind), trials(stats).sweep(), stats ? d_counters + 1 : nullptr,
+                               queued ? d_queue.p : nullptr, nwaves);
         if (rc) return rc;
         if (stats) DFTA_HIP(ctx, hipEventRecord(ev[1], st));
         if (!pk) {          // packed rounds have no scouts (capz == tcap)
@@ -1361,14 +1366,13 @@ int LevelSolver::finish_wavefunctions(RunPlan& p)
         if (p.early_pending) DFTA_HIP(ctx, hipStreamWaitEvent(st, ev_early, 0));       // the early solves use the same per-job scratch arrays
         hipLaunchKernelGGL(k_job_energies, dim3((njobs + 63) / 64), dim3(64), 0, st, d_jobs.p, njobs, d_jE.p, d_jslot.p, d_jl.p);
         DFTA_CHECK_LAUNCH(ctx);
-        int rc = dfta_launch_boundary(ctx, g, d_jE, njobs, d_jstart, d_jus, d_jus1, 1, d_jl, d_Q /* uniform: start value at the first node, one per job */);
+        int rc = dfta_launch_boundary(ctx, g, job_boundary(), nullptr);
         if (rc) return rc;
         // cut-off index -1 = skipped by k_match: frozen jobs (the result of their last solve stands) and jobs matched already;
         // d_jstart_keep: the cut-off index of every job that was matched in this run (-1: frozen)
         hipLaunchKernelGGL(k_mask_rest, dim3((njobs + 63) / 64), dim3(64), 0, st, d_jobs.p, njobs, d_jstart.p, d_jmatched.p, d_jstart_keep.p);
         DFTA_CHECK_LAUNCH(ctx);
-        rc = dfta_launch_match(ctx, g, njobs, d_tab, d_jslot, d_jE, d_jstart, d_jus, d_jus1, d_jl, d_Psi, d_Q, d_jmp, g->uniform ? nullptr : d_bounds.p,
-                               d_Q);
+        rc = dfta_launch_match(ctx, g, tables(), job_match(), nullptr);
         if (rc) return rc;
         hipLaunchKernelGGL(k_store_match, dim3((njobs + 63) / 64), dim3(64), 0, st, d_jobs.p, njobs, d_jmp.p, d_jstart_keep.p);
         DFTA_CHECK_LAUNCH(ctx);

@@ -28,6 +28,7 @@
 
 #include "internal.h"
 #include "levels.h"
+#include "numerov_host.h"
 #include "ordered_sum.h"
 
 namespace {
@@ -1618,68 +1619,132 @@ GridScalars scalars_of(const dfta_grid* g)
     return gs;
 }
 
-// uniform grid, host side: cut-off and start values exactly as the reference evaluates them (libm), Numerov.h:32-41,274-296
-void host_boundary_uniform(const dfta_grid* g, double E, unsigned l, bool for_match, int* start, double* us, double* us1, double* uz)
-{
-    const double s = sqrt(2. * fabs(E));
-    const double mr = 200. / s;
-    const double sp = mr < g->Rmax ? mr : g->Rmax;
-    const long steps = static_cast<long>(sp / g->h);
-    const double hh = for_match ? sp / steps : g->h;
-    *start = static_cast<int>(steps);
-    *us = exp(-sp * s);
-    *us1 = exp(-(sp - hh) * s);
-    if (uz) *uz = pow(hh, static_cast<double>(l) + 1.);
-}
-
-// host-side boundary values exactly as the reference evaluates them (libm exp)
-void host_boundary(const dfta_grid* g, double E, int* start, double* us, double* us1)
-{
-    const double s = sqrt(2. * fabs(E));
-    auto far = [&](int i) { return exp(-g->h_r[i] * s - static_cast<double>(i) * g->delta * 0.5); };
-    size_t maxIndex = static_cast<size_t>(g->N - 1), minIndex = 1;
-    while (maxIndex - minIndex > 1) {
-        const size_t mid = (maxIndex + minIndex) / 2;
-        if (far(static_cast<int>(mid)) < 1E-200) maxIndex = mid; else minIndex = mid;
-    }
-    *start = static_cast<int>(maxIndex);
-    *us = far(static_cast<int>(maxIndex));
-    *us1 = far(static_cast<int>(maxIndex) - 1);
-}
-
-
 #include "levels_device.inc"
 #include "persist.inc"
 #include "own.inc"
 
 }  // namespace
 
-// ---- own-pace level search of a batch (own.inc): one workgroup of W waves per live level, ONE ordinary launch ---------------------------
-// d_live (device, may be null: level q = job q): the jobs to solve; their records carry phase = first bisection and tbase = q * 64 W.
-// The trial arrays are the level solver's own (room for nlive * 64 W trials; blk_first[b] = 64 b, blk_cnt[b] = 64).
-int dfta_launch_levels_own(dfta_ctx* ctx, const dfta_grid* g, dfta::Job* d_jobs, const int* d_live, int nlive, int W, const double2* d_tab, const double2* d_bounds,
-                           int* blk_slot, const int* blk_first, const int* blk_cnt, double* dE, int* dLimit, int* dStart, double* dUs, double* dUs1, int* dCount,
-                           double* dU0, double* dPhi, int* dIstop, int* dTrip, unsigned long long* d_counters, bool stats, int nopredict, int spine_cap)
+// Launch plumbing shared with levels.hip and numerov_api.cpp ------------------------------------------------------------------
+// per slot: [0] the fast-division bounds, [1 ..] {min, max} of veff per block of kPipeChunk points, [stride-1] the bounds over
+// i >= kTinyFrom (series reciprocal)
+int dfta_bounds_stride(const dfta_grid* g) { return 1 + (g->N + kPipeChunk - 1) / kPipeChunk + 1 + 1; }
+
+namespace {
+// the one place that fills the sweeps' kernel argument (the three launches below)
+SweepArgs sweep_args(const dfta_grid* g, int kind, const SlotTables& tables, const WaveBlocks& blocks, const SweepTrials& trials, unsigned long long* total_trips)
 {
-    if (nlive < 1 || W < 1 || W > 8 || (W & (W - 1)) != 0 || g->uniform) return DFTA_ERR_INVALID;
     SweepArgs a;
-    a.slot_l = nullptr;
-    a.phi = dPhi; a.istop = dIstop;
-    a.kind = DFTA_SWEEP_COUNT; a.blk_kind = nullptr; a.bounds = d_bounds; a.bstride = dfta_bounds_stride(g);
-    a.tab = d_tab; a.blk_slot = blk_slot; a.blk_first = blk_first; a.blk_cnt = blk_cnt;
-    a.E = dE; a.limit = dLimit; a.start = dStart; a.us = dUs; a.us1 = dUs1; a.count = dCount; a.u0 = dU0;
-    a.trip = stats ? dTrip : nullptr; a.total_trips = stats ? d_counters + 1 : nullptr;
+    a.tab = tables.tab; a.bounds = tables.bounds; a.bstride = dfta_bounds_stride(g); a.slot_l = tables.slot_l;
+    a.blk_slot = blocks.slot; a.blk_first = blocks.first; a.blk_cnt = blocks.cnt; a.blk_kind = blocks.kind; a.kind = kind;
+    a.E = trials.E; a.limit = trials.limit; a.start = trials.start; a.us = trials.us; a.us1 = trials.us1;
+    a.count = trials.count; a.u0 = trials.u0; a.trip = trials.trip; a.phi = trials.phi; a.istop = trials.istop;
+    a.total_trips = total_trips;
+    return a;
+}
+// the sweeps of nblocks blocks run on the pipelined kernel (one workgroup per block), not on the fused one
+bool sweep_is_pipe(const dfta_ctx* ctx, int nblocks)
+{
+    return ctx->sweep_kernel == DFTA_SWEEP_AUTO ? nblocks <= kPipeMaxBlocks : ctx->sweep_kernel == DFTA_SWEEP_PIPELINED;
+}
+}  // namespace
+
+bool dfta_sweep_is_fused(const dfta_ctx* ctx, int nblocks) { return !sweep_is_pipe(ctx, nblocks); }
+
+int dfta_launch_build_tab(dfta_ctx* ctx, const dfta_grid* g, double2* tab, const double* dV, const int* d_slot_v,
+                          const int* d_slot_l, int nslots, double2* bounds)
+{
+    dim3 grid((g->N + 255) / 256 > 64 ? 64 : (g->N + 255) / 256, nslots);
+    hipLaunchKernelGGL(k_build_tab, grid, dim3(256), 0, ctx->stream, tab, dV, g->d_cl, g->d_e2, d_slot_v, d_slot_l, g->N, g->uniform);
+    DFTA_CHECK_LAUNCH(ctx);
+    if (bounds && !g->uniform) {
+        const int bstride = dfta_bounds_stride(g);
+        hipLaunchKernelGGL(k_slot_bounds, dim3(nslots), dim3(kBoundsThreads), 0, ctx->stream, tab, g->N, 2. * g->Rp2delta2, bounds, bstride);
+        hipLaunchKernelGGL(k_block_minmax, dim3((bstride + 254) / 256, nslots), dim3(256), 0, ctx->stream, tab, g->N, bounds, bstride);
+        DFTA_CHECK_LAUNCH(ctx);
+    }
+    return DFTA_OK;
+}
+
+int dfta_launch_boundary(dfta_ctx* ctx, const dfta_grid* g, const BoundaryTrials& t, hipStream_t stream)
+{
+    hipStream_t st = stream ? stream : ctx->stream;
+    if (g->uniform) {
+        hipLaunchKernelGGL(k_boundary_uniform, dim3((t.n + 255) / 256), dim3(256), 0, st, t.E, t.n, scalars_of(g), t.start,
+                           t.us, t.us1, t.for_match, t.l, t.l ? t.uz : nullptr);
+        DFTA_CHECK_LAUNCH(ctx);
+        return DFTA_OK;
+    }
+    hipLaunchKernelGGL(k_boundary, dim3((t.n + 255) / 256), dim3(256), 0, st, g->d_r, t.E, t.n, scalars_of(g), t.start, t.us, t.us1);
+    DFTA_CHECK_LAUNCH(ctx);
+    return DFTA_OK;
+}
+
+int dfta_launch_sweep(dfta_ctx* ctx, const dfta_grid* g, int kind, const SlotTables& tables, const WaveBlocks& blocks, const SweepTrials& trials,
+                      unsigned long long* total_trips, const int* queue, int qcap)
+{
+    const SweepArgs a = sweep_args(g, kind, tables, blocks, trials, total_trips);
+    const int nblocks = blocks.n;
+    if (g->uniform) {
+        if (!tables.slot_l) { snprintf(ctx->err, sizeof(ctx->err), "uniform sweeps need the slots' l"); return DFTA_ERR_INVALID; }
+        hipLaunchKernelGGL(k_usweep, dim3(nblocks), dim3(64), 0, ctx->stream, a, scalars_of(g), nblocks);
+    } else if (sweep_is_pipe(ctx, nblocks)) {
+        hipLaunchKernelGGL((k_sweep_pipe<kPipeChunk>), dim3(nblocks), dim3(kPipeThreads), 0, ctx->stream, a, scalars_of(g), nblocks, queue,
+                           queue ? queue + kSweepQueueClasses + 1 : nullptr, qcap);
+    } else if (queue) {
+        hipLaunchKernelGGL((k_sweep_queue<kChunk>), dim3(nblocks), dim3(64), 0, ctx->stream, a, scalars_of(g), queue, queue + kSweepQueueClasses + 1, qcap);
+    } else {
+        const dim3 grid((nblocks + 3) / 4), block(256);
+        hipLaunchKernelGGL((k_sweep<kChunk>), grid, block, 0, ctx->stream, a, scalars_of(g), nblocks);
+    }
+    DFTA_CHECK_LAUNCH(ctx);
+    return DFTA_OK;
+}
+
+int dfta_launch_match(dfta_ctx* ctx, const dfta_grid* g, const SlotTables& tables, const MatchTrials& t, hipStream_t stream)
+{
+    hipStream_t st = stream ? stream : ctx->stream;
+    if (g->uniform) {
+        if (!t.uz) { snprintf(ctx->err, sizeof(ctx->err), "uniform match needs the start values at the origin"); return DFTA_ERR_INVALID; }
+        hipLaunchKernelGGL(k_umatch, dim3(t.n), dim3(64), 0, st, tables.tab, t.slot, t.E, t.start, t.us, t.us1, t.uz, t.l, scalars_of(g),
+                           t.Psi, t.match_point);
+        DFTA_CHECK_LAUNCH(ctx);
+        return DFTA_OK;
+    }
+    hipLaunchKernelGGL(k_match, dim3(t.n), dim3(128), 0, st, tables.tab, t.slot, t.E, t.start, t.us, t.us1, t.l,
+                       g->zero1[0], g->zero1[1], g->zero1[2], g->zero1[3], scalars_of(g), tables.bounds, dfta_bounds_stride(g), t.Psi, t.Q,
+                       t.match_point);
+    DFTA_CHECK_LAUNCH(ctx);
+    return DFTA_OK;
+}
+
+// ---- own-pace level search of a batch (own.inc): one workgroup of W waves per live level, ONE ordinary launch ---------------------------
+int dfta_launch_levels_own(dfta_ctx* ctx, const dfta_grid* g, const OwnLevels& levels, const SlotTables& tables, const WaveBlocksRW& blocks,
+                           const TrialArrays& trials, unsigned long long* counters, const OwnOptions& opt)
+{
+    const int W = levels.W;
+    if (levels.nlive < 1 || W < 1 || W > 8 || (W & (W - 1)) != 0 || g->uniform) return DFTA_ERR_INVALID;
+    SweepTrials st = trials.sweep();
+    if (!opt.stats) st.trip = nullptr;
+    const SweepArgs a = sweep_args(g, DFTA_SWEEP_COUNT, tables, blocks.view(), st, opt.stats ? counters + 1 : nullptr);
     OwnArgs oa;
-    oa.jobs = d_jobs; oa.live = d_live; oa.r = g->d_r; oa.W = W; oa.nopredict = nopredict; oa.spine_cap = spine_cap;
-    oa.E = dE; oa.us = dUs; oa.us1 = dUs1; oa.limit = dLimit; oa.start = dStart; oa.blk_slot = blk_slot;
-    oa.issued = d_counters;
-    oa.max_rounds = reinterpret_cast<unsigned int*>(d_counters + 2);
-    hipLaunchKernelGGL(k_levels_own, dim3(nlive), dim3(64 * W), 0, ctx->stream, a, scalars_of(g), oa);
+    oa.jobs = levels.jobs; oa.live = levels.live; oa.r = g->d_r; oa.W = W; oa.nopredict = opt.nopredict; oa.spine_cap = opt.spine_cap;
+    oa.E = trials.E; oa.us = trials.us; oa.us1 = trials.us1; oa.limit = trials.limit; oa.start = trials.start; oa.blk_slot = blocks.slot;
+    oa.issued = counters;
+    oa.max_rounds = reinterpret_cast<unsigned int*>(counters + 2);
+    hipLaunchKernelGGL(k_levels_own, dim3(levels.nlive), dim3(64 * W), 0, ctx->stream, a, scalars_of(g), oa);
     DFTA_CHECK_LAUNCH(ctx);
     return DFTA_OK;
 }
 
 // ---- device-side level search (persist.inc): buffers and launch ------------------------------------------------------------------
+WaveBlocksRW dfta_persist_buffers::blocks() const
+{
+    WaveBlocksRW b;
+    b.slot = blk; b.first = blk + kPersistMaxBlocks; b.cnt = blk + 2 * kPersistMaxBlocks; b.n = nblocks;
+    return b;
+}
+
 int dfta_persist_create(dfta_ctx* ctx, const dfta_grid* g, int nlive_cap, dfta_persist_buffers* pb)
 {
     pb->reset();
@@ -1714,678 +1779,128 @@ int dfta_persist_create(dfta_ctx* ctx, const dfta_grid* g, int nlive_cap, dfta_p
     return DFTA_OK;
 }
 
-// Launches the search of the live levels `live` (host, indices into d_jobs, whose records carry phase = first bisection, tbase = position
-// in `live` x pb->tmax).  *aborted = 1: a worker was lost (time-out) -- nothing is valid, the caller repeats the solve with host rounds.
-int dfta_launch_levels_persist(dfta_ctx* ctx, const dfta_grid* g, dfta_persist_buffers* pb, dfta::Job* d_jobs, const int* live, int nlive,
-                               const double2* d_tab, const double2* d_bounds, double* d_Psi, double* d_Q, int* d_jstart_keep,
-                               unsigned long long* d_counters, bool stats, int nopredict, int integ_rule, const double* tuning /* noise rel, abs, secant, kappa */,
-                               int fixed_point, int* rounds, int* aborted, std::vector<unsigned long long>* trace_out, const int* share, int deep_reserve)
+namespace {
+constexpr size_t kCtlMbox = sizeof(PersistCtl);                                              // the parts of the control block, in bytes
+constexpr size_t kCtlJobs = kCtlMbox + sizeof(unsigned long long) * kPersistMaxBlocks;
+
+// this translation unit's copies of the prediction constants (levels_device.inc), per device
+int persist_upload_constants(dfta_ctx* ctx, const double* tuning, int fixed_point)
 {
-    *aborted = 0;
-    if (nlive < 1 || nlive > pb->nlive_cap || g->uniform) return DFTA_ERR_INVALID;
-    const int nblocks = pb->nblocks;
-    const int base = nblocks / nlive;
-    if (base < 1) return DFTA_ERR_INVALID;
-    hipStream_t st = ctx->stream;
-    {   // this translation unit's copies of the prediction constants (levels_device.inc), per device
-        static std::mutex mu;                 // (contexts of several host threads may launch on the same device)
-        std::lock_guard<std::mutex> lock(mu);
-        static double last[16][4];
-        static int last_fp[16];
-        static bool have[16];
-        const int dv = ctx->device >= 0 && ctx->device < 16 ? ctx->device : -1;
-        if (dv < 0 || !have[dv] || memcmp(last[dv], tuning, sizeof(last[dv])) != 0 || last_fp[dv] != fixed_point) {
-            DFTA_HIP(ctx, hipMemcpyToSymbol(HIP_SYMBOL(g_noise_rel), &tuning[0], sizeof(double)));
-            DFTA_HIP(ctx, hipMemcpyToSymbol(HIP_SYMBOL(g_noise_abs), &tuning[1], sizeof(double)));
-            DFTA_HIP(ctx, hipMemcpyToSymbol(HIP_SYMBOL(g_secant_noise), &tuning[2], sizeof(double)));
-            DFTA_HIP(ctx, hipMemcpyToSymbol(HIP_SYMBOL(g_secant_kappa), &tuning[3], sizeof(double)));
-            DFTA_HIP(ctx, hipMemcpyToSymbol(HIP_SYMBOL(g_fixed_point), &fixed_point, sizeof(int)));
-            if (dv >= 0) { memcpy(last[dv], tuning, sizeof(last[dv])); last_fp[dv] = fixed_point; have[dv] = true; }
-        }
+    static std::mutex mu;                 // (contexts of several host threads may launch on the same device)
+    std::lock_guard<std::mutex> lock(mu);
+    static double last[16][4];
+    static int last_fp[16];
+    static bool have[16];
+    const int dv = ctx->device >= 0 && ctx->device < 16 ? ctx->device : -1;
+    if (dv < 0 || !have[dv] || memcmp(last[dv], tuning, sizeof(last[dv])) != 0 || last_fp[dv] != fixed_point) {
+        DFTA_HIP(ctx, hipMemcpyToSymbol(HIP_SYMBOL(g_noise_rel), &tuning[0], sizeof(double)));
+        DFTA_HIP(ctx, hipMemcpyToSymbol(HIP_SYMBOL(g_noise_abs), &tuning[1], sizeof(double)));
+        DFTA_HIP(ctx, hipMemcpyToSymbol(HIP_SYMBOL(g_secant_noise), &tuning[2], sizeof(double)));
+        DFTA_HIP(ctx, hipMemcpyToSymbol(HIP_SYMBOL(g_secant_kappa), &tuning[3], sizeof(double)));
+        DFTA_HIP(ctx, hipMemcpyToSymbol(HIP_SYMBOL(g_fixed_point), &fixed_point, sizeof(int)));
+        if (dv >= 0) { memcpy(last[dv], tuning, sizeof(last[dv])); last_fp[dv] = fixed_point; have[dv] = true; }
     }
-    // control block: pool, counters, mailboxes (the first workgroup of every level plans its first round), the levels' workgroups
+    return DFTA_OK;
+}
+
+// control block: pool, counters, mailboxes (the first workgroup of every level plans its first round), the levels' workgroups
+int persist_upload_ctl(dfta_ctx* ctx, dfta_persist_buffers* pb, const int* live, int nlive, const dfta_nh::PersistPlan& plan)
+{
     std::vector<unsigned char>& hb = pb->h_stage;
-    const size_t ctl_used = sizeof(PersistCtl) + sizeof(unsigned long long) * kPersistMaxBlocks + sizeof(PersistJob) * (size_t)nlive;   // (the records of the levels in use)
+    const size_t ctl_used = kCtlJobs + sizeof(PersistJob) * (size_t)nlive;   // (the records of the levels in use)
     hb.assign(ctl_used, 0);
     PersistCtl* hc = reinterpret_cast<PersistCtl*>(hb.data());
-    unsigned long long* hm = reinterpret_cast<unsigned long long*>(hb.data() + sizeof(PersistCtl));
-    PersistJob* hj = reinterpret_cast<PersistJob*>(hb.data() + sizeof(PersistCtl) + sizeof(unsigned long long) * kPersistMaxBlocks);
+    unsigned long long* hm = reinterpret_cast<unsigned long long*>(hb.data() + kCtlMbox);
+    PersistJob* hj = reinterpret_cast<PersistJob*>(hb.data() + kCtlJobs);
     hc->live = (unsigned)nlive;
     hc->t0 = ~0ull;
-    int next = 0;
+    for (size_t w = 0; w < plan.pool.size(); ++w) hc->pool[w] = plan.pool[w];
+    for (int q = 0; q < pb->nblocks; ++q) if (plan.plan_level[q] >= 0) hm[q] = persist_msg(kCmdPlan, plan.plan_level[q], 0);
     for (int k = 0; k < nlive; ++k) {
-        // (a level never starts with more than an equal share -- except where that share is ONE workgroup: the caller hands the rest out as second ones)
-        const int mine = share ? (base == 1 ? std::min(std::max(share[k], 1), 2) : std::max(2, std::min(share[k], base))) : base;      // (a level never starts with more than an equal share)
         hj[k].job = live[k];
-        hj[k].base = mine;
-        hj[k].nown = mine;
-        for (int q = 0; q < mine; ++q) hj[k].blocks[q] = static_cast<unsigned short>(next + q);
-        hm[next] = persist_msg(kCmdPlan, k, 0);
-        next += mine;
+        hj[k].base = plan.base[k];
+        hj[k].nown = plan.nown[k];
+        std::copy_n(plan.blocks.begin() + plan.first[k], plan.nown[k], hj[k].blocks);
     }
-    if (next > nblocks) return DFTA_ERR_INVALID;
-    for (int q = next; q < nblocks; ++q) hc->pool[q >> 6] |= 1ull << (q & 63);
-    unsigned char* dctl = pb->d_ctl;
-    DFTA_HIP(ctx, hipMemcpyAsync(dctl, hb.data(), ctl_used, hipMemcpyHostToDevice, st));
+    DFTA_HIP(ctx, hipMemcpyAsync(pb->d_ctl.p, hb.data(), ctl_used, hipMemcpyHostToDevice, ctx->stream));
+    return DFTA_OK;
+}
 
-    SweepArgs a;
-    a.slot_l = nullptr;
-    a.phi = pb->phi; a.istop = pb->istop;
-    a.kind = DFTA_SWEEP_COUNT; a.blk_kind = nullptr; a.bounds = d_bounds; a.bstride = dfta_bounds_stride(g);
-    a.tab = d_tab; a.blk_slot = pb->blk; a.blk_first = pb->blk + kPersistMaxBlocks; a.blk_cnt = pb->blk + 2 * kPersistMaxBlocks;
-    a.E = pb->E; a.limit = pb->limit; a.start = pb->start; a.us = pb->us; a.us1 = pb->us1; a.count = pb->count; a.u0 = pb->u0;
-    a.trip = stats ? pb->trip : nullptr; a.total_trips = stats ? d_counters + 1 : nullptr;
+PersistArgs persist_args(const dfta_grid* g, const dfta_persist_buffers* pb, dfta::Job* jobs, const PersistRun& run)
+{
+    unsigned char* dctl = pb->d_ctl;
+    const TrialArrays t = pb->trials();
+    const WaveBlocksRW b = pb->blocks();
     PersistArgs pa;
-    pa.jobs = d_jobs;
+    pa.jobs = jobs;
     pa.ctl = reinterpret_cast<PersistCtl*>(dctl);
-    pa.mbox = reinterpret_cast<unsigned long long*>(dctl + sizeof(PersistCtl));
-    pa.pj = reinterpret_cast<PersistJob*>(dctl + sizeof(PersistCtl) + sizeof(unsigned long long) * kPersistMaxBlocks);
+    pa.mbox = reinterpret_cast<unsigned long long*>(dctl + kCtlMbox);
+    pa.pj = reinterpret_cast<PersistJob*>(dctl + kCtlJobs);
     pa.r = g->d_r;
-    pa.nblocks = nblocks;
-    pa.nopredict = nopredict;
+    pa.nblocks = pb->nblocks;
+    pa.nopredict = run.nopredict;
     pa.timeout_ticks = static_cast<long long>(100e6 * (3.0 + 4.0 * g->N / 131072.0));      // wall clock at 100 MHz
     if (pb->timeout_ms > 0) pa.timeout_ticks = static_cast<long long>(1e5 * pb->timeout_ms);
-    pa.E = pb->E; pa.us = pb->us; pa.us1 = pb->us1; pa.limit = pb->limit; pa.start = pb->start;
-    pa.blk_slot = pb->blk; pa.blk_first = pb->blk + kPersistMaxBlocks; pa.blk_cnt = pb->blk + 2 * kPersistMaxBlocks;
-    pa.Psi = d_Psi; pa.Q = d_Q; pa.jstart_keep = d_jstart_keep;
+    pa.E = t.E; pa.us = t.us; pa.us1 = t.us1; pa.limit = t.limit; pa.start = t.start;
+    pa.blk_slot = b.slot; pa.blk_first = b.first; pa.blk_cnt = b.cnt;
+    pa.Psi = run.Psi; pa.Q = run.Q; pa.jstart_keep = run.jstart_keep;
     pa.candP = pb->candP; pa.candQ = pb->candQ;
     pa.eh = g->d_eh; pa.cnst = g->d_cnst;
     for (int q = 0; q < 4; ++q) pa.zero1[q] = g->zero1[q];
     pa.step = 1.0;
-    pa.rule = integ_rule;
-    pa.issued = d_counters;
-    pa.trace = trace_out ? reinterpret_cast<unsigned long long*>(dctl + pb->ctl_bytes) : nullptr;
+    pa.rule = run.integ_rule;
+    pa.issued = run.counters;
+    pa.trace = run.want_trace ? reinterpret_cast<unsigned long long*>(dctl + pb->ctl_bytes) : nullptr;
     pa.trace_cap = (unsigned)pb->trace_cap;
     pa.fault_block = pb->fault_block;
-    pa.deep_reserve = deep_reserve;
-    GridScalars gs = scalars_of(g);
+    pa.deep_reserve = run.deep_reserve;
+    return pa;
+}
+
+// the launch and what it reports
+int persist_launch(dfta_ctx* ctx, const dfta_persist_buffers* pb, SweepArgs a, GridScalars gs, PersistArgs pa, bool want_trace, PersistResult* out)
+{
+    hipStream_t st = ctx->stream;
+    unsigned char* dctl = pb->d_ctl;
     // the workers wait for each other: co-residency is the launch's business (one workgroup per compute unit: 140 KB of LDS).  Under a
     // profiler the launch is an ordinary one (rocprofiler-sdk 7.2 crashes in an exit handler after a cooperative launch, see poisson.hip)
     const bool plain = getenv("ROCP_TOOL_LIBRARIES") != nullptr || pb->plain_launch;
     if (plain) {
-        hipLaunchKernelGGL(k_levels_persist, dim3(nblocks), dim3(kPipeThreads), 0, st, a, gs, pa);
+        hipLaunchKernelGGL(k_levels_persist, dim3(pb->nblocks), dim3(kPipeThreads), 0, st, a, gs, pa);
         DFTA_CHECK_LAUNCH(ctx);
     } else {
         void* args[] = {&a, &gs, &pa};
-        const hipError_t e = hipLaunchCooperativeKernel(reinterpret_cast<const void*>(k_levels_persist), dim3(nblocks), dim3(kPipeThreads), args, 0, st);
-        if (e != hipSuccess) { (void)hipGetLastError(); *aborted = 1; return DFTA_OK; }      // not co-resident: host rounds
+        const hipError_t e = hipLaunchCooperativeKernel(reinterpret_cast<const void*>(k_levels_persist), dim3(pb->nblocks), dim3(kPipeThreads), args, 0, st);
+        if (e != hipSuccess) { (void)hipGetLastError(); out->aborted = 1; return DFTA_OK; }      // not co-resident: host rounds
     }
-    PersistCtl out;
-    DFTA_HIP(ctx, hipMemcpyAsync(&out, dctl, sizeof(out), hipMemcpyDeviceToHost, st));
+    PersistCtl ctl;
+    DFTA_HIP(ctx, hipMemcpyAsync(&ctl, dctl, sizeof(ctl), hipMemcpyDeviceToHost, st));
     DFTA_HIP(ctx, hipStreamSynchronize(st));
-    if (out.abort || out.live != 0) { *aborted = 1; return DFTA_OK; }
-    if (rounds) *rounds = (int)out.max_rounds;
-    if (trace_out) {
-        const unsigned int n = std::min(out.trace_n, (unsigned)pb->trace_cap);
-        trace_out->resize((size_t)4 * n);
-        if (n) DFTA_HIP(ctx, hipMemcpy(trace_out->data(), dctl + pb->ctl_bytes, sizeof(unsigned long long) * 4 * n, hipMemcpyDeviceToHost));
+    if (ctl.abort || ctl.live != 0) { out->aborted = 1; return DFTA_OK; }
+    out->rounds = (int)ctl.max_rounds;
+    if (want_trace) {
+        const unsigned int n = std::min(ctl.trace_n, (unsigned)pb->trace_cap);
+        out->trace.resize((size_t)4 * n);
+        if (n) DFTA_HIP(ctx, hipMemcpy(out->trace.data(), dctl + pb->ctl_bytes, sizeof(unsigned long long) * 4 * n, hipMemcpyDeviceToHost));
     }
-    return DFTA_OK;
-}
-
-// per slot: [0] the fast-division bounds, [1 ..] {min, max} of veff per block of kPipeChunk points, [stride-1] the bounds over
-// i >= kTinyFrom (series reciprocal)
-int dfta_bounds_stride(const dfta_grid* g) { return 1 + (g->N + kPipeChunk - 1) / kPipeChunk + 1 + 1; }
-
-// Launch plumbing shared with levels.hip ------------------------------------------------------------------
-int dfta_launch_build_tab(dfta_ctx* ctx, const dfta_grid* g, double2* tab, const double* dV, const int* d_slot_v,
-                          const int* d_slot_l, int nslots, double2* bounds)
-{
-    dim3 grid((g->N + 255) / 256 > 64 ? 64 : (g->N + 255) / 256, nslots);
-    hipLaunchKernelGGL(k_build_tab, grid, dim3(256), 0, ctx->stream, tab, dV, g->d_cl, g->d_e2, d_slot_v, d_slot_l, g->N, g->uniform);
-    DFTA_CHECK_LAUNCH(ctx);
-    if (bounds && !g->uniform) {
-        const int bstride = dfta_bounds_stride(g);
-        hipLaunchKernelGGL(k_slot_bounds, dim3(nslots), dim3(kBoundsThreads), 0, ctx->stream, tab, g->N, 2. * g->Rp2delta2, bounds, bstride);
-        hipLaunchKernelGGL(k_block_minmax, dim3((bstride + 254) / 256, nslots), dim3(256), 0, ctx->stream, tab, g->N, bounds, bstride);
-        DFTA_CHECK_LAUNCH(ctx);
-    }
-    return DFTA_OK;
-}
-
-int dfta_launch_boundary(dfta_ctx* ctx, const dfta_grid* g, const double* dE, int ntrials, int* dStart, double* dUs, double* dUs1,
-                         int for_match, const int* dL, double* dUz, hipStream_t stream)
-{
-    hipStream_t st = stream ? stream : ctx->stream;
-    if (g->uniform) {
-        hipLaunchKernelGGL(k_boundary_uniform, dim3((ntrials + 255) / 256), dim3(256), 0, st, dE, ntrials, scalars_of(g), dStart,
-                           dUs, dUs1, for_match, dL, dL ? dUz : nullptr);
-        DFTA_CHECK_LAUNCH(ctx);
-        return DFTA_OK;
-    }
-    hipLaunchKernelGGL(k_boundary, dim3((ntrials + 255) / 256), dim3(256), 0, st, g->d_r, dE, ntrials,
-                       scalars_of(g), dStart, dUs, dUs1);
-    DFTA_CHECK_LAUNCH(ctx);
-    return DFTA_OK;
-}
-
-int dfta_launch_sweep(dfta_ctx* ctx, const dfta_grid* g, int kind, const int* blk_kind, int nblocks, const double2* tab,
-                      const int* blk_slot, const int* blk_first, const int* blk_cnt, const double* dE, const int* dLimit,
-                      const int* dStart, const double* dUs, const double* dUs1, int* dCount, double* dU0, int* dTrip,
-                      unsigned long long* dTotalTrips, const double2* bounds, double* dPhi, int* dIstop, const int* d_slot_l, const int* d_queue, int qcap)
-{
-    SweepArgs a;
-    a.slot_l = d_slot_l;
-    a.phi = dPhi; a.istop = dIstop;
-    a.kind = kind; a.blk_kind = blk_kind; a.bounds = bounds; a.bstride = dfta_bounds_stride(g);
-    a.tab = tab; a.blk_slot = blk_slot; a.blk_first = blk_first; a.blk_cnt = blk_cnt; a.E = dE; a.limit = dLimit;
-    a.start = dStart; a.us = dUs; a.us1 = dUs1; a.count = dCount; a.u0 = dU0; a.trip = dTrip; a.total_trips = dTotalTrips;
-    const bool pipe = ctx->sweep_kernel == DFTA_SWEEP_AUTO ? nblocks <= kPipeMaxBlocks : ctx->sweep_kernel == DFTA_SWEEP_PIPELINED;
-    if (g->uniform) {
-        if (!d_slot_l) { snprintf(ctx->err, sizeof(ctx->err), "uniform sweeps need the slots' l"); return DFTA_ERR_INVALID; }
-        hipLaunchKernelGGL(k_usweep, dim3(nblocks), dim3(64), 0, ctx->stream, a, scalars_of(g), nblocks);
-    } else if (pipe) {
-        hipLaunchKernelGGL((k_sweep_pipe<kPipeChunk>), dim3(nblocks), dim3(kPipeThreads), 0, ctx->stream, a, scalars_of(g), nblocks, d_queue,
-                           d_queue ? d_queue + kSweepQueueClasses + 1 : nullptr, qcap);
-    } else if (d_queue) {
-        hipLaunchKernelGGL((k_sweep_queue<kChunk>), dim3(nblocks), dim3(64), 0, ctx->stream, a, scalars_of(g), d_queue, d_queue + kSweepQueueClasses + 1, qcap);
-    } else {
-        const dim3 grid((nblocks + 3) / 4), block(256);
-        hipLaunchKernelGGL((k_sweep<kChunk>), grid, block, 0, ctx->stream, a, scalars_of(g), nblocks);
-    }
-    DFTA_CHECK_LAUNCH(ctx);
-    return DFTA_OK;
-}
-
-bool dfta_sweep_is_fused(const dfta_ctx* ctx, int nblocks)
-{
-    return !(ctx->sweep_kernel == DFTA_SWEEP_AUTO ? nblocks <= kPipeMaxBlocks : ctx->sweep_kernel == DFTA_SWEEP_PIPELINED);
-}
-
-int dfta_launch_match(dfta_ctx* ctx, const dfta_grid* g, int ntrials, const double2* tab, const int* d_trial_slot,
-                      const double* dE, const int* dStart, const double* dUs, const double* dUs1, const int* dL,
-                      double* dPsi, double* dQ, int* dMatch, const double2* bounds, const double* dUz, hipStream_t stream)
-{
-    hipStream_t st = stream ? stream : ctx->stream;
-    if (g->uniform) {
-        if (!dUz) { snprintf(ctx->err, sizeof(ctx->err), "uniform match needs the start values at the origin"); return DFTA_ERR_INVALID; }
-        hipLaunchKernelGGL(k_umatch, dim3(ntrials), dim3(64), 0, st, tab, d_trial_slot, dE, dStart, dUs, dUs1, dUz, dL, scalars_of(g),
-                           dPsi, dMatch);
-        DFTA_CHECK_LAUNCH(ctx);
-        return DFTA_OK;
-    }
-    hipLaunchKernelGGL(k_match, dim3(ntrials), dim3(128), 0, st, tab, d_trial_slot, dE, dStart, dUs, dUs1, dL,
-                       g->zero1[0], g->zero1[1], g->zero1[2], g->zero1[3], scalars_of(g), bounds, dfta_bounds_stride(g), dPsi, dQ,
-                       dMatch);
-    DFTA_CHECK_LAUNCH(ctx);
-    return DFTA_OK;
-}
-
-// ---- C ABI -----------------------------------------------------------------------------------------------------
-namespace {
-
-struct Grouping {
-    std::vector<int> order;       // sorted trial -> original trial
-    std::vector<int> slot_v, slot_l;
-    std::vector<int> blk_slot, blk_first, blk_cnt;
-    std::vector<int> trial_slot;  // per sorted trial
-};
-
-// group trials by (vidx, l) so every wave shares its per-point inputs
-int make_grouping(int ntrials, const int* vidx, const int* l, int nV, Grouping& G)
-{
-    G.order.resize(ntrials);
-    std::iota(G.order.begin(), G.order.end(), 0);
-    auto key = [&](int t) { return (vidx ? vidx[t] : 0) * 4 + l[t]; };
-    for (int t = 0; t < ntrials; ++t) {
-        const int v = vidx ? vidx[t] : 0;
-        if (v < 0 || v >= nV || l[t] < 0 || l[t] > 3) return DFTA_ERR_INVALID;
-    }
-    std::stable_sort(G.order.begin(), G.order.end(), [&](int a, int b) { return key(a) < key(b); });
-    G.trial_slot.resize(ntrials);
-    int p = 0;
-    while (p < ntrials) {
-        const int k = key(G.order[p]);
-        int q = p;
-        while (q < ntrials && key(G.order[q]) == k) ++q;
-        const int slot = static_cast<int>(G.slot_v.size());
-        G.slot_v.push_back(k / 4);
-        G.slot_l.push_back(k % 4);
-        for (int s = p; s < q; s += 64) {
-            G.blk_slot.push_back(slot);
-            G.blk_first.push_back(s);
-            G.blk_cnt.push_back(std::min(64, q - s));
-        }
-        for (int s = p; s < q; ++s) G.trial_slot[s] = slot;
-        p = q;
-    }
-    return DFTA_OK;
-}
-
-template <typename T>
-hipError_t upload(DevBuf<T>& d, const std::vector<T>& h, hipStream_t s)
-{
-    hipError_t e = d.alloc(h.size());
-    if (e != hipSuccess || h.empty()) return e;
-    return hipMemcpyAsync(d.p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice, s);
-}
-
-}  // namespace
-
-extern "C" int dfta_numerov_sweeps(dfta_ctx* ctx, const dfta_grid* g, int kind, int boundary, int nV, const double* V,
-                                   int ntrials, const int* vidx, const int* l, const double* E, const int* nodesLimit,
-                                   int* count_out, double* u0_out, int* start_out, int* trip_out)
-{
-    if (!ctx || !g) return DFTA_ERR_INVALID;
-    DFTA_ENTER(ctx);
-    DFTA_REQUIRE(ctx, ntrials >= 0, "negative trial count");
-    if (ntrials == 0) return DFTA_OK;                       // empty batch
-    DFTA_REQUIRE(ctx, V && l && E && nV > 0, "null input");
-    DFTA_REQUIRE(ctx, kind == DFTA_SWEEP_COUNT || kind == DFTA_SWEEP_ZERO, "kind");
-    DFTA_REQUIRE(ctx, kind != DFTA_SWEEP_COUNT || (nodesLimit && count_out), "COUNT needs nodesLimit and count_out");
-    DFTA_REQUIRE(ctx, kind != DFTA_SWEEP_ZERO || u0_out, "ZERO needs u0_out");
-    if (kind == DFTA_SWEEP_COUNT)
-        for (int t = 0; t < ntrials; ++t) DFTA_REQUIRE(ctx, nodesLimit[t] >= 0 && nodesLimit[t] < (1 << 30), "nodesLimit out of range");
-    if (ntrials == 0) return DFTA_OK;
-    const int N = g->N;
-    Grouping G;
-    if (make_grouping(ntrials, vidx, l, nV, G) != DFTA_OK) { snprintf(ctx->err, sizeof(ctx->err), "invalid vidx/l"); return DFTA_ERR_INVALID; }
-
-    std::vector<double> sE(ntrials), sUs(ntrials), sUs1(ntrials);
-    std::vector<int> sLim(ntrials, 0), sStart(ntrials);
-    for (int s = 0; s < ntrials; ++s) {
-        const int t = G.order[s];
-        sE[s] = E[t];
-        if (nodesLimit) sLim[s] = nodesLimit[t];
-        if (boundary == DFTA_BOUNDARY_HOST) {
-            if (g->uniform) host_boundary_uniform(g, E[t], static_cast<unsigned>(l[t]), false, &sStart[s], &sUs[s], &sUs1[s], nullptr);
-            else host_boundary(g, E[t], &sStart[s], &sUs[s], &sUs1[s]);
-        }
-    }
-    DevBuf<double> dV, dE, dUs, dUs1, dU0;
-    DevBuf<int> dLim, dStart, dCount, dTrip, dSlotV, dSlotL, dBs, dBf, dBc;
-    DevBuf<double2> dTab;
-    hipStream_t st = ctx->stream;
-    DFTA_HIP(ctx, dV.alloc((size_t)nV * N));
-    DFTA_HIP(ctx, hipMemcpyAsync(dV.p, V, (size_t)nV * N * sizeof(double), hipMemcpyHostToDevice, st));
-    DFTA_HIP(ctx, upload(dE, sE, st));
-    DFTA_HIP(ctx, upload(dLim, sLim, st));
-    DFTA_HIP(ctx, upload(dSlotV, G.slot_v, st));
-    DFTA_HIP(ctx, upload(dSlotL, G.slot_l, st));
-    DFTA_HIP(ctx, upload(dBs, G.blk_slot, st));
-    DFTA_HIP(ctx, upload(dBf, G.blk_first, st));
-    DFTA_HIP(ctx, upload(dBc, G.blk_cnt, st));
-    DFTA_HIP(ctx, dTab.alloc(G.slot_v.size() * (size_t)N));
-    DFTA_HIP(ctx, dCount.alloc(ntrials));
-    DFTA_HIP(ctx, dTrip.alloc(ntrials));
-    DFTA_HIP(ctx, dU0.alloc(ntrials));
-    if (boundary == DFTA_BOUNDARY_HOST) {
-        DFTA_HIP(ctx, upload(dStart, sStart, st));
-        DFTA_HIP(ctx, upload(dUs, sUs, st));
-        DFTA_HIP(ctx, upload(dUs1, sUs1, st));
-    } else {
-        DFTA_HIP(ctx, dStart.alloc(ntrials));
-        DFTA_HIP(ctx, dUs.alloc(ntrials));
-        DFTA_HIP(ctx, dUs1.alloc(ntrials));
-        int rc = dfta_launch_boundary(ctx, g, dE.p, ntrials, dStart.p, dUs.p, dUs1.p);
-        if (rc) return rc;
-    }
-    DevBuf<double2> dBounds;
-    DFTA_HIP(ctx, dBounds.alloc(G.slot_v.size() * (size_t)dfta_bounds_stride(g)));
-    int rc = dfta_launch_build_tab(ctx, g, dTab.p, dV.p, dSlotV.p, dSlotL.p, (int)G.slot_v.size(), dBounds.p);
-    if (rc) return rc;
-    DFTA_HIP(ctx, hipEventRecord(ctx->ev[0], st));
-    rc = dfta_launch_sweep(ctx, g, kind, nullptr, (int)G.blk_slot.size(), dTab.p, dBs.p, dBf.p, dBc.p, dE.p, dLim.p, dStart.p,
-                           dUs.p, dUs1.p, dCount.p, dU0.p, dTrip.p, nullptr, dBounds.p, nullptr, nullptr, dSlotL.p);
-    if (rc) return rc;
-    DFTA_HIP(ctx, hipEventRecord(ctx->ev[1], st));
-    ctx->have_kernel_time = true;
-    std::vector<int> hCount(ntrials), hTrip(ntrials), hStart(ntrials);
-    std::vector<double> hU0(ntrials);
-    DFTA_HIP(ctx, hipMemcpyAsync(hCount.data(), dCount.p, ntrials * sizeof(int), hipMemcpyDeviceToHost, st));
-    DFTA_HIP(ctx, hipMemcpyAsync(hTrip.data(), dTrip.p, ntrials * sizeof(int), hipMemcpyDeviceToHost, st));
-    DFTA_HIP(ctx, hipMemcpyAsync(hStart.data(), dStart.p, ntrials * sizeof(int), hipMemcpyDeviceToHost, st));
-    DFTA_HIP(ctx, hipMemcpyAsync(hU0.data(), dU0.p, ntrials * sizeof(double), hipMemcpyDeviceToHost, st));
-    DFTA_HIP(ctx, hipStreamSynchronize(st));
-    for (int s = 0; s < ntrials; ++s) {
-        const int t = G.order[s];
-        if (count_out && kind == DFTA_SWEEP_COUNT) count_out[t] = hCount[s];
-        if (u0_out) u0_out[t] = hU0[s];
-        if (start_out) start_out[t] = hStart[s];
-        if (trip_out) trip_out[t] = hTrip[s];
-    }
-    return DFTA_OK;
-}
-
-extern "C" int dfta_numerov_sweeps_dev(dfta_ctx* ctx, const dfta_grid* g, int kind, int nV, const double* dV, int ngroups,
-                                       const int* group_off, const int* group_vidx, const int* group_l, const double* dE,
-                                       const int* dLimit, const int* dStart, const double* dUs, const double* dUs1,
-                                       int* dCount, double* dU0, int* dStartOut, int* dTrip)
-{
-    if (!ctx || !g) return DFTA_ERR_INVALID;
-    DFTA_ENTER(ctx);
-    DFTA_REQUIRE(ctx, dV && group_off && group_vidx && group_l && dE && ngroups > 0, "null input");
-    const int N = g->N;
-    const int ntrials = group_off[ngroups];
-    std::vector<int> slot_v(group_vidx, group_vidx + ngroups), slot_l(group_l, group_l + ngroups), bs, bf, bc;
-    for (int k = 0; k < ngroups; ++k) {
-        DFTA_REQUIRE(ctx, slot_v[k] >= 0 && slot_v[k] < nV && slot_l[k] >= 0 && slot_l[k] <= 3, "group vidx/l");
-        for (int s = group_off[k]; s < group_off[k + 1]; s += 64) {
-            bs.push_back(k); bf.push_back(s); bc.push_back(std::min(64, group_off[k + 1] - s));
-        }
-    }
-    hipStream_t st = ctx->stream;
-    DevBuf<int> dSlotV, dSlotL, dBs, dBf, dBc, dSt;
-    DevBuf<double> dA, dB;
-    DevBuf<double2> dTab;
-    DFTA_HIP(ctx, upload(dSlotV, slot_v, st));
-    DFTA_HIP(ctx, upload(dSlotL, slot_l, st));
-    DFTA_HIP(ctx, upload(dBs, bs, st));
-    DFTA_HIP(ctx, upload(dBf, bf, st));
-    DFTA_HIP(ctx, upload(dBc, bc, st));
-    DFTA_HIP(ctx, dTab.alloc((size_t)ngroups * N));
-    const int* pStart = dStart;
-    const double *pUs = dUs, *pUs1 = dUs1;
-    if (!dStart || !dUs || !dUs1) {
-        DFTA_HIP(ctx, dSt.alloc(ntrials));
-        DFTA_HIP(ctx, dA.alloc(ntrials));
-        DFTA_HIP(ctx, dB.alloc(ntrials));
-        int rc = dfta_launch_boundary(ctx, g, dE, ntrials, dSt.p, dA.p, dB.p);
-        if (rc) return rc;
-        pStart = dSt.p; pUs = dA.p; pUs1 = dB.p;
-    }
-    DevBuf<double2> dBounds;
-    DFTA_HIP(ctx, dBounds.alloc((size_t)ngroups * dfta_bounds_stride(g)));
-    int rc = dfta_launch_build_tab(ctx, g, dTab.p, dV, dSlotV.p, dSlotL.p, ngroups, dBounds.p);
-    if (rc) return rc;
-    rc = dfta_launch_sweep(ctx, g, kind, nullptr, (int)bs.size(), dTab.p, dBs.p, dBf.p, dBc.p, dE, dLimit, pStart, pUs, pUs1, dCount,
-                           dU0, dTrip, nullptr, dBounds.p, nullptr, nullptr, dSlotL.p);
-    if (rc) return rc;
-    if (dStartOut) DFTA_HIP(ctx, hipMemcpyAsync(dStartOut, pStart, ntrials * sizeof(int), hipMemcpyDeviceToDevice, st));
-    DFTA_HIP(ctx, hipStreamSynchronize(st));   // scratch buffers die with this scope
-    return DFTA_OK;
-}
-
-extern "C" int dfta_numerov_match(dfta_ctx* ctx, const dfta_grid* g, int boundary, int nV, const double* V, int ntrials,
-                                  const int* vidx, const int* l, const double* E, double* Psi_out, long* matchPoint_out)
-{
-    if (!ctx || !g) return DFTA_ERR_INVALID;
-    DFTA_ENTER(ctx);
-    DFTA_REQUIRE(ctx, V && l && E && Psi_out && matchPoint_out && nV > 0 && ntrials >= 0, "null input");
-    if (ntrials == 0) return DFTA_OK;
-    const int N = g->N;
-    Grouping G;
-    if (make_grouping(ntrials, vidx, l, nV, G) != DFTA_OK) { snprintf(ctx->err, sizeof(ctx->err), "invalid vidx/l"); return DFTA_ERR_INVALID; }
-    std::vector<double> sE(ntrials), sUs(ntrials), sUs1(ntrials), sUz(ntrials, 0.0);
-    std::vector<int> sStart(ntrials), sL(ntrials);
-    for (int s = 0; s < ntrials; ++s) {
-        const int t = G.order[s];
-        sE[s] = E[t];
-        sL[s] = l[t];
-        if (boundary == DFTA_BOUNDARY_HOST) {
-            if (g->uniform) host_boundary_uniform(g, E[t], static_cast<unsigned>(l[t]), true, &sStart[s], &sUs[s], &sUs1[s], &sUz[s]);
-            else host_boundary(g, E[t], &sStart[s], &sUs[s], &sUs1[s]);
-        }
-    }
-    hipStream_t st = ctx->stream;
-    DevBuf<double> dV, dE, dUs, dUs1, dPsi, dQ, dUz;
-    DevBuf<int> dStart, dSlotV, dSlotL, dTs, dL, dMp;
-    DevBuf<double2> dTab;
-    DFTA_HIP(ctx, dV.alloc((size_t)nV * N));
-    DFTA_HIP(ctx, hipMemcpyAsync(dV.p, V, (size_t)nV * N * sizeof(double), hipMemcpyHostToDevice, st));
-    DFTA_HIP(ctx, upload(dE, sE, st));
-    DFTA_HIP(ctx, upload(dL, sL, st));
-    DFTA_HIP(ctx, upload(dSlotV, G.slot_v, st));
-    DFTA_HIP(ctx, upload(dSlotL, G.slot_l, st));
-    DFTA_HIP(ctx, upload(dTs, G.trial_slot, st));
-    DFTA_HIP(ctx, dTab.alloc(G.slot_v.size() * (size_t)N));
-    DFTA_HIP(ctx, dPsi.alloc((size_t)ntrials * N));
-    DFTA_HIP(ctx, dQ.alloc((size_t)ntrials * N));
-    DFTA_HIP(ctx, dMp.alloc(ntrials));
-    if (boundary == DFTA_BOUNDARY_HOST) {
-        DFTA_HIP(ctx, upload(dStart, sStart, st));
-        DFTA_HIP(ctx, upload(dUs, sUs, st));
-        DFTA_HIP(ctx, upload(dUs1, sUs1, st));
-        DFTA_HIP(ctx, upload(dUz, sUz, st));
-    } else {
-        DFTA_HIP(ctx, dStart.alloc(ntrials));
-        DFTA_HIP(ctx, dUs.alloc(ntrials));
-        DFTA_HIP(ctx, dUs1.alloc(ntrials));
-        DFTA_HIP(ctx, dUz.alloc(ntrials));
-        int rc = dfta_launch_boundary(ctx, g, dE.p, ntrials, dStart.p, dUs.p, dUs1.p, 1, dL.p, dUz.p);
-        if (rc) return rc;
-    }
-    DevBuf<double2> dBounds;
-    DFTA_HIP(ctx, dBounds.alloc(G.slot_v.size() * (size_t)dfta_bounds_stride(g)));
-    int rc = dfta_launch_build_tab(ctx, g, dTab.p, dV.p, dSlotV.p, dSlotL.p, (int)G.slot_v.size(), dBounds.p);
-    if (rc) return rc;
-    rc = dfta_launch_match(ctx, g, ntrials, dTab.p, dTs.p, dE.p, dStart.p, dUs.p, dUs1.p, dL.p, dPsi.p, dQ.p, dMp.p, g->uniform ? nullptr : dBounds.p,
-                           dUz.p);
-    if (rc) return rc;
-    std::vector<double> hPsi((size_t)ntrials * N);
-    std::vector<int> hMp(ntrials);
-    DFTA_HIP(ctx, hipMemcpyAsync(hPsi.data(), dPsi.p, hPsi.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-    DFTA_HIP(ctx, hipMemcpyAsync(hMp.data(), dMp.p, ntrials * sizeof(int), hipMemcpyDeviceToHost, st));
-    DFTA_HIP(ctx, hipStreamSynchronize(st));
-    for (int s = 0; s < ntrials; ++s) {
-        const int t = G.order[s];
-        memcpy(Psi_out + (size_t)t * N, hPsi.data() + (size_t)s * N, sizeof(double) * N);
-        matchPoint_out[t] = hMp[s];
-    }
-    return DFTA_OK;
-}
-
-// ---- a potential resident on the device (include/dftatom_hip.h: dfta_potential) -------------------------------------------------
-// The reference's Numerov holds a REFERENCE to the caller's Potential and re-reads it on every call (Numerov.h:69,186); its L3 makes
-// ~2100 calls on one Numerov object per SCF step.  dfta_numerov_sweeps re-uploads the 1 MB potential and rebuilds the slot table on each
-// of them (0.8 ... 6 ms per call); here both are done once per potential, and a call costs its sweep.
-struct dfta_potential {
-    dfta_ctx* ctx = nullptr;
-    const dfta_grid* g = nullptr;
-    std::vector<double> h_V;
-    DevBuf<double> dV;
-    DevBuf<double2> dTab;           // 4 slots: l = 0..3
-    DevBuf<double2> dBounds;
-    DevBuf<int> dSlots;             // slot_v (4 zeros), slot_l (0..3)
-    dfta_scan_tables scan;          // tolerance mode: built on first use
-    bool scan_built = false;
-    // per-call scratch, grown on demand: one staging block in, one out
-    size_t cap = 0;
-    DevBuf<char> dIn, dOut;
-    std::vector<char> hIn, hOut;
-    DevBuf<double> dPsi, dQ;
-    size_t psi_cap = 0;
-};
-
-namespace {
-int potential_build(dfta_potential* p)
-{
-    dfta_ctx* ctx = p->ctx;
-    const int N = p->g->N;
-    DFTA_HIP(ctx, hipMemcpyAsync(p->dV, p->h_V.data(), sizeof(double) * N, hipMemcpyHostToDevice, ctx->stream));
-    int rc = dfta_launch_build_tab(ctx, p->g, p->dTab, p->dV, p->dSlots, p->dSlots + 4, 4, p->dBounds);
-    if (rc) return rc;
-    if (p->scan_built) rc = dfta_launch_scan_build_tab(ctx, p->g, p->scan, p->dV, p->dSlots, p->dSlots + 4);
-    return rc;
-}
-int potential_scratch(dfta_potential* p, int ntrials)
-{
-    dfta_ctx* ctx = p->ctx;
-    const size_t need = (size_t)std::max(ntrials, 64) * 64;      // 64 bytes per trial either way
-    if (need <= p->cap) return DFTA_OK;
-    p->dIn.reset(); p->dOut.reset(); p->cap = 0;
-    DFTA_HIP(ctx, p->dIn.alloc(need));
-    DFTA_HIP(ctx, p->dOut.alloc(need));
-    p->hIn.resize(need); p->hOut.resize(need);
-    p->cap = need;
     return DFTA_OK;
 }
 }  // namespace
 
-extern "C" void dfta_potential_destroy(dfta_potential* p)
+int dfta_launch_levels_persist(dfta_ctx* ctx, const dfta_grid* g, dfta_persist_buffers* pb, dfta::Job* jobs, const int* live, int nlive,
+                               const SlotTables& tables, const PersistRun& run, PersistResult* out)
 {
-    delete p;
-}
-
-extern "C" int dfta_potential_create(dfta_ctx* ctx, const dfta_grid* g, const double* V, dfta_potential** out)
-{
-    if (!ctx || !g || !V || !out) return DFTA_ERR_INVALID;
-    DFTA_ENTER(ctx);
-    const int N = g->N;
-    std::unique_ptr<dfta_potential> p(new dfta_potential());
-    p->ctx = ctx; p->g = g;
-    p->h_V.assign(V, V + N);
-    hipError_t e = p->dV.alloc(N);
-    if (e == hipSuccess) e = p->dTab.alloc(4 * (size_t)N);
-    if (e == hipSuccess) e = p->dBounds.alloc(4 * (size_t)dfta_bounds_stride(g));
-    if (e == hipSuccess) e = p->dSlots.alloc(8);
-    const int slots[8] = {0, 0, 0, 0, 0, 1, 2, 3};
-    if (e == hipSuccess) e = hipMemcpy(p->dSlots, slots, sizeof(slots), hipMemcpyHostToDevice);
-    if (e != hipSuccess) { snprintf(ctx->err, sizeof(ctx->err), "dfta_potential_create: %s", hipGetErrorString(e)); return DFTA_ERR_HIP; }
-    const int rc = potential_build(p.get());
+    out->aborted = 0;
+    if (nlive < 1 || nlive > pb->nlive_cap || g->uniform) return DFTA_ERR_INVALID;
+    dfta_nh::PersistPlan plan;
+    if (dfta_nh::plan_persist(pb->nblocks, nlive, run.share, &plan) != DFTA_OK) return DFTA_ERR_INVALID;
+    int rc = persist_upload_constants(ctx, run.tuning, run.fixed_point);
+    if (!rc) rc = persist_upload_ctl(ctx, pb, live, nlive, plan);
     if (rc) return rc;
-    *out = p.release();
-    return DFTA_OK;
-}
-
-extern "C" int dfta_potential_update(dfta_potential* p, const double* V)
-{
-    if (!p || !V) return DFTA_ERR_INVALID;
-    DFTA_ENTER(p->ctx);
-    if (memcmp(V, p->h_V.data(), sizeof(double) * p->g->N) == 0) return DFTA_OK;      // what the reference would re-read is what is resident
-    DFTA_HIP(p->ctx, hipStreamSynchronize(p->ctx->stream));                            // h_V may still be the source of a copy
-    p->h_V.assign(V, V + p->g->N);
-    return potential_build(p);
-}
-
-extern "C" int dfta_potential_sweeps(dfta_potential* p, int kind, int sweep_mode, int ntrials, const int* l, const double* E, const int* nodesLimit,
-                                     int* count_out, double* u0_out, int* start_out, int* trip_out)
-{
-    if (!p) return DFTA_ERR_INVALID;
-    dfta_ctx* ctx = p->ctx;
-    const dfta_grid* g = p->g;
-    DFTA_ENTER(ctx);
-    DFTA_REQUIRE(ctx, l && E && ntrials >= 0, "null input");
-    DFTA_REQUIRE(ctx, kind == DFTA_SWEEP_COUNT || kind == DFTA_SWEEP_ZERO, "kind");
-    DFTA_REQUIRE(ctx, kind != DFTA_SWEEP_COUNT || (nodesLimit && count_out), "COUNT needs nodesLimit and count_out");
-    DFTA_REQUIRE(ctx, kind != DFTA_SWEEP_ZERO || u0_out, "ZERO needs u0_out");
-    DFTA_REQUIRE(ctx, sweep_mode == DFTA_SWEEPS_EXACT || (sweep_mode == DFTA_SWEEPS_TOLERANCE && dfta_scan_supported(g)), "sweep mode / grid");
-    if (ntrials == 0) return DFTA_OK;
-    hipStream_t st = ctx->stream;
-    int rc = potential_scratch(p, ntrials);
-    if (rc) return rc;
-    // staging block in: E, us, us1 (doubles), then limit, start, blk_slot, blk_first, blk_cnt / trial_slot (ints): one copy each way
-    const size_t nt = ntrials;
-    double* hE = reinterpret_cast<double*>(p->hIn.data());
-    double *hUs = hE + nt, *hUs1 = hUs + nt;
-    int* hLim = reinterpret_cast<int*>(hUs1 + nt);
-    int *hStart = hLim + nt, *hBs = hStart + nt, *hBf = hBs + nt, *hBc = hBf + nt;
-    double* dE = reinterpret_cast<double*>(p->dIn.p);
-    double *dUs = dE + nt, *dUs1 = dUs + nt;
-    int* dLim = reinterpret_cast<int*>(dUs1 + nt);
-    int *dStart = dLim + nt, *dBs = dStart + nt, *dBf = dBs + nt, *dBc = dBf + nt;
-    double* dU0 = reinterpret_cast<double*>(p->dOut.p);
-    int* dCount = reinterpret_cast<int*>(dU0 + nt);
-    int *dTrip = dCount + nt, *dStartOut = dTrip + nt, *dBad = dStartOut + nt;
-    if (sweep_mode == DFTA_SWEEPS_TOLERANCE) {
-        if (!p->scan_built) {
-            rc = dfta_scan_tables_create(ctx, g, 4, &p->scan);
-            if (rc) return rc;
-            p->scan_built = true;
-            rc = dfta_launch_scan_build_tab(ctx, g, p->scan, p->dV, p->dSlots, p->dSlots + 4);
-            if (rc) return rc;
-        }
-        for (size_t t = 0; t < nt; ++t) {
-            DFTA_REQUIRE(ctx, l[t] >= 0 && l[t] <= 3, "l");
-            hE[t] = E[t]; hLim[t] = nodesLimit ? nodesLimit[t] : 0; hBs[t] = l[t];
-        }
-        DFTA_HIP(ctx, hipMemcpyAsync(p->dIn, p->hIn.data(), nt * 64, hipMemcpyHostToDevice, st));
-        DFTA_HIP(ctx, hipEventRecord(ctx->ev[0], st));
-        rc = dfta_launch_scan_sweeps(ctx, g, kind, ntrials, p->scan, dBs, dE, dLim, dCount, dU0, dStartOut, dTrip, dBad);
-        if (rc) return rc;
-        DFTA_HIP(ctx, hipEventRecord(ctx->ev[1], st));
-        ctx->have_kernel_time = true;
-        DFTA_HIP(ctx, hipMemcpyAsync(p->hOut.data(), p->dOut, nt * 64, hipMemcpyDeviceToHost, st));
-        DFTA_HIP(ctx, hipStreamSynchronize(st));
-        const double* oU0 = reinterpret_cast<const double*>(p->hOut.data());
-        const int* oCount = reinterpret_cast<const int*>(oU0 + nt);
-        const int *oTrip = oCount + nt, *oStart = oTrip + nt, *oBad = oStart + nt;
-        bool anybad = false;
-        for (size_t t = 0; t < nt; ++t) {
-            anybad = anybad || oBad[t];
-            if (count_out && kind == DFTA_SWEEP_COUNT) count_out[t] = oCount[t];
-            if (u0_out) u0_out[t] = oU0[t];
-            if (start_out) start_out[t] = oStart[t];
-            if (trip_out) trip_out[t] = oTrip[t];
-        }
-        if (!anybad) return DFTA_OK;
-        // a trial the scan could not decide: the whole call again on the exact kernels
-    }
-    Grouping G;
-    if (make_grouping(ntrials, nullptr, l, 1, G) != DFTA_OK) { snprintf(ctx->err, sizeof(ctx->err), "invalid l"); return DFTA_ERR_INVALID; }
-    for (size_t s = 0; s < nt; ++s) {
-        const int t = G.order[s];
-        hE[s] = E[t];
-        hLim[s] = nodesLimit ? nodesLimit[t] : 0;
-        if (g->uniform) host_boundary_uniform(g, E[t], static_cast<unsigned>(l[t]), false, &hStart[s], &hUs[s], &hUs1[s], nullptr);
-        else host_boundary(g, E[t], &hStart[s], &hUs[s], &hUs1[s]);
-    }
-    const size_t nb = G.blk_slot.size();
-    for (size_t b = 0; b < nb; ++b) { hBs[b] = G.slot_l[G.blk_slot[b]]; hBf[b] = G.blk_first[b]; hBc[b] = G.blk_cnt[b]; }    // table slot = l
-    DFTA_HIP(ctx, hipMemcpyAsync(p->dIn, p->hIn.data(), nt * 64, hipMemcpyHostToDevice, st));
-    DFTA_HIP(ctx, hipEventRecord(ctx->ev[0], st));
-    rc = dfta_launch_sweep(ctx, g, kind, nullptr, (int)nb, p->dTab, dBs, dBf, dBc, dE, dLim, dStart, dUs, dUs1, dCount, dU0, dTrip, nullptr, p->dBounds, nullptr,
-                           nullptr, p->dSlots + 4);
-    if (rc) return rc;
-    DFTA_HIP(ctx, hipEventRecord(ctx->ev[1], st));
-    ctx->have_kernel_time = true;
-    DFTA_HIP(ctx, hipMemcpyAsync(p->hOut.data(), p->dOut, nt * 64, hipMemcpyDeviceToHost, st));
-    DFTA_HIP(ctx, hipStreamSynchronize(st));
-    const double* oU0 = reinterpret_cast<const double*>(p->hOut.data());
-    const int* oCount = reinterpret_cast<const int*>(oU0 + nt);
-    const int* oTrip = oCount + nt;
-    for (size_t s = 0; s < nt; ++s) {
-        const int t = G.order[s];
-        if (count_out && kind == DFTA_SWEEP_COUNT) count_out[t] = oCount[s];
-        if (u0_out) u0_out[t] = oU0[s];
-        if (start_out) start_out[t] = hStart[s];
-        if (trip_out) trip_out[t] = oTrip[s];
-    }
-    return DFTA_OK;
-}
-
-extern "C" int dfta_potential_match(dfta_potential* p, int ntrials, const int* l, const double* E, double* Psi_out, long* matchPoint_out)
-{
-    if (!p) return DFTA_ERR_INVALID;
-    dfta_ctx* ctx = p->ctx;
-    const dfta_grid* g = p->g;
-    DFTA_ENTER(ctx);
-    DFTA_REQUIRE(ctx, l && E && Psi_out && matchPoint_out && ntrials >= 0, "null input");
-    if (ntrials == 0) return DFTA_OK;
-    const int N = g->N;
-    hipStream_t st = ctx->stream;
-    int rc = potential_scratch(p, ntrials);
-    if (rc) return rc;
-    if ((size_t)ntrials > p->psi_cap) {
-        p->dPsi.reset(); p->dQ.reset(); p->psi_cap = 0;
-        DFTA_HIP(ctx, p->dPsi.alloc((size_t)ntrials * N));
-        DFTA_HIP(ctx, p->dQ.alloc((size_t)ntrials * N));
-        p->psi_cap = ntrials;
-    }
-    const size_t nt = ntrials;
-    double* hE = reinterpret_cast<double*>(p->hIn.data());
-    double *hUs = hE + nt, *hUs1 = hUs + nt, *hUz = hUs1 + nt;
-    int* hStart = reinterpret_cast<int*>(hUz + nt);
-    int *hL = hStart + nt, *hTs = hL + nt;
-    double* dE = reinterpret_cast<double*>(p->dIn.p);
-    double *dUs = dE + nt, *dUs1 = dUs + nt, *dUz = dUs1 + nt;
-    int* dStart = reinterpret_cast<int*>(dUz + nt);
-    int *dL = dStart + nt, *dTs = dL + nt;
-    int* dMp = reinterpret_cast<int*>(p->dOut.p);
-    for (size_t t = 0; t < nt; ++t) {
-        DFTA_REQUIRE(ctx, l[t] >= 0 && l[t] <= 3, "l");
-        hE[t] = E[t]; hL[t] = l[t]; hTs[t] = l[t]; hUz[t] = 0;
-        if (g->uniform) host_boundary_uniform(g, E[t], static_cast<unsigned>(l[t]), true, &hStart[t], &hUs[t], &hUs1[t], &hUz[t]);
-        else host_boundary(g, E[t], &hStart[t], &hUs[t], &hUs1[t]);
-    }
-    DFTA_HIP(ctx, hipMemcpyAsync(p->dIn, p->hIn.data(), nt * 64, hipMemcpyHostToDevice, st));
-    rc = dfta_launch_match(ctx, g, ntrials, p->dTab, dTs, dE, dStart, dUs, dUs1, dL, p->dPsi, p->dQ, dMp, g->uniform ? nullptr : p->dBounds, dUz);
-    if (rc) return rc;
-    DFTA_HIP(ctx, hipMemcpyAsync(Psi_out, p->dPsi, sizeof(double) * nt * N, hipMemcpyDeviceToHost, st));
-    DFTA_HIP(ctx, hipMemcpyAsync(p->hOut.data(), dMp, sizeof(int) * nt, hipMemcpyDeviceToHost, st));
-    DFTA_HIP(ctx, hipStreamSynchronize(st));
-    for (size_t t = 0; t < nt; ++t) matchPoint_out[t] = reinterpret_cast<const int*>(p->hOut.data())[t];
-    return DFTA_OK;
+    SweepTrials st = pb->trials().sweep();
+    if (!run.stats) st.trip = nullptr;
+    const SweepArgs a = sweep_args(g, DFTA_SWEEP_COUNT, tables, pb->blocks().view(), st, run.stats ? run.counters + 1 : nullptr);
+    return persist_launch(ctx, pb, a, scalars_of(g), persist_args(g, pb, jobs, run), run.want_trace, out);
 }
 
 #ifdef DFTA_PIPE_PROF
