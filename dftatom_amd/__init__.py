@@ -33,6 +33,8 @@ RECORD_DOUBLES = 64
 # columns of an orbital-property row (DFTA_ORB_*): NORM, <1/r>, <r>, <r^2>, <r^4>, T, r at the largest |u|, <1/r^3> (l >= 1, else 0)
 ORB_PROPS = 8
 ORB_NORM, ORB_RM1, ORB_R1, ORB_R2, ORB_R4, ORB_T, ORB_RPEAK, ORB_RM3 = range(8)
+SLATER_KMAX = 8                        # DFTA_SLATER_KMAX: largest k of a Slater integral R^k
+SLATER_F, SLATER_G = 0, 1              # kinds of slater_fg_jobs
 
 c_dp = C.POINTER(C.c_double)
 c_ip = C.POINTER(C.c_int)
@@ -157,6 +159,12 @@ SIGNATURES = {
     "dfta_scf_orbital_matrix": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, c_dp]),
     "dfta_orbital_properties": (C.c_int, [vp, vp, C.c_int, c_ip, c_dp, c_dp]),
     "dfta_orbital_matrix": (C.c_int, [vp, vp, C.c_int, c_dp, C.c_int, c_dp]),
+    "dfta_gaunt_3j2": (C.c_int, [C.c_int, C.c_int, C.c_int, c_dp]),
+    "dfta_slater_fg_jobs": (C.c_int, [C.c_int, c_ip, c_ip, c_ip]),
+    "dfta_slater_rk": (C.c_int, [vp, vp, C.c_int, c_dp, C.c_int, c_ip, c_dp]),
+    "dfta_scf_slater_rk": (C.c_int, [vp, C.c_int, C.c_int, c_ip, c_dp]),
+    "dfta_scf_slater_fg": (C.c_int, [vp, C.c_int, C.c_int, c_dp, c_dp]),
+    "dfta_scf_coulomb_exchange": (C.c_int, [vp, C.c_int, c_dp, c_dp]),
 }
 
 _lib = None
@@ -581,6 +589,37 @@ def orbital_matrix(ctx, grid, u, k):
     return M
 
 
+def gaunt_3j2(la, k, lb):
+    """(la k lb; 0 0 0)^2, the angular factor of the exchange sum (host-only; 0.0 where parity or the triangle rule fails)"""
+    out = C.c_double()
+    if load().dfta_gaunt_3j2(int(la), int(k), int(lb), C.byref(out)) != OK:
+        raise DftaError("dfta_gaunt_3j2(%d, %d, %d): arguments must be >= 0 and la, lb <= 4" % (la, k, lb))
+    return out.value
+
+
+def slater_fg_jobs(l):
+    """dfta_slater_fg_jobs (host-only): (jobs, kinds) for orbitals of angular momenta l -- jobs (njobs, 5) int32 rows a, b, c, d, k,
+    first the F^k(a,b) (a <= b, kinds SLATER_F), then the G^k(a,b) (a < b, SLATER_G)"""
+    lib = load()
+    l = _i32(np.atleast_1d(l))
+    n = lib.dfta_slater_fg_jobs(len(l), _ip(l), None, None)
+    if n < 0:
+        raise DftaError("dfta_slater_fg_jobs: angular momenta must lie in 0 .. 4")
+    jobs, kinds = np.zeros((n, 5), np.int32), np.zeros(n, np.int32)
+    lib.dfta_slater_fg_jobs(len(l), _ip(l), _ip(jobs), _ip(kinds))
+    return jobs, kinds
+
+
+def slater_rk(ctx, grid, u, jobs):
+    """dfta_slater_rk: the Slater integrals R^k(ab,cd) of the rows (a, b, c, d, k) of jobs over orbitals u = r R of shape (norb, N),
+    every job in one launch: (njobs,).  F^k(a,b) = R^k(ab,ab), G^k(a,b) = R^k(ab,ba); 0 <= k <= SLATER_KMAX."""
+    u = _f64(u).reshape(-1, grid.N)
+    jobs = _i32(jobs).reshape(-1, 5)
+    R = np.zeros(len(jobs))
+    ctx.check(ctx.lib.dfta_slater_rk(ctx.h, grid.h, u.shape[0], _dp(u), len(jobs), _ip(jobs), _dp(R)))
+    return R
+
+
 class Mixer:
     """The SCF's density-mixing stage on its own (dfta_mixer): the launches dfta_scf_step issues for `mixing`, on the caller's arrays."""
 
@@ -732,6 +771,29 @@ class Scf:
         M = np.zeros((cnt, cnt))
         self.ctx.check(self.ctx.lib.dfta_scf_orbital_matrix(self.h, int(atom), int(spin), int(k), _dp(M)))
         return M
+
+    def slater_rk(self, atom, jobs):
+        """R^k(ab,cd) of the rows (a, b, c, d, k) of jobs over the orbitals of `atom`, read in place; indices count the atom's rows
+        of orbital_jobs(): alpha levels, then beta levels (a cross-spin F^0 is a job like any other)"""
+        jobs = _i32(jobs).reshape(-1, 5)
+        R = np.zeros(len(jobs))
+        self.ctx.check(self.ctx.lib.dfta_scf_slater_rk(self.h, int(atom), len(jobs), _ip(jobs), _dp(R)))
+        return R
+
+    def slater_fg(self, atom=0, spin=0):
+        """(F, G), each (SLATER_KMAX + 1, nlev, nlev): F^k(a,b) and G^k(a,b) of the levels of (atom, spin) from one launch, symmetric
+        bit for bit, G^k(a,a) = F^k(a,a), 0.0 where slater_fg_jobs has no job"""
+        cnt = max(self.ctx.lib.dfta_scf_num_levels(self.h, atom, spin), 0)
+        F, G = np.zeros((SLATER_KMAX + 1, cnt, cnt)), np.zeros((SLATER_KMAX + 1, cnt, cnt))
+        self.ctx.check(self.ctx.lib.dfta_scf_slater_fg(self.h, int(atom), int(spin), _dp(F), _dp(G)))
+        return F, G
+
+    def coulomb_exchange(self, atom=0):
+        """(E_H, E_x): the Hartree energy and the exact-exchange energy of the atom's orbitals and occupations (spherically averaged;
+        include/dftatom_hip.h has the sums), from one launch"""
+        eh, ex = C.c_double(), C.c_double()
+        self.ctx.check(self.ctx.lib.dfta_scf_coulomb_exchange(self.h, int(atom), C.byref(eh), C.byref(ex)))
+        return eh.value, ex.value
 
     def set_integrator(self, rule):
         """INT_TRAPEZOID .. INT_ROMBERG: quadrature of the energy integrals and of the orbitals' normalisation."""

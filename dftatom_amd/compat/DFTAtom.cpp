@@ -21,6 +21,7 @@ int DFTAtom::poissonMode = -1;      // as dfta_poisson_create: exact unless $DFT
 int DFTAtom::mixing = DFTA_MIX_LINEAR;     // --mixing=anderson: Anderson density mixing, default history and warm-up
 std::ostream* DFTAtom::jsonOut = nullptr;
 bool DFTAtom::orbitalTable = false;        // --orbital-table
+bool DFTAtom::slaterTable = false;         // --slater-table
 
 namespace {
 struct LevelLine { int n, l; double occ, E; int status, n_count, n_zero; };
@@ -102,6 +103,35 @@ void print_orbital_table(dfta_scf* scf, bool lsda)
     std::cout << std::endl;
 }
 
+// --slater-table: one line per F^k / G^k of each channel's table (dfta_scf_slater_fg: one launch per channel), then the Hartree and
+// exact-exchange energies of the orbitals (dfta_scf_coulomb_exchange)
+void print_slater_table(dfta_scf* scf, bool lsda)
+{
+    for (int spin = 0; spin < (lsda ? 2 : 1); ++spin) {
+        const std::vector<LevelLine> lv = fetch_levels(scf, spin);
+        const size_t n = lv.size();
+        if (n == 0) continue;
+        std::vector<int> l(n);
+        for (size_t a = 0; a < n; ++a) l[a] = lv[a].l;
+        const int njobs = dfta_slater_fg_jobs(static_cast<int>(n), l.data(), nullptr, nullptr);
+        if (njobs < 0) throw std::runtime_error("dfta_slater_fg_jobs");
+        std::vector<int> jobs(static_cast<size_t>(njobs) * 5), kinds(njobs);
+        dfta_slater_fg_jobs(static_cast<int>(n), l.data(), jobs.data(), kinds.data());
+        std::vector<double> F((DFTA_SLATER_KMAX + 1) * n * n), G((DFTA_SLATER_KMAX + 1) * n * n);
+        if (dfta_scf_slater_fg(scf, 0, spin, F.data(), G.data()) != DFTA_OK) throw std::runtime_error("dfta_scf_slater_fg");
+        for (int j = 0; j < njobs; ++j) {
+            const int a = jobs[5 * j], b = jobs[5 * j + 1], k = jobs[5 * j + 4];
+            const double v = (kinds[j] ? G : F)[(k * n + a) * n + b];
+            std::cout << "Slater " << (lsda ? (spin == 0 ? "alpha " : "beta ") : "") << (kinds[j] ? "G" : "F") << k << "(" << lv[a].n + 1
+                      << DFTAtom::orb[lv[a].l] << "," << lv[b].n + 1 << DFTAtom::orb[lv[b].l] << ") = " << std::fixed << std::setprecision(6) << v
+                      << std::endl;
+        }
+    }
+    double EH = 0, EXX = 0;
+    if (dfta_scf_coulomb_exchange(scf, 0, &EH, &EXX) != DFTA_OK) throw std::runtime_error("dfta_scf_coulomb_exchange");
+    std::cout << "EHartree = " << std::fixed << std::setprecision(6) << EH << " EXX = " << EXX << std::endl << std::endl;
+}
+
 void print_configuration(std::vector<LevelLine> levels)
 {
     // levels sorted by energy for the final configuration line (DFTAtom.cpp:487-490)
@@ -160,6 +190,7 @@ void DFTAtom::Run(bool lsda, bool uniform, int Z, int MultigridLevels, double al
         if (finished) {
             std::cout << std::endl << "Finished!" << std::endl << std::endl;
             if (orbitalTable) print_orbital_table(scf, lsda);
+            if (slaterTable) print_slater_table(scf, lsda);
             break;
         }
         std::cout << "********************************************************************************" << std::endl;

@@ -45,6 +45,9 @@ public:
     static std::ostream* jsonOut;
     // after "Finished!", one line per level: n, l, occupation, E and <r>, <r^2>, T, r_peak of its orbital (dfta_scf_orbital_properties)
     static bool orbitalTable;
+    // after "Finished!" (and the orbital table), one line per F^k / G^k of the levels' Slater integrals, then E_H and the exact-exchange
+    // energy of the orbitals (dfta_scf_slater_fg, dfta_scf_coulomb_exchange)
+    static bool slaterTable;
 
 private:
     static constexpr double fourM_PI = 4. * M_PI;

@@ -14,6 +14,9 @@
 //                phase times) to FILE, or to stderr -- the console protocol on stdout stays the reference's.
 // --orbital-table: after "Finished!", one line per level with n, l, occupation, E and <r>, <r^2>, the kinetic energy T and r_peak of its
 //                orbital (atomic units; include/dftatom_hip.h: dfta_scf_orbital_properties).  Without it the output is unchanged.
+// --slater-table: after "Finished!" (and the orbital table), one line per Slater integral F^k(a,b), G^k(a,b) of the levels (per spin
+//                channel with LSDA), then one line with the Hartree energy and the exact-exchange energy of the orbitals (atomic units;
+//                include/dftatom_hip.h: dfta_scf_slater_fg, dfta_scf_coulomb_exchange).  Without it the output is unchanged.
 // --sweeps=exact|tolerance, --poisson=exact|tolerance|adaptive: the opt-in tolerance modes of the device path (include/dftatom_hip.h).
 // --mixing=linear (default, the reference's density mixing) | anderson (Anderson acceleration: about half the SCF steps, same protocol).
 // --xc=vwn (default, what the reference runs) | chachiyo | chachiyo-improved (LDA only) | pw92 | pbe (logarithmic grid only).
@@ -90,6 +93,8 @@ int main(int argc, char** argv)
             DFT::DFTAtom::jsonOut = &jf;
         } else if (a == "--orbital-table") {
             DFT::DFTAtom::orbitalTable = true;
+        } else if (a == "--slater-table") {
+            DFT::DFTAtom::slaterTable = true;
         } else if (a == "--sweeps=tolerance" || a == "--sweeps=exact") {
             DFT::DFTAtom::sweepMode = a == "--sweeps=tolerance" ? DFTA_SWEEPS_TOLERANCE : DFTA_SWEEPS_EXACT;
         } else if (a == "--poisson=tolerance" || a == "--poisson=adaptive" || a == "--poisson=exact") {
@@ -140,6 +145,7 @@ int main(int argc, char** argv)
                   << "       --xc=vwn (default) | chachiyo | chachiyo-improved | pw92 | pbe\n"
                   << "       --mixing=linear (default) | anderson: Anderson density mixing, fewer SCF steps\n"
                   << "       --orbital-table: after Finished!, one line per level with <r>, <r^2>, T and r_peak of its orbital\n"
+                  << "       --slater-table: after Finished!, the Slater integrals F^k, G^k of the levels, then E_H and the exact-exchange energy\n"
                   << "       --charge=q: the cation (q > 0); --config: an electron configuration, fractional occupations allowed\n";
         return 2;
     }

@@ -189,6 +189,16 @@ int dfta_orbital_scratch_create(dfta_ctx* ctx, const dfta_grid* g, int norb_max,
 // props: norb x DFTA_ORB_PROPS; records the launch's time for dfta_ctx_last_kernel_ms
 int dfta_launch_orbital_properties(dfta_ctx* ctx, const dfta_grid* g, int norb, const int* dL, const double* dU, double* dProps);
 int dfta_launch_orbital_matrix(dfta_ctx* ctx, const dfta_grid* g, int norb, const double* dU, int k, double* dSlab, unsigned* dTicket, double* dM);
+// slater.hip: Slater integrals R^k(ab,cd) of orbitals u = r R (device pointers; jobs: rows a,b,c,d,k, validated by the caller --
+// slater_plan.h: check_jobs); records the launch's time for dfta_ctx_last_kernel_ms
+int dfta_launch_slater_rk(dfta_ctx* ctx, const dfta_grid* g, const double* dU, int njobs, const int* dJobs, double* dR);
+struct dfta_slater_scratch {               // job table and results on the device: empty until the first run, grown as needed
+    int cap = 0;                           // jobs the buffers hold
+    DevBuf<int> d_jobs;
+    DevBuf<double> d_R;
+    // uploads the table (host), launches, copies the njobs results to R (host) and synchronises
+    int run(dfta_ctx* ctx, const dfta_grid* g, const double* dU, int njobs, const int* jobs, double* R);
+};
 // scf.hip: the k_mix launch (DFTA_MIX_LINEAR), same arguments
 int dfta_launch_linear_mix(dfta_ctx* ctx, const dfta_grid* g, int lsda, int natoms, double alpha, double oneMinusAlpha, double* newDensity,
                            double* density, double* dA, double* dB, const int* fin);

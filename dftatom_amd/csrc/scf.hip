@@ -15,6 +15,7 @@
 #include "internal.h"
 #include "levels.h"
 #include "ordered_sum.h"
+#include "slater_plan.h"
 #include "xc.h"
 
 namespace dfta { void config_set_error(const char* msg); }   // ctx_grid.cpp: the text dfta_config_last_error() returns
@@ -273,6 +274,7 @@ struct dfta_scf {
     DevBuf<int> d_orb_l;                  // per job: l
     DevBuf<double> d_orb_props;           // njobs x DFTA_ORB_PROPS
     dfta_orbital_scratch orb_scratch;     // of dfta_scf_orbital_matrix, sized for the longest channel of the batch
+    dfta_slater_scratch slater;           // of the Slater-integral calls (slater.hip): job table and results, made by the first such call
 };
 
 static int scf_xc(dfta_scf* s)
@@ -906,6 +908,80 @@ int dfta_scf_orbital_matrix(dfta_scf* s, int atom, int spin, int k, double* M)
     return DFTA_OK;
 }
 #undef DFTA_SCF_CHANNEL
+
+// ---- Slater integrals of the SCF's orbitals (slater.hip; the orbitals are read in place) ---------------------------------------------
+// first job and number of orbitals of an atom (alpha levels, then beta levels) and their l; the orbitals exist once a step has run
+#define DFTA_SCF_ATOM(s, ctx, atom, k0, norb)                                                                      \
+    DFTA_REQUIRE(ctx, s->steps_done > 0, "no SCF step has run yet: there are no orbitals");                        \
+    DFTA_REQUIRE(ctx, atom >= 0 && atom < s->natoms, "atom");                                                      \
+    DFTA_REQUIRE(ctx, s->g->N >= 5, "Slater integrals need a grid of 5 nodes");                                     \
+    const int k0 = s->h_atoms[atom].job_off, norb = s->spin_nlev[0][atom] + s->spin_nlev[1][atom]
+
+int dfta_scf_slater_rk(dfta_scf* s, int atom, int njobs, const int* jobs, double* R)
+{
+    if (!s) return DFTA_ERR_INVALID;
+    dfta_ctx* ctx = s->ctx;
+    DFTA_ENTER(ctx);
+    DFTA_SCF_ATOM(s, ctx, atom, k0, norb);
+    DFTA_REQUIRE(ctx, njobs >= 0, "njobs");
+    if (njobs == 0) return DFTA_OK;
+    DFTA_REQUIRE(ctx, jobs && R, "jobs / R");
+    if (const char* msg = dfta_slater::check_jobs(norb, njobs, jobs)) DFTA_REQUIRE(ctx, false, msg);
+    return s->slater.run(ctx, s->g, s->solver.d_Psi + (size_t)k0 * s->g->N, njobs, jobs, R);
+}
+
+int dfta_scf_slater_fg(dfta_scf* s, int atom, int spin, double* F, double* G)
+{
+    if (!s) return DFTA_ERR_INVALID;
+    dfta_ctx* ctx = s->ctx;
+    DFTA_ENTER(ctx);
+    DFTA_SCF_ATOM(s, ctx, atom, k0, norb);
+    (void)norb;
+    DFTA_REQUIRE(ctx, spin >= 0 && spin < s->nspin, "spin");
+    const int c0 = k0 + (spin ? s->spin_nlev[0][atom] : 0), cnt = s->spin_nlev[spin][atom];
+    DFTA_REQUIRE(ctx, (F && G) || cnt == 0, "F / G");
+    if (cnt == 0) return DFTA_OK;
+    std::vector<int> l(cnt);
+    for (int a = 0; a < cnt; ++a) l[a] = s->h_jobs[c0 + a].l;
+    const int njobs = dfta_slater::fg_jobs(cnt, l.data(), nullptr, nullptr);
+    DFTA_REQUIRE(ctx, njobs >= 0, "Slater table: an orbital with l > 4");
+    std::vector<int> jobs((size_t)njobs * dfta_slater::kJobInts), kinds(njobs);
+    std::vector<double> R(njobs);
+    dfta_slater::fg_jobs(cnt, l.data(), jobs.data(), kinds.data());
+    const int rc = s->slater.run(ctx, s->g, s->solver.d_Psi + (size_t)c0 * s->g->N, njobs, jobs.data(), R.data());
+    if (rc) return rc;
+    const size_t plane = (size_t)cnt * cnt;
+    std::fill(F, F + (DFTA_SLATER_KMAX + 1) * plane, 0.);
+    std::fill(G, G + (DFTA_SLATER_KMAX + 1) * plane, 0.);
+    for (int j = 0; j < njobs; ++j) {             // each value once, mirrored; G^k(a,a) is F^k(a,a)
+        const int a = jobs[(size_t)j * dfta_slater::kJobInts], b = jobs[(size_t)j * dfta_slater::kJobInts + 1];
+        const int k = jobs[(size_t)j * dfta_slater::kJobInts + 4];
+        double* T = kinds[j] == dfta_slater::kKindF ? F : G;
+        T[k * plane + (size_t)a * cnt + b] = T[k * plane + (size_t)b * cnt + a] = R[j];
+        if (a == b) G[k * plane + (size_t)a * cnt + a] = R[j];
+    }
+    return DFTA_OK;
+}
+
+int dfta_scf_coulomb_exchange(dfta_scf* s, int atom, double* EH, double* EXX)
+{
+    if (!s) return DFTA_ERR_INVALID;
+    dfta_ctx* ctx = s->ctx;
+    DFTA_ENTER(ctx);
+    DFTA_SCF_ATOM(s, ctx, atom, k0, norb);
+    DFTA_REQUIRE(ctx, EH && EXX, "EH / EXX");
+    std::vector<int> l(norb);
+    for (int a = 0; a < norb; ++a) l[a] = s->h_jobs[k0 + a].l;
+    dfta_slater::EnergyPlan plan;
+    DFTA_REQUIRE(ctx, dfta_slater::plan_energy(s->spin_nlev[0][atom], s->spin_nlev[1][atom], l.data(), &plan) == 0,
+                 "exchange energy: an orbital with l > 4");
+    std::vector<double> R(plan.njobs());
+    const int rc = s->slater.run(ctx, s->g, s->solver.d_Psi + (size_t)k0 * s->g->N, plan.njobs(), plan.jobs.data(), R.data());
+    if (rc) return rc;
+    dfta_slater::energy_sums(plan, s->solver.h_occ.data() + k0, s->lsda, R.data(), EH, EXX);
+    return DFTA_OK;
+}
+#undef DFTA_SCF_ATOM
 
 int dfta_scf_get_records_dev(dfta_scf* s, double* dRecords)
 {

@@ -9,6 +9,7 @@ costs nothing more (dfta_scf_step).  The fixed-size result records are gathered 
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 examples/periodic_table.py
     python examples/periodic_table.py --mixing anderson     # Anderson density mixing: about half the SCF steps
     python examples/periodic_table.py --charge 1            # the cations X+ (Z > charge)
+    python examples/periodic_table.py --exx                 # E_H, the exact-exchange energy of the orbitals and the functional's E_xc per atom
     python examples/periodic_table.py --ionization          # IE = E(X+) - E(X): neutral atom and cation of every Z in ONE batch per rank
 """
 import argparse
@@ -47,6 +48,9 @@ def main():
     ap.add_argument("--charge", type=int, default=0, help="ionic charge of every atom (cations: dftatom_amd.ion_config); atoms with Z <= charge are skipped")
     ap.add_argument("--orbitals", action="store_true",
                     help="add <r> and r_peak of every atom's outermost level (the last of its alpha levels) to its row: Scf.orbital_properties()")
+    ap.add_argument("--exx", action="store_true",
+                    help="add the Hartree energy E_H, the exact-exchange (Hartree-Fock) energy of the Kohn-Sham orbitals and the functional's "
+                         "own exchange-correlation energy to every atom's row: Scf.coulomb_exchange()")
     ap.add_argument("--lsda", action="store_true", help="spin-polarised (LSDA) instead of LDA")
     ap.add_argument("--ionization", action="store_true",
                     help="first ionization energies: the neutral atom and the +1 cation of every Z of a rank's shard advance in one batch; "
@@ -144,6 +148,16 @@ def main():
             parts = [None] * world
             dist.all_gather_object(parts, outer)
             outer = {z: v for p in parts for z, v in p.items()}
+    exx = {}
+    if args.exx:                                # one launch per atom: F^0 of all its shell pairs and the G^k of each channel
+        en, _ = scf.energies()
+        for a, z in enumerate(mine):
+            eh, ex = scf.coulomb_exchange(a)
+            exx[int(z)] = {"E_H": eh, "E_x_EXX": ex, "E_xc": en[a].Exc}
+        if world > 1:
+            parts = [None] * world
+            dist.all_gather_object(parts, exx)
+            exx = {z: v for p in parts for z, v in p.items()}
     block = torch.zeros((cap, D.RECORD_DOUBLES), dtype=torch.float64, device="cuda")
     scf.records_into(block.data_ptr())          # rows beyond len(mine) stay zero (Z = 0: no atom)
     ctx.synchronize()
@@ -154,8 +168,10 @@ def main():
         for r in rows:
             ref = NIST_LDA.get(r["Z"])
             o = outer.get(r["Z"])
-            print("Z %3d  Etotal %16.6f  steps %3d  finished %d%s%s" % (r["Z"], r["Etotal"], r["steps"], r["finished"],
+            x = exx.get(r["Z"])
+            print("Z %3d  Etotal %16.6f  steps %3d  finished %d%s%s%s" % (r["Z"], r["Etotal"], r["steps"], r["finished"],
                   "   %d%s <r> %.4f r_peak %.4f" % (o["n"], "spdf"[o["l"]], o["r_mean"], o["r_peak"]) if o else "",
+                  "   E_H %.6f E_x(EXX) %.6f E_xc %.6f" % (x["E_H"], x["E_x_EXX"], x["E_xc"]) if x else "",
                   "   NIST LDA %.6f (diff %.1e)" % (ref, r["Etotal"] - ref) if ref else ""))
         print("%d atoms, %d GPU(s), %d SCF steps of the longest-running atom of rank 0, %d atom-steps in all, %d finished, %.1f s"
               % (len(rows), world, steps, sum(r["steps"] for r in rows), sum(r["finished"] for r in rows), elapsed))
@@ -163,7 +179,8 @@ def main():
             with open(args.out, "w") as f:
                 json.dump({"n_gpus": world, "levels": args.levels, "steps": steps, "seconds": elapsed,
                            "atoms": [dict({"Z": r["Z"], "Etotal": r["Etotal"], "steps": r["steps"], "finished": r["finished"]},
-                                          **({"outermost": outer[r["Z"]]} if r["Z"] in outer else {})) for r in rows]},
+                                          **({"outermost": outer[r["Z"]]} if r["Z"] in outer else {}),
+                                          **({"exx": exx[r["Z"]]} if r["Z"] in exx else {})) for r in rows]},
                           f, indent=1)
     scf.close()
     grid.close()

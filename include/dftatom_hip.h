@@ -449,6 +449,51 @@ int  dfta_scf_orbital_matrix(dfta_scf* s, int atom, int spin, int k, double* M);
 int  dfta_orbital_properties(dfta_ctx* ctx, const dfta_grid* g, int norb, const int* l, const double* u, double* props);
 int  dfta_orbital_matrix(dfta_ctx* ctx, const dfta_grid* g, int norb, const double* u, int k, double* M);
 
+/* ---- Slater integrals R^k, F^k, G^k and the exact-exchange energy of orbitals (beyond the reference) ---------------------------------
+ * With the orbitals u, s_i = dr/di and the quadrature Q[f] of the block above, and P_xy,i = u_x,i u_y,i,
+ *   R^k(ab,cd) = Int Int u_a(r) u_c(r) r_<^k / r_>^(k+1) u_b(r') u_d(r') dr dr'
+ *              = Int r^(-k-1) [P_ac(r) Z^k_bd(r) + P_bd(r) Z^k_ac(r)] dr,   Z^k_xy(r) = Int_0^r t^k P_xy(t) dt
+ * (the regions r' < r and r' > r swapped into one form: forward cumulative integrals only).  What the library computes, node by node:
+ *   g_i = (p_i P_xy,i) s_i with p_i = r_i^k formed as p = 1, then k times p = p * r_i;
+ *   d_1 = (((9 g_0 + 19 g_1) - 5 g_2) + g_3) / 24,  d_i = (13 (g_{i-1} + g_i) - (g_{i-2} + g_{i+1})) / 24 for 2 <= i <= N-2,
+ *   d_{N-1} = (((g_{N-4} - 5 g_{N-3}) + 19 g_{N-2}) + 9 g_{N-1}) / 24;   Z_0 = 0, Z_i = Sum_{j <= i} d_j;
+ *   R^k = Q[ ((P_X,i Z_Y,i + P_Y,i Z_X,i) (1 / (p_i r_i))) s_i ], the term of node 0 (r_0 = 0) being 0,
+ * where X = (min(a,c), max(a,c)) and Y = (min(b,d), max(b,d)) are exchanged if Y < X (first index, then second), a product is its
+ * lower-indexed orbital times the other, and X == Y is one stream.  R^k is therefore bit-identical under a <-> c, b <-> d and
+ * (a,c) <-> (b,d).  F^k(a,b) = R^k(ab,ab), G^k(a,b) = R^k(ab,ba).  0 <= k <= DFTA_SLATER_KMAX, N >= 5.  The sums have a fixed shape
+ * that depends on N alone (no atomics): a job's value depends on its orbitals, k and N -- not on the other jobs of the
+ * call, its position among them, or the run.  Nodes beyond an orbital's cut-off are zeros like any others.
+ *
+ * A job table is njobs rows of five ints a, b, c, d, k.  Energies, with N_i the occupation of shell i in its channel
+ * (dfta_scf_get_occupations) and n_a = N_a for LSDA, N_a / 2 in each of two equal channels for LDA:
+ *   E_H = 1/2 Sum_i Sum_j (N_i N_j) F^0(i,j) over all shells of the atom, both channels: rows i, then j, one accumulator;
+ *   E_x = -1/2 Sum_sigma Sum_{a,b in sigma} (n_a n_b) T_ab,  T_ab = Sum_k (l_a k l_b; 0 0 0)^2 G^k(a,b),  G^k(a,a) = F^k(a,a),
+ *         |l_a - l_b| <= k <= l_a + l_b, k = l_a + l_b (mod 2), ascending: one accumulator S over the channels, alpha first, rows a,
+ *         then b (every b of the channel); LSDA: E_x = -0.5 S; LDA: S of the one channel with n = 0.5 N, E_x = -S.
+ * This is the spherically averaged exchange: valid for fractional occupations; for closed shells the average-of-configuration
+ * formula.  Both sums are host arithmetic in double on the integrals of ONE launch. */
+#define DFTA_SLATER_KMAX 8
+/* host-only: (la k lb; 0 0 0)^2 from the factorial closed form, correctly rounded; 0.0 where parity or the triangle rule fails.
+ * DFTA_ERR_INVALID: a negative argument, la or lb > 4, out NULL. */
+int  dfta_gaunt_3j2(int la, int k, int lb, double* out);
+/* host-only: the job table of the F^k / G^k of norb orbitals with angular momenta l (0 .. 4).  First the F^k(a,b), a <= b, k = 0, 2 ..
+ * 2 min(l_a, l_b), rows a,b,a,b,k ordered by a, then b, then k (kinds[j] = 0); then the G^k(a,b), a < b, k of the exchange sum, rows
+ * a,b,b,a,k in the same order (kinds[j] = 1).  G^k(a,a) = F^k(a,a) is no job of its own.  Returns the number of jobs (jobs, kinds may be
+ * NULL: count only), or -1 for norb < 0, l NULL or an l outside 0 .. 4. */
+int  dfta_slater_fg_jobs(int norb, const int* l, int* jobs, int* kinds);
+/* every job in one launch, on caller-supplied orbitals; host pointers.  u: norb x N; R: njobs.  njobs == 0: DFTA_OK, nothing is
+ * written.  Records the launch's time for dfta_ctx_last_kernel_ms. */
+int  dfta_slater_rk(dfta_ctx* ctx, const dfta_grid* g, int norb, const double* u, int njobs, const int* jobs, double* R);
+/* ... on the orbitals of an atom of the SCF, read in place; indices count the atom's orbitals as dfta_scf_orbital_properties lists
+ * them: alpha levels, then beta levels.  Before the first dfta_scf_step: DFTA_ERR_INVALID.  The job table and the results are kept
+ * on the device from the first such call on (grown when a longer table comes). */
+int  dfta_scf_slater_rk(dfta_scf* s, int atom, int njobs, const int* jobs, double* R);
+/* F, G: (DFTA_SLATER_KMAX + 1) x nlev x nlev each, k-major (host): the table of dfta_slater_fg_jobs for the levels of (atom, spin)
+ * from one launch, each value computed once and mirrored (symmetric bit for bit), G^k(a,a) = F^k(a,a), 0.0 where there is no job. */
+int  dfta_scf_slater_fg(dfta_scf* s, int atom, int spin, double* F, double* G);
+/* E_H and E_x of an atom from one launch: the F^0 of all its shell pairs, the G^k of each channel, then the host sums above */
+int  dfta_scf_coulomb_exchange(dfta_scf* s, int atom, double* EH, double* EXX);
+
 /* ---- Aufbau -------------------------------------------------------------------------------------------------
  * AufbauPrinciple::GetSubshells + sort (AufbauPrinciple.h:36-75, DFTAtom.cpp:367); integer-only host code. */
 int dfta_get_subshells(int Z, int* n, int* l, int* occ, int cap);
