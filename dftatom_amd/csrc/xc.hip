@@ -3,7 +3,7 @@
 // Replaces VWNExchCor::Vexc / eexcDif (VWNExcCor.h:73-128, LDA) and the spin-polarised pair
 // (VWNExcCor.h:134-312, LSDA) with ExcCorBase::f / df (ExcCorBase.h:14-26).  Expressions are written in the
 // reference's operation order; pow/log/atan come from the ROCm device library, so results agree with the
-// glibc-based reference to rounding of those functions (parity tolerance: 1e-13 relative, see tests).
+// glibc-based reference to rounding of those functions (the gate and its measure: tests/test_gpu_vwn.py).
 // HBM-bound by construction: LDA reads 8 B and writes 16 B per point, LSDA reads 16 B and writes 32 B.
 #include <hip/hip_runtime.h>
 

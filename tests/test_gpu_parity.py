@@ -8,7 +8,8 @@ Tolerances (fp64, stated per test):
   * device-side boundary values use the device exp(): u(0) within 1e-10 relative, eigenvalues within 1e-9 Ha;
   * multigrid: every sweep equals the sequential sweep; the 100-V-cycle end state sits on a round-off noise
     floor of ~1e-10 (the reference's 1e-14 stop test is never met, SURVEY C.7), tolerance 1e-10*Z absolute;
-  * VWN (device pow/log/atan): 1e-9 relative; SCF energies 1e-9 relative, eigenvalues 1e-8 Ha.
+  * VWN (device pow/log/atan): the gate and its measure are stated in tests/test_gpu_vwn.py; SCF energies 1e-9 relative,
+    eigenvalues 1e-8 Ha.
 """
 import ctypes as C
 import json
