@@ -1,4 +1,4 @@
-// ctx_grid.cpp -- context, grid tables and the integer-only Aufbau helper of libdftatom_hip.
+// ctx_grid.cpp -- context and grid tables of libdftatom_hip (Aufbau and the electron configurations: scf_config.cpp).
 //
 // Grid tables replace the per-point exp() calls of NumerovFunctionNonUniformGrid (Numerov.h:76-101,
 // 181-184) and of the SCF pointwise loops (DFTAtom.cpp:42,47,334,439-442; PoissonSolver.h:66-74).
@@ -7,11 +7,8 @@
 #include <cmath>
 #include <cstdint>
 #include <cstdlib>
-#include <algorithm>
-#include <cstdarg>
 #include <cstdio>
 #include <cstring>
-#include <string>
 #include <memory>
 #include <vector>
 
@@ -253,264 +250,6 @@ int dfta_grid_get_r(const dfta_grid* g, double* r_host)
     if (!g || !r_host) return DFTA_ERR_INVALID;
     memcpy(r_host, g->h_r.data(), sizeof(double) * g->h_r.size());
     return DFTA_OK;
-}
-
-// ---- Aufbau (integer only; AufbauPrinciple.h:36-75,101-117 and DFTAtom.cpp:367, 611-638) -----------------
-static void adjust_f_block(int& nrElectrons, int Z, int N, int L)
-{
-    if (L == 3) {
-        if ((Z == 57 || Z == 58 || Z == 64) && N == 3) --nrElectrons;      // La, Ce, Gd: one 4f electron goes to 5d
-        else if (N == 4) {
-            if (Z == 89 || Z == 90) nrElectrons = 0;                        // Ac, Th
-            else if (Z == 91 || Z == 92 || Z == 93 || Z == 96) --nrElectrons; // Pa, U, Np, Cm
-        }
-    } else if (Z == 103 && N == 5 && L == 2) nrElectrons = 0;              // Lr
-}
-
-// AufbauPrinciple.h:78-99,119-127: the s shell under a d shell that the Madelung rule leaves one (Pd: two) short hands
-// the electron(s) over.  The reference defines this adjustment but never calls it (Cr comes out as 3d4 4s2); here it is an
-// option, applied once, after the clamp to the electrons that are left (an s shell is never clamped, so once is enough).
-static void adjust_transition_metal(int& nrElectrons, int Z, int N, int L)
-{
-    if (L != 0) return;
-    const bool one = (Z == 24 || Z == 29 || Z == 41 || Z == 42 || Z == 44 || Z == 45 || Z == 47 || Z == 78 || Z == 79);
-    if (one) {
-        const int outer_s = Z <= 29 ? 3 : (Z <= 47 ? 4 : 5);              // 4s, 5s, 6s
-        if (N == outer_s) --nrElectrons;
-    } else if (Z == 46 && N == 4) nrElectrons -= 2;                        // Pd: 4d10 5s0
-}
-
-int dfta_get_subshells(int Z, int* n, int* l, int* occ, int cap) { return dfta_get_subshells_ex(Z, DFTA_AUFBAU_REFERENCE, n, l, occ, cap); }
-
-int dfta_get_subshells_ex(int Z, int aufbau, int* n, int* l, int* occ, int cap)
-{
-    if (Z < 1 || !n || !l || !occ) return -1;
-    struct S { int n, l, occ; };
-    std::vector<S> lv;
-    int electronCount = 0;
-    bool stop = false;
-    for (int NplusL = 0; !stop && NplusL < 10; ++NplusL)
-        for (int N = 0; N <= NplusL; ++N) {
-            const int L = NplusL - N;
-            if (L > N) continue;
-            int e = 2 * (2 * L + 1);
-            adjust_f_block(e, Z, N, L);
-            if (Z - electronCount < e) e = Z - electronCount;
-            adjust_f_block(e, Z, N, L);
-            if (aufbau == DFTA_AUFBAU_TRANSITION_METALS) adjust_transition_metal(e, Z, N, L);
-            if (e > 0) { electronCount += e; lv.push_back({N, L, e}); }
-            if (electronCount == Z) { stop = true; break; }
-        }
-    std::sort(lv.begin(), lv.end(), [](const S& a, const S& b) { return a.n < b.n || (a.n == b.n && a.l < b.l); });
-    if (static_cast<int>(lv.size()) > cap) return -1;
-    for (size_t i = 0; i < lv.size(); ++i) { n[i] = lv[i].n; l[i] = lv[i].l; occ[i] = lv[i].occ; }
-    return static_cast<int>(lv.size());
-}
-
-int dfta_split_spin(int Z, int* nA, int* nB, int* an, int* al, int* aocc, int* bn, int* bl, int* bocc, int cap)
-{
-    return dfta_split_spin_ex(Z, DFTA_AUFBAU_REFERENCE, nA, nB, an, al, aocc, bn, bl, bocc, cap);
-}
-
-int dfta_split_spin_ex(int Z, int aufbau, int* nA, int* nB, int* an, int* al, int* aocc, int* bn, int* bl, int* bocc, int cap)
-{
-    if (!nA || !nB) return DFTA_ERR_INVALID;
-    const int cnt = dfta_get_subshells_ex(Z, aufbau, an, al, aocc, cap);
-    if (cnt < 0) return DFTA_ERR_INVALID;
-    int m = 0;
-    for (int i = 0; i < cnt; ++i) {
-        const int maxe = 2 * al[i] + 1;
-        int b;
-        if (aocc[i] >= maxe) { b = aocc[i] - maxe; aocc[i] = maxe; }
-        else b = 0;
-        if (b != 0) { bn[m] = an[i]; bl[m] = al[i]; bocc[m] = b; ++m; }
-    }
-    *nA = cnt;
-    *nB = m;
-    return DFTA_OK;
-}
-
-// ---- electron configurations (host only): text, charge rule, validation ----------------------------------------------------
-namespace {
-
-thread_local char g_config_err[160] = "";
-
-int config_fail(const char* fmt, ...) __attribute__((format(printf, 1, 2)));
-int config_fail(const char* fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_config_err, sizeof(g_config_err), fmt, ap);
-    va_end(ap);
-    return DFTA_ERR_INVALID;
-}
-
-struct Sub {
-    int n, l;            // n: principal quantum number - 1, as dfta_get_subshells_ex reports it (the reference's m_N)
-    double occ;          // total
-    bool split;          // LSDA: alpha / beta given explicitly
-    double a, b;
-    bool core;           // taken from a noble-gas core (a token may replace it)
-};
-
-const char kSpd[] = "spdf";
-
-// the Aufbau configuration of Z as subshells, sorted by (n, l)
-int aufbau_subs(int Z, int aufbau, std::vector<Sub>& out)
-{
-    int n[32], l[32], o[32];
-    const int cnt = dfta_get_subshells_ex(Z, aufbau, n, l, o, 32);
-    if (cnt < 0) return config_fail("no Aufbau configuration for Z = %d", Z);
-    out.clear();
-    for (int k = 0; k < cnt; ++k) out.push_back({n[k], l[k], static_cast<double>(o[k]), false, 0., 0., true});
-    return DFTA_OK;
-}
-
-// validation, the spin split and the output arrays (alpha levels, then beta levels; LDA: alpha only)
-int emit(int Z, int lsda, std::vector<Sub> subs, int cap, int* nA, int* nB, int* an, int* al, double* aocc, int* bn, int* bl,
-         double* bocc)
-{
-    if (Z < 1 || Z > 118) return config_fail("Z = %d out of range 1 .. 118", Z);
-    std::stable_sort(subs.begin(), subs.end(), [](const Sub& x, const Sub& y) { return x.n < y.n || (x.n == y.n && x.l < y.l); });
-    double ne = 0;
-    for (size_t k = 0; k < subs.size(); ++k) {
-        const Sub& s = subs[k];
-        if (s.l < 0 || s.l > 3 || s.n < s.l) return config_fail("level n = %d, l = %d: needs 0 <= l < n and l <= 3", s.n + 1, s.l);
-        if (k > 0 && subs[k - 1].n == s.n && subs[k - 1].l == s.l) return config_fail("%d%c given twice", s.n + 1, kSpd[s.l]);
-        const double full = 2. * (2 * s.l + 1);
-        if (!(s.occ > 0) || s.occ > full) return config_fail("%d%c: occupation %g outside (0, %g]", s.n + 1, kSpd[s.l], s.occ, full);
-        if (s.split && (!(s.a >= 0) || !(s.b >= 0) || s.a > full / 2 || s.b > full / 2))
-            return config_fail("%d%c: spin occupations %g / %g outside [0, %g]", s.n + 1, kSpd[s.l], s.a, s.b, full / 2);
-        ne += s.occ;
-    }
-    if (!(ne > 0)) return config_fail("no electrons");
-    if (ne > Z + 1e-9) return config_fail("%g electrons for Z = %d: anions are not supported", ne, Z);
-    int ka = 0, kb = 0;
-    for (const Sub& s : subs) {
-        double a = s.occ, b = 0;
-        if (lsda) {
-            const double maxe = 2 * s.l + 1;                 // DFTAtom.cpp:611-638 / dfta_split_spin_ex
-            if (s.split) { a = s.a; b = s.b; }
-            else if (s.occ >= maxe) { a = maxe; b = s.occ - maxe; }
-        }
-        if (a != 0) {
-            if (ka >= cap) return config_fail("more than %d levels", cap);
-            an[ka] = s.n; al[ka] = s.l; aocc[ka] = a; ++ka;
-        }
-        if (b != 0) {
-            if (kb >= cap) return config_fail("more than %d levels", cap);
-            bn[kb] = s.n; bl[kb] = s.l; bocc[kb] = b; ++kb;
-        }
-    }
-    *nA = ka;
-    *nB = kb;
-    g_config_err[0] = 0;
-    return DFTA_OK;
-}
-
-bool parse_number(const char*& p, double& v)
-{
-    if (!((*p >= '0' && *p <= '9') || *p == '.')) return false;
-    char* end = nullptr;
-    v = strtod(p, &end);
-    if (end == p) return false;
-    p = end;
-    return true;
-}
-
-}  // namespace
-
-const char* dfta_config_last_error(void) { return g_config_err; }
-
-}  // extern "C"
-
-namespace dfta {
-void config_set_error(const char* msg) { snprintf(g_config_err, sizeof(g_config_err), "%s", msg); }   // dfta_scf_create_config's refusals
-}
-
-extern "C" {
-
-int dfta_config_parse(int Z, int lsda, int aufbau, const char* text, int cap, int* nA, int* nB, int* an, int* al, double* aocc,
-                      int* bn, int* bl, double* bocc)
-{
-    if (!text || !nA || !nB || !an || !al || !aocc || (lsda && (!bn || !bl || !bocc))) return config_fail("null argument");
-    if (aufbau != DFTA_AUFBAU_REFERENCE && aufbau != DFTA_AUFBAU_TRANSITION_METALS) return config_fail("aufbau option %d", aufbau);
-    std::vector<Sub> subs;
-    const char* p = text;
-    bool any = false;
-    for (;;) {
-        while (*p == ' ' || *p == '\t' || *p == '\n' || *p == '\r') ++p;
-        if (!*p) break;
-        const char* tok = p;
-        while (*p && *p != ' ' && *p != '\t' && *p != '\n' && *p != '\r') ++p;
-        const std::string t(tok, p);
-        if (t[0] == '[') {
-            static const char* const gas[] = {"[He]", "[Ne]", "[Ar]", "[Kr]", "[Xe]", "[Rn]"};
-            static const int gasZ[] = {2, 10, 18, 36, 54, 86};
-            int zc = 0;
-            for (int k = 0; k < 6; ++k) if (t == gas[k]) zc = gasZ[k];
-            if (!zc) return config_fail("unknown core '%s' (one of [He] [Ne] [Ar] [Kr] [Xe] [Rn])", t.c_str());
-            if (any) return config_fail("the core '%s' must come first", t.c_str());
-            if (int rc = aufbau_subs(zc, aufbau, subs)) return rc;
-            any = true;
-            continue;
-        }
-        any = true;
-        const char* q = t.c_str();
-        char* end = nullptr;
-        const long n = strtol(q, &end, 10);
-        if (end == q || n < 1 || n > 99) return config_fail("'%s': expected <n><spdf><occupation>", t.c_str());
-        q = end;
-        const char* lc = *q ? strchr(kSpd, *q) : nullptr;
-        if (!lc) return config_fail("'%s': expected <n><spdf><occupation>", t.c_str());
-        ++q;
-        Sub s{static_cast<int>(n) - 1, static_cast<int>(lc - kSpd), 0., false, 0., 0., false};
-        if (!parse_number(q, s.occ)) return config_fail("'%s': missing occupation", t.c_str());
-        if (*q == '/') {
-            if (!lsda) return config_fail("'%s': an alpha / beta split needs LSDA", t.c_str());
-            ++q;
-            s.a = s.occ;
-            if (!parse_number(q, s.b)) return config_fail("'%s': missing beta occupation", t.c_str());
-            s.split = true;
-            s.occ = s.a + s.b;
-        }
-        if (*q) return config_fail("'%s': trailing characters", t.c_str());
-        bool dup = false;
-        for (Sub& x : subs)
-            if (x.n == s.n && x.l == s.l) {
-                if (!x.core) return config_fail("%d%c given twice", s.n + 1, kSpd[s.l]);
-                x = s;                                         // replaces what the core holds there
-                dup = true;
-            }
-        if (!dup) subs.push_back(s);
-    }
-    if (!any) return config_fail("empty configuration");
-    std::vector<Sub> kept;
-    for (const Sub& s : subs) if (s.occ != 0) kept.push_back(s);       // occupation 0 removes the subshell
-    return emit(Z, lsda, kept, cap, nA, nB, an, al, aocc, bn, bl, bocc);
-}
-
-int dfta_ion_config(int Z, int charge, int lsda, int aufbau, int cap, int* nA, int* nB, int* an, int* al, double* aocc,
-                    int* bn, int* bl, double* bocc)
-{
-    if (!nA || !nB || !an || !al || !aocc || (lsda && (!bn || !bl || !bocc))) return config_fail("null argument");
-    if (Z < 1 || Z > 118) return config_fail("Z = %d out of range 1 .. 118", Z);
-    if (aufbau != DFTA_AUFBAU_REFERENCE && aufbau != DFTA_AUFBAU_TRANSITION_METALS) return config_fail("aufbau option %d", aufbau);
-    if (charge < 0) return config_fail("charge %d: anions are not supported", charge);
-    if (charge >= Z) return config_fail("charge %d leaves no electrons for Z = %d", charge, Z);
-    std::vector<Sub> subs;
-    if (int rc = aufbau_subs(Z, aufbau, subs)) return rc;
-    // the electrons leave the subshell of highest n, ties to the highest l (Fe+ = 3d6 4s1), one subshell after the other
-    for (int q = charge; q > 0;) {
-        size_t top = 0;
-        for (size_t k = 1; k < subs.size(); ++k)
-            if (subs[k].n > subs[top].n || (subs[k].n == subs[top].n && subs[k].l > subs[top].l)) top = k;
-        const int take = std::min<int>(q, static_cast<int>(subs[top].occ));
-        subs[top].occ -= take;
-        q -= take;
-        if (subs[top].occ == 0) subs.erase(subs.begin() + static_cast<long>(top));
-    }
-    return emit(Z, lsda, subs, cap, nA, nB, an, al, aocc, bn, bl, bocc);
 }
 
 }  // extern "C"

@@ -178,7 +178,7 @@ int dfta_anderson_create(dfta_ctx* ctx, const dfta_grid* g, int natoms, int nspi
 int dfta_launch_anderson_mix(dfta_ctx* ctx, const dfta_grid* g, dfta_anderson* an, int lsda, int natoms, double alpha, double oneMinusAlpha,
                              double* newDensity, double* density, double* dA, double* dB, const int* fin);
 // orbitals.hip: expectation values and r^k matrix elements of orbitals u = r R (device pointers; include/dftatom_hip.h has the definitions)
-constexpr int kOrbitalMatrixMax = 32;      // orbitals of one matrix: the levels of a spin channel (scf_configure allows 32)
+constexpr int kOrbitalMatrixMax = 32;      // orbitals of one matrix: the levels of a spin channel (plan_scf_config allows 32)
 struct dfta_orbital_scratch {              // of dfta_launch_orbital_matrix, for up to norb_max orbitals
     int norb_max = 0;
     DevBuf<double> slab;                   // [chunk][pair a <= b]: the chunks' partial sums

@@ -4,12 +4,9 @@
 
 #include "common.h"
 #include "internal.h"
+#include "scf_config.h"     // JobSpec
 
 namespace dfta {
-
-// occ: the level's integer occupation as the reference's records hold it (Job::occ); docc: the occupation the density and the
-// electronic energy are summed with -- (double)occ for an Aufbau configuration, a fractional one for dfta_scf_create_config
-struct JobSpec { int v, n, l, occ; double docc; };
 
 // state of one (potential, level) eigenvalue search; lives in device memory
 struct Job {

@@ -5,6 +5,7 @@
 // (atom, spin), density mixing, multigrid Poisson, VWN, the pointwise potential/integrand pass, the five
 // Simpson 3/8 integrals (reference summation order) and the energy assembly + convergence test.
 // Potentials are stored as V[(atom * nspin + spin) * N + i].
+// What a configuration and the options may be is scf_config.cpp's (pure host code); the accessors of the state are scf_api.cpp's.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -12,31 +13,15 @@
 #include <cstdlib>
 #include <vector>
 
-#include "internal.h"
-#include "levels.h"
 #include "ordered_sum.h"
-#include "slater_plan.h"
+#include "scf_state.h"
 #include "xc.h"
-
-namespace dfta { void config_set_error(const char* msg); }   // ctx_grid.cpp: the text dfta_config_last_error() returns
 
 namespace {
 
 constexpr double kPi = 3.14159265358979323846;
 constexpr double fourM_PI = 4. * kPi;
 constexpr double kTotalEnergyErr = 1E-11;   // DFTAtom.cpp:349
-
-struct AtomState {          // per atom, device
-    int Z;                  // nuclear charge: potential, energies, bracket bottoms, R[0] of the record
-    double nE;              // electrons: the flat start density and the multigrid's outer boundary (== Z for a neutral atom)
-    double nAlphaE, nBetaE; // electrons per spin (LSDA), DFTAtom.cpp:611-638
-    int job_off, job_end;   // jobs of this atom in the level solver (alpha levels first, then beta)
-    int lastTimeConverged;
-    int finished;
-    int steps;
-    double Eold;
-    dfta_energies e;
-};
 
 // flat start density (DFTAtom.cpp:371-376 / 874-884)
 __global__ void k_init_density(const AtomState* __restrict__ atoms, int lsda, int N, double MaxR, double* __restrict__ density,
@@ -229,54 +214,6 @@ __global__ void k_scatter_rows(const double* __restrict__ src, const int* __rest
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < N; i += gridDim.x * blockDim.x) d[i] = s[i];
 }
 
-constexpr int kLiveClasses = 6;
-constexpr int kLiveClassAtoms[kLiveClasses] = {7, 15, 16, 32, 64, 128};     // (7 / 15: the resident multigrid's two configurations)
-
-struct dfta_scf {
-    dfta_ctx* ctx = nullptr;
-    const dfta_grid* g = nullptr;
-    int lsda = 0, natoms = 0, nspin = 1, nV = 0;
-    double alpha = 0.5;
-    dfta::LevelSolver solver;
-    dfta_poisson* poisson = nullptr;
-    // Finished atoms are frozen, and the multigrid's workgroups per atom are a function of the batch size (1 for > 128 atoms ... 16 for
-    // <= 16, the resident groups' 33 for <= 7): once the LIVE atoms of a batch fit a smaller size class, their solve goes to a second
-    // solver made for that class, on gathered copies of their densities (results scattered back; the same bits -- every grouping of
-    // the multigrid is bit-identical to one workgroup per atom).
-    struct LiveSolver { dfta_poisson* p = nullptr; int G = 0; bool tried = false; };
-    LiveSolver live_solver[kLiveClasses];
-    int live_cap = 0;                     // atoms the gather buffers hold
-    DevBuf<int> d_liveIdx;                // live_cap skip flags, then live_cap atom indices
-    DevBuf<double> d_liveNe, d_liveRho, d_liveU;   // d_liveNe: the live atoms' electron counts
-    void free_live() { d_liveIdx.reset(); d_liveNe.reset(); d_liveRho.reset(); d_liveU.reset(); live_cap = 0; }
-    std::vector<AtomState> h_atoms;
-    std::vector<int> h_liveIdx;           // host staging of d_liveIdx and d_liveNe (the copies are asynchronous: they live to the step's last
-    std::vector<double> h_liveNe;         // synchronisation at least)
-    std::vector<double> h_bottom0;        // per potential: -Z^2-1 (DFTAtom.cpp:407)
-    std::vector<double> h_job_bottom;     // per job: bracket start of the next level solve
-    std::vector<dfta::Job> h_jobs;        // job results of the last step
-    std::vector<unsigned char> h_frozen;  // per job: its atom has finished
-    DevBuf<int> d_fin;                    // per atom: finished (device copy for the kernels that skip frozen atoms)
-    bool debug_levels = false;            // $DFTA_DEBUG_LEVELS
-    int integ_rule = DFTA_INT_SIMPSON38;  // dfta_scf_set_integrator
-    int functional = DFTA_XC_VWN;         // dfta_scf_options::functional
-    int fallbacks_seen = 0;               // level-search fallbacks already reported in a step's statistics
-    int levels_mode = DFTA_LEVELS_BATCHED;
-    int steps_done = 0;
-    int mixing = DFTA_MIX_LINEAR;         // dfta_scf_options::mixing
-    dfta_anderson anderson;               // DFTA_MIX_ANDERSON: the atoms' history and the solve's scratch (mixing.hip); empty otherwise
-    std::vector<int> spin_nlev[2];      // per atom number of levels per spin
-    DevBuf<AtomState> d_atoms;
-    DevBuf<double> d_Ne;                  // per atom: electrons, the multigrid's outer boundary U(Rmax)
-    DevBuf<double> d_density, d_dA, d_dB, d_V, d_U, d_Vexc, d_va, d_vb, d_eexc, d_newDensity, d_integrands, d_integrals, d_records;
-    DevEvent ev[5];
-    // orbital expectation values and matrix elements (orbitals.hip): nothing is allocated before the first such call
-    DevBuf<int> d_orb_l;                  // per job: l
-    DevBuf<double> d_orb_props;           // njobs x DFTA_ORB_PROPS
-    dfta_orbital_scratch orb_scratch;     // of dfta_scf_orbital_matrix, sized for the longest channel of the batch
-    dfta_slater_scratch slater;           // of the Slater-integral calls (slater.hip): job table and results, made by the first such call
-};
-
 static int scf_xc(dfta_scf* s)
 {
     const size_t sz = (size_t)s->natoms * s->g->N;
@@ -317,99 +254,6 @@ int dfta_scf_create_ex(dfta_ctx* ctx, const dfta_grid* g, int lsda, int natoms, 
     return dfta_scf_create_config(ctx, g, lsda, natoms, Z, nullptr, nullptr, nullptr, nullptr, alpha, levels_mode, tree_depth, options, out);
 }
 
-// the levels of one spin channel of an explicit configuration: sorted by (n, l) (DFTAtom.cpp:367) and checked; ne += their electrons
-static bool config_channel(dfta_ctx* ctx, int a, int lsda, int cnt, const int* n, const int* l, const double* occ,
-                           std::vector<std::pair<std::pair<int, int>, double>>& lev, double& ne)
-{
-    lev.clear();
-    for (int k = 0; k < cnt; ++k) lev.push_back({{n[k], l[k]}, occ[k]});
-    std::stable_sort(lev.begin(), lev.end(), [](const auto& x, const auto& y) { return x.first < y.first; });
-    const double perl = lsda ? 1. : 2.;
-    for (size_t k = 0; k < lev.size(); ++k) {
-        const int N = lev[k].first.first, L = lev[k].first.second;
-        const double o = lev[k].second;
-        // N: principal quantum number - 1, as dfta_get_subshells_ex and dfta_scf_get_levels report it
-        if (L < 0 || L > 3 || N < L) { snprintf(ctx->err, sizeof(ctx->err), "atom %d: level n = %d, l = %d (needs 0 <= l < n, l <= 3)", a, N + 1, L); return false; }
-        if (k > 0 && lev[k - 1].first == lev[k].first) { snprintf(ctx->err, sizeof(ctx->err), "atom %d: level n = %d, l = %d given twice", a, N + 1, L); return false; }
-        if (!(o > 0) || o > perl * (2 * L + 1)) {
-            snprintf(ctx->err, sizeof(ctx->err), "atom %d: level n = %d, l = %d: occupation %g outside (0, %g]", a, N + 1, L, o, perl * (2 * L + 1));
-            return false;
-        }
-        ne += o;
-    }
-    return true;
-}
-
-// (Z, explicit configuration or Aufbau) of every atom -> its AtomState, the bracket bottoms, the levels per spin and the job list.
-// Host only; on an error the text is in ctx->err (and, for an explicit configuration, in dfta_config_last_error()).
-static int scf_configure(dfta_scf* s, const int* Z, const int* nlev, const int* cn, const int* cl, const double* cocc, int aufbau,
-                         std::vector<dfta::JobSpec>& specs)
-{
-    dfta_ctx* ctx = s->ctx;
-    const int lsda = s->lsda, natoms = s->natoms;
-    s->h_atoms.resize(natoms);
-    s->h_bottom0.resize(s->nV);
-    s->spin_nlev[0].resize(natoms); s->spin_nlev[1].assign(natoms, 0);
-    std::vector<std::pair<std::pair<int, int>, double>> lev;
-    size_t coff = 0;                                           // running offset into the caller's n / l / occ
-    for (int a = 0; a < natoms; ++a) {
-        if (Z[a] < 1 || Z[a] > 118) {
-            snprintf(ctx->err, sizeof(ctx->err), "Z out of range");
-            if (nlev) dfta::config_set_error(ctx->err);
-            return DFTA_ERR_INVALID;
-        }
-        AtomState& st = s->h_atoms[a];
-        memset(&st, 0, sizeof(st));
-        st.Z = Z[a];
-        st.job_off = (int)specs.size();
-        for (int spin = 0; spin < s->nspin; ++spin) s->h_bottom0[s->nspin * a + spin] = -double(Z[a]) * Z[a] - 1.;     // DFTAtom.cpp:407 / 919,929
-        int an[32], al[32], ao[32], bn[32], bl[32], bo[32], nA = 0, nB = 0;
-        if (nlev) {                                            // explicit configuration (fractional occupations, cations)
-            nA = nlev[2 * a];
-            nB = nlev[2 * a + 1];
-            double ne = 0, neA = 0;
-            bool ok = nA >= 0 && nB >= 0 && nA + nB >= 1 && nA <= 32 && nB <= 32 && (lsda || nB == 0);
-            if (!ok) snprintf(ctx->err, sizeof(ctx->err), "atom %d: level counts %d / %d (1 .. 32 levels; LDA: no beta levels)", a, nA, nB);
-            for (int spin = 0; ok && spin < (lsda ? 2 : 1); ++spin) {
-                const int cnt = spin ? nB : nA;
-                ok = config_channel(ctx, a, lsda, cnt, cn + coff, cl + coff, cocc + coff, lev, ne);
-                coff += (size_t)cnt;
-                for (size_t k = 0; ok && k < lev.size(); ++k) {
-                    const double o = lev[k].second;
-                    const int io = (o == std::floor(o)) ? static_cast<int>(o) : 0;     // Job::occ: the integer, 0 for a fractional one
-                    specs.push_back({lsda ? 2 * a + spin : a, lev[k].first.first, lev[k].first.second, io, o});
-                }
-                if (spin == 0) neA = ne;
-            }
-            if (ok && ne > Z[a] + 1e-9) {
-                snprintf(ctx->err, sizeof(ctx->err), "atom %d: %g electrons for Z = %d (anions are not supported)", a, ne, Z[a]);
-                ok = false;
-            }
-            if (!ok) { dfta::config_set_error(ctx->err); return DFTA_ERR_INVALID; }
-            st.nE = ne;
-            st.nAlphaE = neA;
-            st.nBetaE = ne - neA;
-        } else if (!lsda) {
-            nA = dfta_get_subshells_ex(Z[a], aufbau, an, al, ao, 32);
-            if (nA < 0) return DFTA_ERR_INVALID;
-            for (int k = 0; k < nA; ++k) specs.push_back({a, an[k], al[k], ao[k], static_cast<double>(ao[k])});
-            st.nE = Z[a];
-        } else {
-            if (dfta_split_spin_ex(Z[a], aufbau, &nA, &nB, an, al, ao, bn, bl, bo, 32) != DFTA_OK) return DFTA_ERR_INVALID;
-            int ne = 0;
-            for (int k = 0; k < nA; ++k) { specs.push_back({2 * a, an[k], al[k], ao[k], static_cast<double>(ao[k])}); ne += ao[k]; }
-            for (int k = 0; k < nB; ++k) specs.push_back({2 * a + 1, bn[k], bl[k], bo[k], static_cast<double>(bo[k])});
-            st.nE = Z[a];
-            st.nAlphaE = ne;
-            st.nBetaE = Z[a] - ne;
-        }
-        s->spin_nlev[0][a] = nA;
-        s->spin_nlev[1][a] = nB;
-        st.job_end = (int)specs.size();
-    }
-    return DFTA_OK;
-}
-
 int dfta_scf_create_config(dfta_ctx* ctx, const dfta_grid* g, int lsda, int natoms, const int* Z, const int* nlev, const int* cn,
                            const int* cl, const double* cocc, double alpha, int levels_mode, int tree_depth,
                            const dfta_scf_options* options, dfta_scf** out)
@@ -418,42 +262,30 @@ int dfta_scf_create_config(dfta_ctx* ctx, const dfta_grid* g, int lsda, int nato
     DFTA_ENTER(ctx);
     DFTA_REQUIRE(ctx, natoms >= 1 && Z && alpha >= 0 && alpha <= 1, "scf arguments");
     DFTA_REQUIRE(ctx, !nlev || (cn && cl && cocc), "configuration: n, l and occ are needed with nlev");
-    dfta_scf_options opt = {(int)sizeof(dfta_scf_options), DFTA_INT_SIMPSON38, DFTA_XC_VWN, DFTA_AUFBAU_REFERENCE, -1, DFTA_SWEEPS_EXACT, DFTA_MIX_LINEAR, 0, 0};
-    if (options) {
-        // the caller's struct may be shorter (an older header) or longer (a newer one) than this library's: read what both know
-        const int sz = options->struct_size;
-        DFTA_REQUIRE(ctx, sz >= (int)(2 * sizeof(int)) && sz % (int)sizeof(int) == 0 && sz <= 4096, "dfta_scf_options::struct_size (set it to sizeof(dfta_scf_options))");
-        // members the caller's struct does not have keep the defaults above; those it has are taken as they are (0 = the reference's behaviour)
-        memcpy(&opt, options, std::min<size_t>((size_t)sz, sizeof(opt)));
-        opt.struct_size = (int)sizeof(dfta_scf_options);
-    }
-    DFTA_REQUIRE(ctx, opt.poisson_mode >= -1 && opt.poisson_mode <= DFTA_POISSON_ADAPTIVE, "poisson mode");
-    DFTA_REQUIRE(ctx, dfta_integral_shape_ok(opt.integrator, g->N), "integration rule / grid size");
-    DFTA_REQUIRE(ctx, opt.functional >= DFTA_XC_VWN && opt.functional <= DFTA_XC_PBE, "functional (DFTA_XC_VWN .. DFTA_XC_PBE)");
-    DFTA_REQUIRE(ctx, (opt.functional != DFTA_XC_CHACHIYO && opt.functional != DFTA_XC_CHACHIYO_IMPROVED) || !lsda, "the Chachiyo functional is LDA only (ExcCor.h)");
-    DFTA_REQUIRE(ctx, opt.functional != DFTA_XC_PBE || !g->uniform, "the PBE functional needs a logarithmic grid (no GGA on the uniform grid)");
-    DFTA_REQUIRE(ctx, opt.aufbau == DFTA_AUFBAU_REFERENCE || opt.aufbau == DFTA_AUFBAU_TRANSITION_METALS, "aufbau");
-    DFTA_REQUIRE(ctx, opt.sweep_mode == DFTA_SWEEPS_EXACT || opt.sweep_mode == DFTA_SWEEPS_TOLERANCE, "sweep mode");
-    DFTA_REQUIRE(ctx, opt.sweep_mode == DFTA_SWEEPS_EXACT || dfta_scan_supported(g), "the tolerance mode of the sweeps needs a logarithmic grid of 12 .. 20 multigrid levels");
-    DFTA_REQUIRE(ctx, opt.mixing == DFTA_MIX_LINEAR || opt.mixing == DFTA_MIX_ANDERSON, "mixing (DFTA_MIX_LINEAR / DFTA_MIX_ANDERSON)");
-    DFTA_REQUIRE(ctx, opt.mix_history >= 0 && opt.mix_history <= kAndersonMaxHistory, "mix_history (1 .. 8; 0: the default, 4)");
-    DFTA_REQUIRE(ctx, opt.mix_warmup >= 0 && opt.mix_warmup <= 100, "mix_warmup (1 .. 100; 0: the default, 3)");
+    dfta::ScfFacts facts = {lsda ? 1 : 0, g->uniform, dfta_scan_supported(g), 0u, kAndersonMaxHistory};
+    for (int r = 0; r <= DFTA_INT_ROMBERG; ++r) if (dfta_integral_shape_ok(r, g->N)) facts.integrators_fit |= 1u << r;
+    dfta_scf_options opt;
+    if (const char* why = dfta::resolve_scf_options(options, facts, &opt)) DFTA_REQUIRE(ctx, false, why);
     dfta_scf* s = new dfta_scf();
     struct Guard { dfta_scf* s; ~Guard() { dfta_scf_destroy(s); } } guard{s};      // every error return below destroys what has been made
     s->solver.sweep_mode = opt.sweep_mode;
-    s->integ_rule = opt.integrator;
     s->solver.integ_rule = opt.integrator;
     s->functional = opt.functional;
     s->ctx = ctx; s->g = g; s->lsda = lsda ? 1 : 0; s->natoms = natoms; s->nspin = lsda ? 2 : 1; s->nV = natoms * s->nspin;
     s->alpha = alpha;
     const int N = g->N;
-    std::vector<dfta::JobSpec> specs;
-    int rc = scf_configure(s, Z, nlev, cn, cl, cocc, opt.aufbau, specs);
-    if (rc) return rc;
-    s->levels_mode = levels_mode;
-    s->h_job_bottom.resize(specs.size());
-    for (size_t k = 0; k < specs.size(); ++k) s->h_job_bottom[k] = s->h_bottom0[specs[k].v];
-    rc = s->solver.setup(ctx, g, levels_mode, tree_depth, s->nV, specs);
+    if (dfta::plan_scf_config(natoms, Z, nlev, cn, cl, cocc, s->lsda, opt.aufbau, &s->cfg)) {
+        snprintf(ctx->err, sizeof(ctx->err), "%s", dfta_config_last_error());
+        return DFTA_ERR_INVALID;
+    }
+    s->h_atoms.resize(natoms);
+    for (int a = 0; a < natoms; ++a) {
+        const dfta::AtomConfig& c = s->cfg.atoms[a];
+        AtomState& at = s->h_atoms[a];
+        memset(&at, 0, sizeof(at));
+        at.Z = c.Z; at.nE = c.nE; at.nAlphaE = c.nAlphaE; at.nBetaE = c.nBetaE; at.job_off = c.job_off; at.job_end = c.job_end;
+    }
+    int rc = s->solver.setup(ctx, g, levels_mode, tree_depth, s->nV, s->cfg.specs);
     if (rc) return rc;
     rc = opt.poisson_mode < 0 ? dfta_poisson_create(ctx, g, natoms, &s->poisson) : dfta_poisson_create_ex(ctx, g, natoms, opt.poisson_mode, &s->poisson);
     if (rc) return rc;
@@ -468,7 +300,7 @@ int dfta_scf_create_config(dfta_ctx* ctx, const dfta_grid* g, int lsda, int nato
     al(s->d_atoms, natoms); al(s->d_Ne, natoms); al(s->d_fin, natoms);
     s->mixing = opt.mixing;
     if (e == hipSuccess && s->mixing == DFTA_MIX_ANDERSON) {       // the history ring: 2 mix_history doubles per node and spin channel
-        rc = dfta_anderson_create(ctx, g, natoms, s->nspin, opt.mix_history ? opt.mix_history : 4, opt.mix_warmup ? opt.mix_warmup : 3, &s->anderson);
+        rc = dfta_anderson_create(ctx, g, natoms, s->nspin, opt.mix_history, opt.mix_warmup, &s->anderson);
         if (rc) return rc;
     }
     if (e == hipSuccess) e = hipMemsetAsync(s->d_fin, 0, sizeof(int) * natoms, st);
@@ -494,7 +326,7 @@ int dfta_scf_create_config(dfta_ctx* ctx, const dfta_grid* g, int lsda, int nato
     rc = dfta_poisson_take_vcycles(s->poisson, &dummy);
     if (rc) return rc;
     s->debug_levels = dfta_knob("DEBUG_LEVELS") != nullptr;
-    s->h_frozen.assign(specs.size(), 0);
+    s->h_frozen.assign(s->cfg.specs.size(), 0);
     guard.s = nullptr;
     *out = s;
     return DFTA_OK;
@@ -570,8 +402,7 @@ static int scf_fill_stats(dfta_scf* s, const dfta::LevelStats& ls, dfta_poisson*
 {
     dfta_ctx* ctx = s->ctx;
     const int user_size = user->struct_size;
-    DFTA_REQUIRE(ctx, user_size >= (int)(4 * sizeof(int)) && user_size % (int)sizeof(int) == 0 && user_size <= 4096,
-                 "dfta_step_stats::struct_size (set it to sizeof(dfta_step_stats) before the call)");
+    DFTA_REQUIRE(ctx, dfta::versioned_size_ok(user_size, dfta::kStatsMinSize), "dfta_step_stats::struct_size (set it to sizeof(dfta_step_stats) before the call)");
     dfta_step_stats mine;
     dfta_step_stats* const stats = &mine;
     DFTA_HIP(ctx, hipEventSynchronize(s->ev[3]));
@@ -610,8 +441,7 @@ static int scf_fill_stats(dfta_scf* s, const dfta::LevelStats& ls, dfta_poisson*
         vc += vl;
     }
     stats->vcycles = (long)vc;
-    memcpy(user, &mine, std::min<size_t>((size_t)user_size, sizeof(mine)));
-    user->struct_size = user_size;
+    dfta::copy_versioned(user, &mine, user_size, dfta::kStatsMinSize, sizeof(mine), user_size);
     return DFTA_OK;
 }
 
@@ -628,8 +458,8 @@ int dfta_scf_step(dfta_scf* s, dfta_step_stats* stats)
     DFTA_HIP(ctx, hipEventRecord(s->ev[0], st));
     DFTA_HIP(ctx, hipMemsetAsync(s->d_newDensity, 0, sizeof(double) * (size_t)s->nV * N, st));
     dfta::LevelStats ls;
-    // bracket starts: CHAINED hands E-3 from level to level exactly as DFTAtom.cpp:541 (levels one after the other);
-    // BATCHED starts every level concurrently from max(-Z^2-1, min Veff_l) (LevelSolver::clamp_bottoms)
+    // bracket starts: every level solve starts from the bottoms planned at creation, -Z^2-1 (CHAINED hands E-3 from level to level inside
+    // the solver, as DFTAtom.cpp:541; BATCHED clamps them to min Veff_l: LevelSolver::clamp_bottoms)
     // atoms that have met the reference's stop test (DFTAtom.cpp:474-479) are frozen: no level search, no mixing, no
     // Poisson solve, no new energies -- every atom of a batch ends in the state of its own last step
     bool any_frozen = false;
@@ -641,7 +471,7 @@ int dfta_scf_step(dfta_scf* s, dfta_step_stats* stats)
     int rc;
     {
         dfta_range r_levels("dfta: level search (LoopOverLevels: all subshells of the batch)");
-        rc = s->solver.run(s->d_V, s->h_job_bottom.data(), s->levels_mode, s->d_newDensity, stats ? &ls : nullptr,
+        rc = s->solver.run(s->d_V, s->cfg.bottom.data(), s->solver.mode, s->d_newDensity, stats ? &ls : nullptr,
                            any_frozen ? s->h_frozen.data() : nullptr);
     }
     if (rc) return rc;
@@ -649,7 +479,6 @@ int dfta_scf_step(dfta_scf* s, dfta_step_stats* stats)
         std::vector<dfta::Job>& jobs = s->h_jobs;
         rc = s->solver.fetch_jobs(jobs);
         if (rc) return rc;
-        for (size_t k = 0; k < jobs.size(); ++k) s->h_job_bottom[k] = s->h_bottom0[jobs[k].v];
         s->steps_done++;
         if (s->debug_levels) {
             for (size_t k = 0; k < jobs.size(); ++k)
@@ -707,10 +536,10 @@ int dfta_scf_step(dfta_scf* s, dfta_step_stats* stats)
     // Simpson38(1, .) on the logarithmic grid (DFTAtom.cpp:459-467), Simpson38(h, .) on the uniform one (DFTAtom.cpp:167-177)
     // (tolerance mode of the sweeps: the two sums of Simpson 3/8 in parallel, as the normalisation integral of scan_match takes them --
     // 0.44 ms of ordered additions per step otherwise; the energies move by a few 1e-16 relative)
-    if (s->solver.sweep_mode == DFTA_SWEEPS_TOLERANCE && s->integ_rule == DFTA_INT_SIMPSON38 && !dfta_knob("SCF_ORDERED_SUMS"))
+    if (s->solver.sweep_mode == DFTA_SWEEPS_TOLERANCE && s->solver.integ_rule == DFTA_INT_SIMPSON38 && !dfta_knob("SCF_ORDERED_SUMS"))
         rc = dfta_launch_integrate_simpson38_parallel(ctx, g->uniform ? g->h : 1.0, s->d_integrands, N, natoms * 5, (size_t)N, s->d_integrals);
     else
-        rc = dfta_launch_integrate_ordered(ctx, s->integ_rule, g->uniform ? g->h : 1.0, s->d_integrands, N, natoms * 5, (size_t)N, s->d_integrals);
+        rc = dfta_launch_integrate_ordered(ctx, s->solver.integ_rule, g->uniform ? g->h : 1.0, s->d_integrands, N, natoms * 5, (size_t)N, s->d_integrals);
     if (rc) return rc;
     hipLaunchKernelGGL(k_energies, dim3((natoms + 63) / 64), dim3(64), 0, st, s->d_atoms.p, natoms, s->solver.d_jobs.p, s->solver.d_occ.p, s->d_integrals.p,
                        s->d_records.p, s->d_fin.p);
@@ -720,277 +549,6 @@ int dfta_scf_step(dfta_scf* s, dfta_step_stats* stats)
     DFTA_HIP(ctx, hipMemcpyAsync(s->h_atoms.data(), s->d_atoms, sizeof(AtomState) * natoms, hipMemcpyDeviceToHost, st));
     DFTA_HIP(ctx, hipStreamSynchronize(st));
     return stats ? scf_fill_stats(s, ls, ps, stats) : DFTA_OK;
-}
-
-int dfta_scf_get_energies(dfta_scf* s, dfta_energies* e, int* finished)
-{
-    if (!s) return DFTA_ERR_INVALID;
-    dfta_ctx* ctx = s->ctx;
-    DFTA_ENTER(ctx);
-    for (int a = 0; a < s->natoms; ++a) {      // h_atoms is current: every step ends with its copy
-        if (e) e[a] = s->h_atoms[a].e;
-        if (finished) finished[a] = s->h_atoms[a].finished;
-    }
-    return DFTA_OK;
-}
-
-int dfta_scf_info(const dfta_scf* s, int* tree_depth, int* njobs, long* trials_per_round)
-{
-    if (!s) return DFTA_ERR_INVALID;
-    if (tree_depth) *tree_depth = s->solver.depth;
-    if (njobs) *njobs = s->solver.njobs;
-    if (trials_per_round) *trials_per_round = s->solver.ntrials;
-    return DFTA_OK;
-}
-
-int dfta_scf_set_integrator(dfta_scf* s, int rule)
-{
-    if (!s) return DFTA_ERR_INVALID;
-    DFTA_REQUIRE(s->ctx, dfta_integral_shape_ok(rule, s->g->N), "integration rule / grid size");
-    s->integ_rule = rule;
-    s->solver.integ_rule = rule;
-    return DFTA_OK;
-}
-
-int dfta_scf_poisson_info(const dfta_scf* s, int* G, int* degraded, int* aborts)
-{
-    if (!s) return DFTA_ERR_INVALID;
-    return dfta_poisson_group_state(s->poisson, G, degraded, aborts);
-}
-
-int dfta_scf_num_levels(const dfta_scf* s, int atom, int spin)
-{
-    if (!s || atom < 0 || atom >= s->natoms || spin < 0 || spin > 1) return -1;
-    return s->spin_nlev[spin][atom];
-}
-
-int dfta_scf_get_levels(dfta_scf* s, int atom, int spin, int* n, int* l, int* occ, double* E, int* converged)
-{
-    if (!s) return DFTA_ERR_INVALID;
-    dfta_ctx* ctx = s->ctx;
-    DFTA_ENTER(ctx);
-    DFTA_REQUIRE(ctx, atom >= 0 && atom < s->natoms && spin >= 0 && spin < s->nspin, "atom/spin");
-    const std::vector<dfta::Job>& jobs = s->h_jobs;
-    DFTA_REQUIRE(ctx, !jobs.empty(), "no SCF step has run yet");
-    int k0 = s->h_atoms[atom].job_off + (spin ? s->spin_nlev[0][atom] : 0);
-    const int cnt = s->spin_nlev[spin][atom];
-    if (occ)                                     // the whole channel is checked before anything is written
-        for (int k = 0; k < cnt; ++k) {
-            const double o = s->solver.h_occ[k0 + k];
-            DFTA_REQUIRE(ctx, o == std::floor(o), "a fractional occupation: read it with dfta_scf_get_occupations");
-        }
-    for (int k = 0; k < cnt; ++k) {
-        const dfta::Job& j = jobs[k0 + k];
-        if (n) n[k] = j.n;
-        if (l) l[k] = j.l;
-        if (occ) occ[k] = static_cast<int>(s->solver.h_occ[k0 + k]);
-        if (E) E[k] = j.E;
-        if (converged) converged[k] = j.converged;
-    }
-    return DFTA_OK;
-}
-
-int dfta_scf_get_occupations(dfta_scf* s, int atom, int spin, double* occ)
-{
-    if (!s) return DFTA_ERR_INVALID;
-    dfta_ctx* ctx = s->ctx;
-    DFTA_ENTER(ctx);
-    DFTA_REQUIRE(ctx, atom >= 0 && atom < s->natoms && spin >= 0 && spin < s->nspin && occ, "atom/spin/occ");
-    const int k0 = s->h_atoms[atom].job_off + (spin ? s->spin_nlev[0][atom] : 0);
-    for (int k = 0; k < s->spin_nlev[spin][atom]; ++k) occ[k] = s->solver.h_occ[k0 + k];
-    return DFTA_OK;
-}
-
-int dfta_scf_get_level_status(dfta_scf* s, int atom, int spin, int* status, int* n_count, int* n_zero)
-{
-    if (!s) return DFTA_ERR_INVALID;
-    dfta_ctx* ctx = s->ctx;
-    DFTA_ENTER(ctx);
-    DFTA_REQUIRE(ctx, atom >= 0 && atom < s->natoms && spin >= 0 && spin < s->nspin, "atom/spin");
-    const std::vector<dfta::Job>& jobs = s->h_jobs;
-    DFTA_REQUIRE(ctx, !jobs.empty(), "no SCF step has run yet");
-    const int k0 = s->h_atoms[atom].job_off + (spin ? s->spin_nlev[0][atom] : 0);
-    for (int k = 0; k < s->spin_nlev[spin][atom]; ++k) {
-        if (status) status[k] = jobs[k0 + k].status;
-        if (n_count) n_count[k] = jobs[k0 + k].n_count;
-        if (n_zero) n_zero[k] = jobs[k0 + k].n_zero;
-    }
-    return DFTA_OK;
-}
-
-int dfta_scf_get_array(dfta_scf* s, int atom, int which, double* out)
-{
-    if (!s) return DFTA_ERR_INVALID;
-    dfta_ctx* ctx = s->ctx;
-    DFTA_ENTER(ctx);
-    DFTA_REQUIRE(ctx, atom >= 0 && atom < s->natoms && out, "atom/out");
-    const int N = s->g->N;
-    const double* src = nullptr;
-    switch (which) {
-    case 0: src = s->d_density + (size_t)atom * N; break;
-    case 1: src = (s->lsda ? s->d_dA : s->d_density) + (size_t)atom * N; break;
-    case 2: src = (s->lsda ? s->d_dB : s->d_density) + (size_t)atom * N; break;
-    case 3: src = s->d_V + (size_t)atom * s->nspin * N; break;
-    case 4: src = s->d_V + ((size_t)atom * s->nspin + (s->lsda ? 1 : 0)) * N; break;
-    case 5: src = s->d_U + (size_t)atom * N; break;
-    default: DFTA_REQUIRE(ctx, false, "which");
-    }
-    DFTA_HIP(ctx, hipMemcpyAsync(out, src, sizeof(double) * N, hipMemcpyDeviceToHost, ctx->stream));
-    DFTA_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return DFTA_OK;
-}
-
-// first job and number of levels of (atom, spin); the orbitals exist once a step has run
-#define DFTA_SCF_CHANNEL(s, ctx, atom, spin, k0, cnt)                                                              \
-    DFTA_REQUIRE(ctx, s->steps_done > 0, "no SCF step has run yet: there are no orbitals");                        \
-    DFTA_REQUIRE(ctx, atom >= 0 && atom < s->natoms && spin >= 0 && spin < s->nspin, "atom/spin");                 \
-    const int k0 = s->h_atoms[atom].job_off + (spin ? s->spin_nlev[0][atom] : 0), cnt = s->spin_nlev[spin][atom]
-
-int dfta_scf_get_orbitals(dfta_scf* s, int atom, int spin, double* u)
-{
-    if (!s) return DFTA_ERR_INVALID;
-    dfta_ctx* ctx = s->ctx;
-    DFTA_ENTER(ctx);
-    DFTA_SCF_CHANNEL(s, ctx, atom, spin, k0, cnt);
-    DFTA_REQUIRE(ctx, u || cnt == 0, "u");
-    if (cnt == 0) return DFTA_OK;
-    const size_t N = s->g->N;
-    DFTA_HIP(ctx, hipMemcpyAsync(u, s->solver.d_Psi + (size_t)k0 * N, sizeof(double) * cnt * N, hipMemcpyDeviceToHost, ctx->stream));
-    DFTA_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return DFTA_OK;
-}
-
-int dfta_scf_orbital_properties(dfta_scf* s, double* props)
-{
-    if (!s) return DFTA_ERR_INVALID;
-    dfta_ctx* ctx = s->ctx;
-    DFTA_ENTER(ctx);
-    DFTA_REQUIRE(ctx, s->steps_done > 0, "no SCF step has run yet: there are no orbitals");
-    DFTA_REQUIRE(ctx, props, "props");
-    const int njobs = s->solver.njobs;
-    hipStream_t st = ctx->stream;
-    if (!s->d_orb_props.p) {                  // first use: the levels' l and the result rows
-        std::vector<int> hl(njobs);
-        for (int k = 0; k < njobs; ++k) hl[k] = s->h_jobs[k].l;
-        DFTA_HIP(ctx, s->d_orb_l.alloc(njobs));
-        DFTA_HIP(ctx, hipMemcpyAsync(s->d_orb_l.p, hl.data(), sizeof(int) * njobs, hipMemcpyHostToDevice, st));
-        DFTA_HIP(ctx, hipStreamSynchronize(st));          // hl is the source of the copy
-        DFTA_HIP(ctx, s->d_orb_props.alloc((size_t)njobs * DFTA_ORB_PROPS));
-    }
-    const int rc = dfta_launch_orbital_properties(ctx, s->g, njobs, s->d_orb_l.p, s->solver.d_Psi.p, s->d_orb_props.p);
-    if (rc) return rc;
-    DFTA_HIP(ctx, hipMemcpyAsync(props, s->d_orb_props.p, sizeof(double) * njobs * DFTA_ORB_PROPS, hipMemcpyDeviceToHost, st));
-    DFTA_HIP(ctx, hipStreamSynchronize(st));
-    return DFTA_OK;
-}
-
-int dfta_scf_orbital_matrix(dfta_scf* s, int atom, int spin, int k, double* M)
-{
-    if (!s) return DFTA_ERR_INVALID;
-    dfta_ctx* ctx = s->ctx;
-    DFTA_ENTER(ctx);
-    DFTA_SCF_CHANNEL(s, ctx, atom, spin, k0, cnt);
-    DFTA_REQUIRE(ctx, k >= 0 && k <= 2, "k (0, 1 or 2)");
-    DFTA_REQUIRE(ctx, M || cnt == 0, "M");
-    if (cnt == 0) return DFTA_OK;
-    if (!s->orb_scratch.norb_max) {           // first use: scratch for the longest channel of the batch
-        int most = 1;
-        for (int a = 0; a < s->natoms; ++a) most = std::max(most, std::max(s->spin_nlev[0][a], s->spin_nlev[1][a]));
-        const int rc = dfta_orbital_scratch_create(ctx, s->g, most, &s->orb_scratch);
-        if (rc) return rc;
-    }
-    hipStream_t st = ctx->stream;
-    const int rc = dfta_launch_orbital_matrix(ctx, s->g, cnt, s->solver.d_Psi + (size_t)k0 * s->g->N, k, s->orb_scratch.slab.p,
-                                              s->orb_scratch.ticket.p, s->orb_scratch.M.p);
-    if (rc) return rc;
-    DFTA_HIP(ctx, hipMemcpyAsync(M, s->orb_scratch.M.p, sizeof(double) * cnt * cnt, hipMemcpyDeviceToHost, st));
-    DFTA_HIP(ctx, hipStreamSynchronize(st));
-    return DFTA_OK;
-}
-#undef DFTA_SCF_CHANNEL
-
-// ---- Slater integrals of the SCF's orbitals (slater.hip; the orbitals are read in place) ---------------------------------------------
-// first job and number of orbitals of an atom (alpha levels, then beta levels) and their l; the orbitals exist once a step has run
-#define DFTA_SCF_ATOM(s, ctx, atom, k0, norb)                                                                      \
-    DFTA_REQUIRE(ctx, s->steps_done > 0, "no SCF step has run yet: there are no orbitals");                        \
-    DFTA_REQUIRE(ctx, atom >= 0 && atom < s->natoms, "atom");                                                      \
-    DFTA_REQUIRE(ctx, s->g->N >= 5, "Slater integrals need a grid of 5 nodes");                                     \
-    const int k0 = s->h_atoms[atom].job_off, norb = s->spin_nlev[0][atom] + s->spin_nlev[1][atom]
-
-int dfta_scf_slater_rk(dfta_scf* s, int atom, int njobs, const int* jobs, double* R)
-{
-    if (!s) return DFTA_ERR_INVALID;
-    dfta_ctx* ctx = s->ctx;
-    DFTA_ENTER(ctx);
-    DFTA_SCF_ATOM(s, ctx, atom, k0, norb);
-    DFTA_REQUIRE(ctx, njobs >= 0, "njobs");
-    if (njobs == 0) return DFTA_OK;
-    DFTA_REQUIRE(ctx, jobs && R, "jobs / R");
-    if (const char* msg = dfta_slater::check_jobs(norb, njobs, jobs)) DFTA_REQUIRE(ctx, false, msg);
-    return s->slater.run(ctx, s->g, s->solver.d_Psi + (size_t)k0 * s->g->N, njobs, jobs, R);
-}
-
-int dfta_scf_slater_fg(dfta_scf* s, int atom, int spin, double* F, double* G)
-{
-    if (!s) return DFTA_ERR_INVALID;
-    dfta_ctx* ctx = s->ctx;
-    DFTA_ENTER(ctx);
-    DFTA_SCF_ATOM(s, ctx, atom, k0, norb);
-    (void)norb;
-    DFTA_REQUIRE(ctx, spin >= 0 && spin < s->nspin, "spin");
-    const int c0 = k0 + (spin ? s->spin_nlev[0][atom] : 0), cnt = s->spin_nlev[spin][atom];
-    DFTA_REQUIRE(ctx, (F && G) || cnt == 0, "F / G");
-    if (cnt == 0) return DFTA_OK;
-    std::vector<int> l(cnt);
-    for (int a = 0; a < cnt; ++a) l[a] = s->h_jobs[c0 + a].l;
-    const int njobs = dfta_slater::fg_jobs(cnt, l.data(), nullptr, nullptr);
-    DFTA_REQUIRE(ctx, njobs >= 0, "Slater table: an orbital with l > 4");
-    std::vector<int> jobs((size_t)njobs * dfta_slater::kJobInts), kinds(njobs);
-    std::vector<double> R(njobs);
-    dfta_slater::fg_jobs(cnt, l.data(), jobs.data(), kinds.data());
-    const int rc = s->slater.run(ctx, s->g, s->solver.d_Psi + (size_t)c0 * s->g->N, njobs, jobs.data(), R.data());
-    if (rc) return rc;
-    const size_t plane = (size_t)cnt * cnt;
-    std::fill(F, F + (DFTA_SLATER_KMAX + 1) * plane, 0.);
-    std::fill(G, G + (DFTA_SLATER_KMAX + 1) * plane, 0.);
-    for (int j = 0; j < njobs; ++j) {             // each value once, mirrored; G^k(a,a) is F^k(a,a)
-        const int a = jobs[(size_t)j * dfta_slater::kJobInts], b = jobs[(size_t)j * dfta_slater::kJobInts + 1];
-        const int k = jobs[(size_t)j * dfta_slater::kJobInts + 4];
-        double* T = kinds[j] == dfta_slater::kKindF ? F : G;
-        T[k * plane + (size_t)a * cnt + b] = T[k * plane + (size_t)b * cnt + a] = R[j];
-        if (a == b) G[k * plane + (size_t)a * cnt + a] = R[j];
-    }
-    return DFTA_OK;
-}
-
-int dfta_scf_coulomb_exchange(dfta_scf* s, int atom, double* EH, double* EXX)
-{
-    if (!s) return DFTA_ERR_INVALID;
-    dfta_ctx* ctx = s->ctx;
-    DFTA_ENTER(ctx);
-    DFTA_SCF_ATOM(s, ctx, atom, k0, norb);
-    DFTA_REQUIRE(ctx, EH && EXX, "EH / EXX");
-    std::vector<int> l(norb);
-    for (int a = 0; a < norb; ++a) l[a] = s->h_jobs[k0 + a].l;
-    dfta_slater::EnergyPlan plan;
-    DFTA_REQUIRE(ctx, dfta_slater::plan_energy(s->spin_nlev[0][atom], s->spin_nlev[1][atom], l.data(), &plan) == 0,
-                 "exchange energy: an orbital with l > 4");
-    std::vector<double> R(plan.njobs());
-    const int rc = s->slater.run(ctx, s->g, s->solver.d_Psi + (size_t)k0 * s->g->N, plan.njobs(), plan.jobs.data(), R.data());
-    if (rc) return rc;
-    dfta_slater::energy_sums(plan, s->solver.h_occ.data() + k0, s->lsda, R.data(), EH, EXX);
-    return DFTA_OK;
-}
-#undef DFTA_SCF_ATOM
-
-int dfta_scf_get_records_dev(dfta_scf* s, double* dRecords)
-{
-    if (!s || !dRecords) return DFTA_ERR_INVALID;
-    dfta_ctx* ctx = s->ctx;
-    DFTA_ENTER(ctx);
-    DFTA_HIP(ctx, hipMemcpyAsync(dRecords, s->d_records, sizeof(double) * (size_t)s->natoms * DFTA_RECORD_DOUBLES,
-                                 hipMemcpyDeviceToDevice, ctx->stream));
-    return DFTA_OK;
 }
 
 }  // extern "C"

@@ -1,0 +1,282 @@
+// scf_api.cpp -- the read-only C ABI of the SCF layer (include/dftatom_hip.h): the accessors of a batch's state (scf_state.h) and the
+// post-SCF analysis entries on its orbitals (orbitals.hip, slater.hip).  Host code only: what runs on the device is launched through the
+// dfta_launch_* helpers (internal.h).  What an entry accepts and rejects is its own and stays in the entry.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <vector>
+
+#include "scf_state.h"
+#include "slater_plan.h"
+#include "xc.h"             // dfta_poisson_group_state
+
+extern "C" {
+
+int dfta_scf_get_energies(dfta_scf* s, dfta_energies* e, int* finished)
+{
+    if (!s) return DFTA_ERR_INVALID;
+    dfta_ctx* ctx = s->ctx;
+    DFTA_ENTER(ctx);
+    for (int a = 0; a < s->natoms; ++a) {      // h_atoms is current: every step ends with its copy
+        if (e) e[a] = s->h_atoms[a].e;
+        if (finished) finished[a] = s->h_atoms[a].finished;
+    }
+    return DFTA_OK;
+}
+
+int dfta_scf_info(const dfta_scf* s, int* tree_depth, int* njobs, long* trials_per_round)
+{
+    if (!s) return DFTA_ERR_INVALID;
+    if (tree_depth) *tree_depth = s->solver.depth;
+    if (njobs) *njobs = s->solver.njobs;
+    if (trials_per_round) *trials_per_round = s->solver.ntrials;
+    return DFTA_OK;
+}
+
+int dfta_scf_set_integrator(dfta_scf* s, int rule)
+{
+    if (!s) return DFTA_ERR_INVALID;
+    DFTA_REQUIRE(s->ctx, dfta_integral_shape_ok(rule, s->g->N), "integration rule / grid size");
+    s->solver.integ_rule = rule;
+    return DFTA_OK;
+}
+
+int dfta_scf_poisson_info(const dfta_scf* s, int* G, int* degraded, int* aborts)
+{
+    if (!s) return DFTA_ERR_INVALID;
+    return dfta_poisson_group_state(s->poisson, G, degraded, aborts);
+}
+
+int dfta_scf_num_levels(const dfta_scf* s, int atom, int spin)
+{
+    if (!s || atom < 0 || atom >= s->natoms || spin < 0 || spin > 1) return -1;
+    return s->cfg.nlev[spin][atom];
+}
+
+int dfta_scf_get_levels(dfta_scf* s, int atom, int spin, int* n, int* l, int* occ, double* E, int* converged)
+{
+    if (!s) return DFTA_ERR_INVALID;
+    dfta_ctx* ctx = s->ctx;
+    DFTA_ENTER(ctx);
+    DFTA_REQUIRE(ctx, atom >= 0 && atom < s->natoms && spin >= 0 && spin < s->nspin, "atom/spin");
+    const std::vector<dfta::Job>& jobs = s->h_jobs;
+    DFTA_REQUIRE(ctx, !jobs.empty(), "no SCF step has run yet");
+    const auto [k0, cnt] = s->channel(atom, spin);
+    if (occ)                                     // the whole channel is checked before anything is written
+        for (int k = 0; k < cnt; ++k) {
+            const double o = s->solver.h_occ[k0 + k];
+            DFTA_REQUIRE(ctx, o == std::floor(o), "a fractional occupation: read it with dfta_scf_get_occupations");
+        }
+    for (int k = 0; k < cnt; ++k) {
+        const dfta::Job& j = jobs[k0 + k];
+        if (n) n[k] = j.n;
+        if (l) l[k] = j.l;
+        if (occ) occ[k] = static_cast<int>(s->solver.h_occ[k0 + k]);
+        if (E) E[k] = j.E;
+        if (converged) converged[k] = j.converged;
+    }
+    return DFTA_OK;
+}
+
+int dfta_scf_get_occupations(dfta_scf* s, int atom, int spin, double* occ)
+{
+    if (!s) return DFTA_ERR_INVALID;
+    dfta_ctx* ctx = s->ctx;
+    DFTA_ENTER(ctx);
+    DFTA_REQUIRE(ctx, atom >= 0 && atom < s->natoms && spin >= 0 && spin < s->nspin && occ, "atom/spin/occ");
+    const auto [k0, cnt] = s->channel(atom, spin);
+    for (int k = 0; k < cnt; ++k) occ[k] = s->solver.h_occ[k0 + k];
+    return DFTA_OK;
+}
+
+int dfta_scf_get_level_status(dfta_scf* s, int atom, int spin, int* status, int* n_count, int* n_zero)
+{
+    if (!s) return DFTA_ERR_INVALID;
+    dfta_ctx* ctx = s->ctx;
+    DFTA_ENTER(ctx);
+    DFTA_REQUIRE(ctx, atom >= 0 && atom < s->natoms && spin >= 0 && spin < s->nspin, "atom/spin");
+    const std::vector<dfta::Job>& jobs = s->h_jobs;
+    DFTA_REQUIRE(ctx, !jobs.empty(), "no SCF step has run yet");
+    const auto [k0, cnt] = s->channel(atom, spin);
+    for (int k = 0; k < cnt; ++k) {
+        if (status) status[k] = jobs[k0 + k].status;
+        if (n_count) n_count[k] = jobs[k0 + k].n_count;
+        if (n_zero) n_zero[k] = jobs[k0 + k].n_zero;
+    }
+    return DFTA_OK;
+}
+
+int dfta_scf_get_array(dfta_scf* s, int atom, int which, double* out)
+{
+    if (!s) return DFTA_ERR_INVALID;
+    dfta_ctx* ctx = s->ctx;
+    DFTA_ENTER(ctx);
+    DFTA_REQUIRE(ctx, atom >= 0 && atom < s->natoms && out, "atom/out");
+    const int N = s->g->N;
+    const double* src = nullptr;
+    switch (which) {
+    case 0: src = s->d_density + (size_t)atom * N; break;
+    case 1: src = (s->lsda ? s->d_dA : s->d_density) + (size_t)atom * N; break;
+    case 2: src = (s->lsda ? s->d_dB : s->d_density) + (size_t)atom * N; break;
+    case 3: src = s->d_V + (size_t)atom * s->nspin * N; break;
+    case 4: src = s->d_V + ((size_t)atom * s->nspin + (s->lsda ? 1 : 0)) * N; break;
+    case 5: src = s->d_U + (size_t)atom * N; break;
+    default: DFTA_REQUIRE(ctx, false, "which");
+    }
+    DFTA_HIP(ctx, hipMemcpyAsync(out, src, sizeof(double) * N, hipMemcpyDeviceToHost, ctx->stream));
+    DFTA_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return DFTA_OK;
+}
+
+// ---- the orbitals of the last step (they exist once a step has run) -------------------------------------------------------------------
+int dfta_scf_get_orbitals(dfta_scf* s, int atom, int spin, double* u)
+{
+    if (!s) return DFTA_ERR_INVALID;
+    dfta_ctx* ctx = s->ctx;
+    DFTA_ENTER(ctx);
+    DFTA_REQUIRE(ctx, s->steps_done > 0, "no SCF step has run yet: there are no orbitals");
+    DFTA_REQUIRE(ctx, atom >= 0 && atom < s->natoms && spin >= 0 && spin < s->nspin, "atom/spin");
+    const auto [k0, cnt] = s->channel(atom, spin);
+    DFTA_REQUIRE(ctx, u || cnt == 0, "u");
+    if (cnt == 0) return DFTA_OK;
+    const size_t N = s->g->N;
+    DFTA_HIP(ctx, hipMemcpyAsync(u, s->solver.d_Psi + (size_t)k0 * N, sizeof(double) * cnt * N, hipMemcpyDeviceToHost, ctx->stream));
+    DFTA_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return DFTA_OK;
+}
+
+int dfta_scf_orbital_properties(dfta_scf* s, double* props)
+{
+    if (!s) return DFTA_ERR_INVALID;
+    dfta_ctx* ctx = s->ctx;
+    DFTA_ENTER(ctx);
+    DFTA_REQUIRE(ctx, s->steps_done > 0, "no SCF step has run yet: there are no orbitals");
+    DFTA_REQUIRE(ctx, props, "props");
+    const int njobs = s->solver.njobs;
+    hipStream_t st = ctx->stream;
+    if (!s->d_orb_props.p) {                  // first use: the levels' l and the result rows
+        std::vector<int> hl(njobs);
+        for (int k = 0; k < njobs; ++k) hl[k] = s->h_jobs[k].l;
+        DFTA_HIP(ctx, s->d_orb_l.alloc(njobs));
+        DFTA_HIP(ctx, hipMemcpyAsync(s->d_orb_l.p, hl.data(), sizeof(int) * njobs, hipMemcpyHostToDevice, st));
+        DFTA_HIP(ctx, hipStreamSynchronize(st));          // hl is the source of the copy
+        DFTA_HIP(ctx, s->d_orb_props.alloc((size_t)njobs * DFTA_ORB_PROPS));
+    }
+    const int rc = dfta_launch_orbital_properties(ctx, s->g, njobs, s->d_orb_l.p, s->solver.d_Psi.p, s->d_orb_props.p);
+    if (rc) return rc;
+    DFTA_HIP(ctx, hipMemcpyAsync(props, s->d_orb_props.p, sizeof(double) * njobs * DFTA_ORB_PROPS, hipMemcpyDeviceToHost, st));
+    DFTA_HIP(ctx, hipStreamSynchronize(st));
+    return DFTA_OK;
+}
+
+int dfta_scf_orbital_matrix(dfta_scf* s, int atom, int spin, int k, double* M)
+{
+    if (!s) return DFTA_ERR_INVALID;
+    dfta_ctx* ctx = s->ctx;
+    DFTA_ENTER(ctx);
+    DFTA_REQUIRE(ctx, s->steps_done > 0, "no SCF step has run yet: there are no orbitals");
+    DFTA_REQUIRE(ctx, atom >= 0 && atom < s->natoms && spin >= 0 && spin < s->nspin, "atom/spin");
+    const auto [k0, cnt] = s->channel(atom, spin);
+    DFTA_REQUIRE(ctx, k >= 0 && k <= 2, "k (0, 1 or 2)");
+    DFTA_REQUIRE(ctx, M || cnt == 0, "M");
+    if (cnt == 0) return DFTA_OK;
+    if (!s->orb_scratch.norb_max) {           // first use: scratch for the longest channel of the batch
+        int most = 1;
+        for (int a = 0; a < s->natoms; ++a) most = std::max(most, std::max(s->cfg.nlev[0][a], s->cfg.nlev[1][a]));
+        const int rc = dfta_orbital_scratch_create(ctx, s->g, most, &s->orb_scratch);
+        if (rc) return rc;
+    }
+    hipStream_t st = ctx->stream;
+    const int rc = dfta_launch_orbital_matrix(ctx, s->g, cnt, s->solver.d_Psi + (size_t)k0 * s->g->N, k, s->orb_scratch.slab.p,
+                                              s->orb_scratch.ticket.p, s->orb_scratch.M.p);
+    if (rc) return rc;
+    DFTA_HIP(ctx, hipMemcpyAsync(M, s->orb_scratch.M.p, sizeof(double) * cnt * cnt, hipMemcpyDeviceToHost, st));
+    DFTA_HIP(ctx, hipStreamSynchronize(st));
+    return DFTA_OK;
+}
+
+// ---- Slater integrals of the SCF's orbitals (slater.hip; the orbitals are read in place) ---------------------------------------------
+int dfta_scf_slater_rk(dfta_scf* s, int atom, int njobs, const int* jobs, double* R)
+{
+    if (!s) return DFTA_ERR_INVALID;
+    dfta_ctx* ctx = s->ctx;
+    DFTA_ENTER(ctx);
+    DFTA_REQUIRE(ctx, s->steps_done > 0, "no SCF step has run yet: there are no orbitals");
+    DFTA_REQUIRE(ctx, atom >= 0 && atom < s->natoms, "atom");
+    DFTA_REQUIRE(ctx, s->g->N >= 5, "Slater integrals need a grid of 5 nodes");
+    const auto [k0, norb] = s->atom_jobs(atom);
+    DFTA_REQUIRE(ctx, njobs >= 0, "njobs");
+    if (njobs == 0) return DFTA_OK;
+    DFTA_REQUIRE(ctx, jobs && R, "jobs / R");
+    if (const char* msg = dfta_slater::check_jobs(norb, njobs, jobs)) DFTA_REQUIRE(ctx, false, msg);
+    return s->slater.run(ctx, s->g, s->solver.d_Psi + (size_t)k0 * s->g->N, njobs, jobs, R);
+}
+
+int dfta_scf_slater_fg(dfta_scf* s, int atom, int spin, double* F, double* G)
+{
+    if (!s) return DFTA_ERR_INVALID;
+    dfta_ctx* ctx = s->ctx;
+    DFTA_ENTER(ctx);
+    DFTA_REQUIRE(ctx, s->steps_done > 0, "no SCF step has run yet: there are no orbitals");
+    DFTA_REQUIRE(ctx, atom >= 0 && atom < s->natoms, "atom");
+    DFTA_REQUIRE(ctx, s->g->N >= 5, "Slater integrals need a grid of 5 nodes");
+    DFTA_REQUIRE(ctx, spin >= 0 && spin < s->nspin, "spin");
+    const auto [c0, cnt] = s->channel(atom, spin);
+    DFTA_REQUIRE(ctx, (F && G) || cnt == 0, "F / G");
+    if (cnt == 0) return DFTA_OK;
+    std::vector<int> l(cnt);
+    for (int a = 0; a < cnt; ++a) l[a] = s->h_jobs[c0 + a].l;
+    const int njobs = dfta_slater::fg_jobs(cnt, l.data(), nullptr, nullptr);
+    DFTA_REQUIRE(ctx, njobs >= 0, "Slater table: an orbital with l > 4");
+    std::vector<int> jobs((size_t)njobs * dfta_slater::kJobInts), kinds(njobs);
+    std::vector<double> R(njobs);
+    dfta_slater::fg_jobs(cnt, l.data(), jobs.data(), kinds.data());
+    const int rc = s->slater.run(ctx, s->g, s->solver.d_Psi + (size_t)c0 * s->g->N, njobs, jobs.data(), R.data());
+    if (rc) return rc;
+    const size_t plane = (size_t)cnt * cnt;
+    std::fill(F, F + (DFTA_SLATER_KMAX + 1) * plane, 0.);
+    std::fill(G, G + (DFTA_SLATER_KMAX + 1) * plane, 0.);
+    for (int j = 0; j < njobs; ++j) {             // each value once, mirrored; G^k(a,a) is F^k(a,a)
+        const int a = jobs[(size_t)j * dfta_slater::kJobInts], b = jobs[(size_t)j * dfta_slater::kJobInts + 1];
+        const int k = jobs[(size_t)j * dfta_slater::kJobInts + 4];
+        double* T = kinds[j] == dfta_slater::kKindF ? F : G;
+        T[k * plane + (size_t)a * cnt + b] = T[k * plane + (size_t)b * cnt + a] = R[j];
+        if (a == b) G[k * plane + (size_t)a * cnt + a] = R[j];
+    }
+    return DFTA_OK;
+}
+
+int dfta_scf_coulomb_exchange(dfta_scf* s, int atom, double* EH, double* EXX)
+{
+    if (!s) return DFTA_ERR_INVALID;
+    dfta_ctx* ctx = s->ctx;
+    DFTA_ENTER(ctx);
+    DFTA_REQUIRE(ctx, s->steps_done > 0, "no SCF step has run yet: there are no orbitals");
+    DFTA_REQUIRE(ctx, atom >= 0 && atom < s->natoms, "atom");
+    DFTA_REQUIRE(ctx, s->g->N >= 5, "Slater integrals need a grid of 5 nodes");
+    const auto [k0, norb] = s->atom_jobs(atom);
+    DFTA_REQUIRE(ctx, EH && EXX, "EH / EXX");
+    std::vector<int> l(norb);
+    for (int a = 0; a < norb; ++a) l[a] = s->h_jobs[k0 + a].l;
+    dfta_slater::EnergyPlan plan;
+    DFTA_REQUIRE(ctx, dfta_slater::plan_energy(s->cfg.nlev[0][atom], s->cfg.nlev[1][atom], l.data(), &plan) == 0,
+                 "exchange energy: an orbital with l > 4");
+    std::vector<double> R(plan.njobs());
+    const int rc = s->slater.run(ctx, s->g, s->solver.d_Psi + (size_t)k0 * s->g->N, plan.njobs(), plan.jobs.data(), R.data());
+    if (rc) return rc;
+    dfta_slater::energy_sums(plan, s->solver.h_occ.data() + k0, s->lsda, R.data(), EH, EXX);
+    return DFTA_OK;
+}
+
+int dfta_scf_get_records_dev(dfta_scf* s, double* dRecords)
+{
+    if (!s || !dRecords) return DFTA_ERR_INVALID;
+    dfta_ctx* ctx = s->ctx;
+    DFTA_ENTER(ctx);
+    DFTA_HIP(ctx, hipMemcpyAsync(dRecords, s->d_records, sizeof(double) * (size_t)s->natoms * DFTA_RECORD_DOUBLES,
+                                 hipMemcpyDeviceToDevice, ctx->stream));
+    return DFTA_OK;
+}
+
+}  // extern "C"

@@ -4,8 +4,9 @@
 //   * oracle/dfta_oracle.c (the test oracle): grid, sweeps, level driver, multigrid pieces and a full solve, VWN LDA / LSDA, the five
 //     quadrature rules, Aufbau for Z = 1..118, two SCF steps of argon (LDA and LSDA) -- and a known answer: Ar LDA Etotal of step 0
 //     against the compiled reference's 17-digit value (tests/golden).
-//   * dftatom_amd/csrc/ctx_grid.cpp (host code of the product: grid tables, Aufbau, spin split) compiled with g++ against the HIP
-//     headers: dfta_get_subshells / dfta_split_spin(_ex) for Z = 1..118, compared with the oracle's.  No device call is made.
+//   * dftatom_amd/csrc/ctx_grid.cpp (host code of the product: grid tables) compiled with g++ against the HIP headers, and
+//     scf_config.cpp (Aufbau, spin split): dfta_get_subshells / dfta_split_spin(_ex) for Z = 1..118, compared with the oracle's.
+//     No device call is made.
 //
 // Built and run by tests/test_sanitizers.py (make -C oracle sanitize); exit code 0 and an empty sanitizer report = pass.
 #include <cmath>

@@ -1,7 +1,8 @@
 """CPU suite: the CPU-side code under AddressSanitizer + UndefinedBehaviorSanitizer.
 
-`make -C oracle sanitize` builds oracle/dfta_oracle.c, dftatom_amd/csrc/ctx_grid.cpp (the product's host code, compiled with g++
-against the HIP headers) and oracle/sanitize_main.cpp with -fsanitize=address,undefined; the driver exercises sweeps, the level
+`make -C oracle sanitize` builds oracle/dfta_oracle.c, the product's host code -- dftatom_amd/csrc/ctx_grid.cpp (context and grid
+tables, compiled with g++ against the HIP headers) and scf_config.cpp (Aufbau, spin split, configurations; plain C++, held to the code
+it replaced by tests/test_scf_config.py) -- and oracle/sanitize_main.cpp with -fsanitize=address,undefined; the driver exercises sweeps, the level
 driver, a multigrid solve, VWN, the quadrature rules, Aufbau / spin split for Z = 1..118 (oracle vs product) and two SCF steps of
 argon in LDA and LSDA.  Pass = exit code 0 and nothing on the sanitizers' report stream.  (GPU sanitizers are not available on the
 pool; the HIP kernels are covered by the parity suite.)
