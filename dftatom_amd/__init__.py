@@ -35,6 +35,8 @@ ORB_PROPS = 8
 ORB_NORM, ORB_RM1, ORB_R1, ORB_R2, ORB_R4, ORB_T, ORB_RPEAK, ORB_RM3 = range(8)
 SLATER_KMAX = 8                        # DFTA_SLATER_KMAX: largest k of a Slater integral R^k
 SLATER_F, SLATER_G = 0, 1              # kinds of slater_fg_jobs
+BT_DENSITY, BT_ORBITAL = 0, 1          # DFTA_BT_*: kinds of bessel_transform
+BESSEL_LMAX = 4                        # DFTA_BESSEL_LMAX: largest order of sph_bessel / bessel_transform
 
 c_dp = C.POINTER(C.c_double)
 c_ip = C.POINTER(C.c_int)
@@ -165,6 +167,10 @@ SIGNATURES = {
     "dfta_scf_slater_rk": (C.c_int, [vp, C.c_int, C.c_int, c_ip, c_dp]),
     "dfta_scf_slater_fg": (C.c_int, [vp, C.c_int, C.c_int, c_dp, c_dp]),
     "dfta_scf_coulomb_exchange": (C.c_int, [vp, C.c_int, c_dp, c_dp]),
+    "dfta_sph_bessel": (C.c_int, [vp, C.c_int, C.c_size_t, c_dp, c_dp]),
+    "dfta_bessel_transform": (C.c_int, [vp, vp, C.c_int, C.c_int, c_ip, c_dp, C.c_int, c_dp, c_dp]),
+    "dfta_scf_form_factors": (C.c_int, [vp, C.c_int, c_dp, c_dp]),
+    "dfta_scf_momentum_orbitals": (C.c_int, [vp, C.c_int, c_dp, c_dp]),
 }
 
 _lib = None
@@ -620,6 +626,28 @@ def slater_rk(ctx, grid, u, jobs):
     return R
 
 
+def sph_bessel(ctx, l, x):
+    """dfta_sph_bessel: the device's spherical Bessel function j_l (0 <= l <= BESSEL_LMAX) at the arguments x >= 0, in x's shape"""
+    x = _f64(x)
+    out = np.zeros(x.shape)
+    ctx.check(ctx.lib.dfta_sph_bessel(ctx.h, int(l), x.size, _dp(x), _dp(out)))
+    return out
+
+
+def bessel_transform(ctx, grid, kind, l, f, q):
+    """dfta_bessel_transform: rows f of shape (nrow, N) with orders l at the momenta q (nq,), every (row, q) in one launch: (nrow, nq).
+    BT_DENSITY: 4 pi Q[f r^2 j_l(q r) dr/di] (f = rho, l = 0: the X-ray form factor); BT_ORBITAL: sqrt(2/pi) Q[f r j_l(q r) dr/di]
+    (f = u_nl = r R_nl: the momentum-space radial function)."""
+    f = _f64(f).reshape(-1, grid.N)
+    l = _i32(np.atleast_1d(l))
+    q = _f64(np.atleast_1d(q))
+    if len(l) != f.shape[0]:
+        raise ValueError("%d orders for %d rows" % (len(l), f.shape[0]))
+    out = np.zeros((f.shape[0], len(q)))
+    ctx.check(ctx.lib.dfta_bessel_transform(ctx.h, grid.h, int(kind), f.shape[0], _ip(l), _dp(f), len(q), _dp(q), _dp(out)))
+    return out
+
+
 class Mixer:
     """The SCF's density-mixing stage on its own (dfta_mixer): the launches dfta_scf_step issues for `mixing`, on the caller's arrays."""
 
@@ -794,6 +822,22 @@ class Scf:
         eh, ex = C.c_double(), C.c_double()
         self.ctx.check(self.ctx.lib.dfta_scf_coulomb_exchange(self.h, int(atom), C.byref(eh), C.byref(ex)))
         return eh.value, ex.value
+
+    def form_factors(self, q):
+        """(natoms, nchan, nq): f(q) = 4 pi Q[rho j_0(q r) r^2 dr/di] of every atom's densities as array(0 / 1 / 2) holds them now, read
+        in place, one launch; nchan = 1 (LDA: rho) or 3 (LSDA: rho, rho_a, rho_b -- f_a - f_b is the magnetic form factor)"""
+        q = _f64(np.atleast_1d(q))
+        out = np.zeros((self.natoms, 3 if self.lsda else 1, len(q)))
+        self.ctx.check(self.ctx.lib.dfta_scf_form_factors(self.h, len(q), _dp(q), _dp(out)))
+        return out
+
+    def momentum_orbitals(self, q):
+        """(values, jobs): values (njobs, nq), the momentum-space radial functions sqrt(2/pi) Q[u_nl j_l(q r) r dr/di] of every orbital
+        of the batch from one launch, jobs = orbital_jobs()"""
+        q = _f64(np.atleast_1d(q))
+        out = np.zeros((self.njobs, len(q)))
+        self.ctx.check(self.ctx.lib.dfta_scf_momentum_orbitals(self.h, len(q), _dp(q), _dp(out)))
+        return out, self.orbital_jobs()
 
     def set_integrator(self, rule):
         """INT_TRAPEZOID .. INT_ROMBERG: quadrature of the energy integrals and of the orbitals' normalisation."""

@@ -22,6 +22,9 @@ int DFTAtom::mixing = DFTA_MIX_LINEAR;     // --mixing=anderson: Anderson densit
 std::ostream* DFTAtom::jsonOut = nullptr;
 bool DFTAtom::orbitalTable = false;        // --orbital-table
 bool DFTAtom::slaterTable = false;         // --slater-table
+bool DFTAtom::formFactorTable = false;     // --form-factor-table[=smax:ns]
+double DFTAtom::formFactorSmax = 2.0;
+int DFTAtom::formFactorPoints = 41;
 
 namespace {
 struct LevelLine { int n, l; double occ, E; int status, n_count, n_zero; };
@@ -132,6 +135,25 @@ void print_slater_table(dfta_scf* scf, bool lsda)
     std::cout << "EHartree = " << std::fixed << std::setprecision(6) << EH << " EXX = " << EXX << std::endl << std::endl;
 }
 
+// --form-factor-table: f(q) of the converged density at s_k = smax k / (ns - 1), q = ((4 pi) s) 0.529177210903 (s in 1 / Angstrom, q in
+// atomic units), every q in one launch (dfta_scf_form_factors); LSDA: the magnetic form factor f_a - f_b beside it
+void print_form_factor_table(dfta_scf* scf, bool lsda)
+{
+    const int ns = DFTAtom::formFactorPoints, nchan = lsda ? 3 : 1;
+    std::vector<double> s(ns), q(ns), f(static_cast<size_t>(nchan) * ns);
+    for (int k = 0; k < ns; ++k) {
+        s[k] = ns > 1 ? DFTAtom::formFactorSmax * k / (ns - 1) : 0.;
+        q[k] = ((4. * M_PI) * s[k]) * 0.529177210903;
+    }
+    if (dfta_scf_form_factors(scf, ns, q.data(), f.data()) != DFTA_OK) throw std::runtime_error("dfta_scf_form_factors");
+    for (int k = 0; k < ns; ++k) {
+        std::cout << "FormFactor s = " << std::fixed << std::setprecision(6) << s[k] << " q = " << q[k] << " f = " << f[k];
+        if (lsda) std::cout << " fa-fb = " << f[ns + k] - f[2 * ns + k];
+        std::cout << std::endl;
+    }
+    std::cout << std::endl;
+}
+
 void print_configuration(std::vector<LevelLine> levels)
 {
     // levels sorted by energy for the final configuration line (DFTAtom.cpp:487-490)
@@ -191,6 +213,7 @@ void DFTAtom::Run(bool lsda, bool uniform, int Z, int MultigridLevels, double al
             std::cout << std::endl << "Finished!" << std::endl << std::endl;
             if (orbitalTable) print_orbital_table(scf, lsda);
             if (slaterTable) print_slater_table(scf, lsda);
+            if (formFactorTable) print_form_factor_table(scf, lsda);
             break;
         }
         std::cout << "********************************************************************************" << std::endl;

@@ -17,12 +17,17 @@
 // --slater-table: after "Finished!" (and the orbital table), one line per Slater integral F^k(a,b), G^k(a,b) of the levels (per spin
 //                channel with LSDA), then one line with the Hartree energy and the exact-exchange energy of the orbitals (atomic units;
 //                include/dftatom_hip.h: dfta_scf_slater_fg, dfta_scf_coulomb_exchange).  Without it the output is unchanged.
+// --form-factor-table[=smax:ns]: after "Finished!" (and the other tables), one line per s = sin(theta) / lambda = smax k / (ns - 1), k = 0 ..
+//                ns - 1 (1 / Angstrom; default 0 .. 2 in 41 points): s, q = 4 pi s 0.529177210903 (atomic units) and the X-ray form factor
+//                f(q) of the converged density; LSDA adds the magnetic form factor f_a - f_b (include/dftatom_hip.h:
+//                dfta_scf_form_factors, one launch for the table).  Without it the output is unchanged.
 // --sweeps=exact|tolerance, --poisson=exact|tolerance|adaptive: the opt-in tolerance modes of the device path (include/dftatom_hip.h).
 // --mixing=linear (default, the reference's density mixing) | anderson (Anderson acceleration: about half the SCF steps, same protocol).
 // --xc=vwn (default, what the reference runs) | chachiyo | chachiyo-improved (LDA only) | pw92 | pbe (logarithmic grid only).
 // --charge=q: the cation X^q+ (electrons leave the subshell of highest n, then highest l: Fe+ = [Ar] 3d6 4s1);
 // --config="[Ne] 3s2 3p5.5": an explicit, possibly fractional configuration ("2p3/1": LSDA alpha / beta split).  An invalid
 // configuration exits with code 2 before anything runs.
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
@@ -95,6 +100,19 @@ int main(int argc, char** argv)
             DFT::DFTAtom::orbitalTable = true;
         } else if (a == "--slater-table") {
             DFT::DFTAtom::slaterTable = true;
+        } else if (a == "--form-factor-table") {
+            DFT::DFTAtom::formFactorTable = true;
+        } else if (a.rfind("--form-factor-table=", 0) == 0) {
+            double smax = 0;
+            int ns = 0;
+            char tail = 0;
+            if (std::sscanf(a.c_str() + 20, "%lf:%d%c", &smax, &ns, &tail) != 2 || !(smax >= 0 && smax <= 1e6) || ns < 1 || ns > 100000) {
+                std::cerr << "bad form-factor table " << a.substr(20) << " (smax:ns, smax in 1/Angstrom, ns points)" << std::endl;
+                return 2;
+            }
+            DFT::DFTAtom::formFactorTable = true;
+            DFT::DFTAtom::formFactorSmax = smax;
+            DFT::DFTAtom::formFactorPoints = ns;
         } else if (a == "--sweeps=tolerance" || a == "--sweeps=exact") {
             DFT::DFTAtom::sweepMode = a == "--sweeps=tolerance" ? DFTA_SWEEPS_TOLERANCE : DFTA_SWEEPS_EXACT;
         } else if (a == "--poisson=tolerance" || a == "--poisson=adaptive" || a == "--poisson=exact") {
@@ -146,6 +164,7 @@ int main(int argc, char** argv)
                   << "       --mixing=linear (default) | anderson: Anderson density mixing, fewer SCF steps\n"
                   << "       --orbital-table: after Finished!, one line per level with <r>, <r^2>, T and r_peak of its orbital\n"
                   << "       --slater-table: after Finished!, the Slater integrals F^k, G^k of the levels, then E_H and the exact-exchange energy\n"
+                  << "       --form-factor-table[=smax:ns]: after Finished!, the X-ray form factor f(q) at ns values of s = sin(theta)/lambda in 0 .. smax 1/Angstrom (default 2:41)\n"
                   << "       --charge=q: the cation (q > 0); --config: an electron configuration, fractional occupations allowed\n";
         return 2;
     }

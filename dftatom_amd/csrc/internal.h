@@ -199,6 +199,18 @@ struct dfta_slater_scratch {               // job table and results on the devic
     // uploads the table (host), launches, copies the njobs results to R (host) and synchronises
     int run(dfta_ctx* ctx, const dfta_grid* g, const double* dU, int njobs, const int* jobs, double* R);
 };
+// bessel.hip: Bessel transforms of radial arrays (device pointers; dRows: nrow device addresses of N doubles each; kind, l and q
+// validated by the caller -- bessel_plan.h: check_transform); dOut: nrow x nq; records the launch's time for dfta_ctx_last_kernel_ms
+int dfta_launch_bessel_transform(dfta_ctx* ctx, const dfta_grid* g, int kind, int nrow, const int* dL, const double* const* dRows, int nq,
+                                 const double* dQ, double* dOut);
+struct dfta_bessel_scratch {               // the tables of a transform and its results on the device: empty until the first run, grown as needed
+    int row_cap = 0, q_cap = 0;
+    DevBuf<int> d_l;
+    DevBuf<const double*> d_rows;
+    DevBuf<double> d_q, d_out;
+    // uploads l, the rows' device addresses and q (host arrays), launches, copies the nrow x nq results to out (host) and synchronises
+    int run(dfta_ctx* ctx, const dfta_grid* g, int kind, int nrow, const int* l, const double* const* rows, int nq, const double* q, double* out);
+};
 // scf.hip: the k_mix launch (DFTA_MIX_LINEAR), same arguments
 int dfta_launch_linear_mix(dfta_ctx* ctx, const dfta_grid* g, int lsda, int natoms, double alpha, double oneMinusAlpha, double* newDensity,
                            double* density, double* dA, double* dB, const int* fin);

@@ -1,5 +1,5 @@
 // scf_api.cpp -- the read-only C ABI of the SCF layer (include/dftatom_hip.h): the accessors of a batch's state (scf_state.h) and the
-// post-SCF analysis entries on its orbitals (orbitals.hip, slater.hip).  Host code only: what runs on the device is launched through the
+// post-SCF analysis entries on its orbitals and densities (orbitals.hip, slater.hip, bessel.hip).  Host code only: what runs on the device is launched through the
 // dfta_launch_* helpers (internal.h).  What an entry accepts and rejects is its own and stays in the entry.
 #include <hip/hip_runtime.h>
 
@@ -7,6 +7,7 @@
 #include <cmath>
 #include <vector>
 
+#include "bessel_plan.h"
 #include "scf_state.h"
 #include "slater_plan.h"
 #include "xc.h"             // dfta_poisson_group_state
@@ -267,6 +268,50 @@ int dfta_scf_coulomb_exchange(dfta_scf* s, int atom, double* EH, double* EXX)
     if (rc) return rc;
     dfta_slater::energy_sums(plan, s->solver.h_occ.data() + k0, s->lsda, R.data(), EH, EXX);
     return DFTA_OK;
+}
+
+// ---- Bessel transforms of the SCF's arrays (bessel.hip; densities and orbitals are read in place) -------------------------------------
+int dfta_scf_form_factors(dfta_scf* s, int nq, const double* q, double* out)
+{
+    if (!s) return DFTA_ERR_INVALID;
+    dfta_ctx* ctx = s->ctx;
+    DFTA_ENTER(ctx);
+    DFTA_REQUIRE(ctx, nq >= 0, "dfta_scf_form_factors: nq");
+    if (nq == 0) return DFTA_OK;
+    DFTA_REQUIRE(ctx, q && out, "dfta_scf_form_factors: q / out");
+    DFTA_REQUIRE(ctx, s->g->N >= 5, "form factors need a grid of 5 nodes");
+    const size_t N = s->g->N;
+    const int nchan = s->lsda ? 3 : 1, nrow = s->natoms * nchan;
+    std::vector<int> l(nrow, 0);
+    std::vector<const double*> rows(nrow);
+    for (int a = 0; a < s->natoms; ++a) {            // the arrays dfta_scf_get_array(.., 0 / 1 / 2) returns
+        rows[(size_t)a * nchan] = s->d_density + a * N;
+        if (s->lsda) { rows[(size_t)a * nchan + 1] = s->d_dA + a * N; rows[(size_t)a * nchan + 2] = s->d_dB + a * N; }
+    }
+    if (const char* msg = dfta_bessel::check_transform(DFTA_BT_DENSITY, nrow, l.data(), nq, q)) DFTA_REQUIRE(ctx, false, msg);
+    return s->bessel.run(ctx, s->g, DFTA_BT_DENSITY, nrow, l.data(), rows.data(), nq, q, out);
+}
+
+int dfta_scf_momentum_orbitals(dfta_scf* s, int nq, const double* q, double* out)
+{
+    if (!s) return DFTA_ERR_INVALID;
+    dfta_ctx* ctx = s->ctx;
+    DFTA_ENTER(ctx);
+    DFTA_REQUIRE(ctx, s->steps_done > 0, "no SCF step has run yet: there are no orbitals");
+    DFTA_REQUIRE(ctx, nq >= 0, "dfta_scf_momentum_orbitals: nq");
+    if (nq == 0) return DFTA_OK;
+    DFTA_REQUIRE(ctx, q && out, "dfta_scf_momentum_orbitals: q / out");
+    DFTA_REQUIRE(ctx, s->g->N >= 5, "momentum orbitals need a grid of 5 nodes");
+    const size_t N = s->g->N;
+    const int njobs = s->solver.njobs;
+    std::vector<int> l(njobs);
+    std::vector<const double*> rows(njobs);
+    for (int k = 0; k < njobs; ++k) {                // rows as dfta_scf_orbital_properties lists them
+        l[k] = s->h_jobs[k].l;
+        rows[k] = s->solver.d_Psi + k * N;
+    }
+    if (const char* msg = dfta_bessel::check_transform(DFTA_BT_ORBITAL, njobs, l.data(), nq, q)) DFTA_REQUIRE(ctx, false, msg);
+    return s->bessel.run(ctx, s->g, DFTA_BT_ORBITAL, njobs, l.data(), rows.data(), nq, q, out);
 }
 
 int dfta_scf_get_records_dev(dfta_scf* s, double* dRecords)

@@ -10,10 +10,12 @@ costs nothing more (dfta_scf_step).  The fixed-size result records are gathered 
     python examples/periodic_table.py --mixing anderson     # Anderson density mixing: about half the SCF steps
     python examples/periodic_table.py --charge 1            # the cations X+ (Z > charge)
     python examples/periodic_table.py --exx                 # E_H, the exact-exchange energy of the orbitals and the functional's E_xc per atom
+    python examples/periodic_table.py --form-factors        # X-ray form factors f(q) of every atom, one launch per shard
     python examples/periodic_table.py --ionization          # IE = E(X+) - E(X): neutral atom and cation of every Z in ONE batch per rank
 """
 import argparse
 import json
+import math
 import os
 import sys
 import time
@@ -51,6 +53,9 @@ def main():
     ap.add_argument("--exx", action="store_true",
                     help="add the Hartree energy E_H, the exact-exchange (Hartree-Fock) energy of the Kohn-Sham orbitals and the functional's "
                          "own exchange-correlation energy to every atom's row: Scf.coulomb_exchange()")
+    ap.add_argument("--form-factors", action="store_true",
+                    help="after the table, every atom's X-ray form factor f(q) at s = sin(theta)/lambda = 0 .. 2 1/Angstrom in 41 points "
+                         "(q = 4 pi s 0.529177210903 a.u.; LSDA adds f_a - f_b), one launch per shard: Scf.form_factors()")
     ap.add_argument("--lsda", action="store_true", help="spin-polarised (LSDA) instead of LDA")
     ap.add_argument("--ionization", action="store_true",
                     help="first ionization energies: the neutral atom and the +1 cation of every Z of a rank's shard advance in one batch; "
@@ -158,6 +163,16 @@ def main():
             parts = [None] * world
             dist.all_gather_object(parts, exx)
             exx = {z: v for p in parts for z, v in p.items()}
+    ff = {}
+    ff_s = [2.0 * k / 40 for k in range(41)]    # sin(theta) / lambda in 1 / Angstrom, as dftatom_cli --form-factor-table
+    if args.form_factors:                       # one launch for every density of this rank's batch
+        f = scf.form_factors([((4.0 * math.pi) * s) * 0.529177210903 for s in ff_s])
+        for a, z in enumerate(mine):
+            ff[int(z)] = {"f": f[a, 0].tolist(), **({"fa_minus_fb": (f[a, 1] - f[a, 2]).tolist()} if args.lsda else {})}
+        if world > 1:
+            parts = [None] * world
+            dist.all_gather_object(parts, ff)
+            ff = {z: v for p in parts for z, v in p.items()}
     block = torch.zeros((cap, D.RECORD_DOUBLES), dtype=torch.float64, device="cuda")
     scf.records_into(block.data_ptr())          # rows beyond len(mine) stay zero (Z = 0: no atom)
     ctx.synchronize()
@@ -173,6 +188,12 @@ def main():
                   "   %d%s <r> %.4f r_peak %.4f" % (o["n"], "spdf"[o["l"]], o["r_mean"], o["r_peak"]) if o else "",
                   "   E_H %.6f E_x(EXX) %.6f E_xc %.6f" % (x["E_H"], x["E_x_EXX"], x["E_xc"]) if x else "",
                   "   NIST LDA %.6f (diff %.1e)" % (ref, r["Etotal"] - ref) if ref else ""))
+        for r in rows:                          # the table of dftatom_cli --form-factor-table, per atom
+            t = ff.get(r["Z"])
+            if t:
+                for k, s in enumerate(ff_s):
+                    print("Z %3d  FormFactor s = %.6f q = %.6f f = %.6f%s" % (r["Z"], s, ((4.0 * math.pi) * s) * 0.529177210903, t["f"][k],
+                          " fa-fb = %.6f" % t["fa_minus_fb"][k] if "fa_minus_fb" in t else ""))
         print("%d atoms, %d GPU(s), %d SCF steps of the longest-running atom of rank 0, %d atom-steps in all, %d finished, %.1f s"
               % (len(rows), world, steps, sum(r["steps"] for r in rows), sum(r["finished"] for r in rows), elapsed))
         if args.out:
@@ -180,7 +201,8 @@ def main():
                 json.dump({"n_gpus": world, "levels": args.levels, "steps": steps, "seconds": elapsed,
                            "atoms": [dict({"Z": r["Z"], "Etotal": r["Etotal"], "steps": r["steps"], "finished": r["finished"]},
                                           **({"outermost": outer[r["Z"]]} if r["Z"] in outer else {}),
-                                          **({"exx": exx[r["Z"]]} if r["Z"] in exx else {})) for r in rows]},
+                                          **({"exx": exx[r["Z"]]} if r["Z"] in exx else {}),
+                                          **({"form_factor": ff[r["Z"]]} if r["Z"] in ff else {})) for r in rows]},
                           f, indent=1)
     scf.close()
     grid.close()

@@ -10,7 +10,8 @@
  * Conventions
  *   - plain C types only; every function returns an int status (DFTA_OK == 0) and never throws;
  *   - all floating point is IEEE fp64; kernels are built with -ffp-contract=off and use only + - * / sqrt on
- *     values, with exp() tables built on the host exactly as the reference evaluates them;
+ *     values, with exp() tables built on the host exactly as the reference evaluates them (the Bessel transforms, which the
+ *     reference does not have, also call the device's sin and cos);
  *   - `_dev` functions take DEVICE pointers and are asynchronous on the context's stream;
  *     functions without the suffix take HOST pointers, copy, run the same kernels and synchronise;
  *   - one in-flight call per context (the reference is single threaded: DFTAtomFrame.cpp:176-198);
@@ -493,6 +494,49 @@ int  dfta_scf_slater_rk(dfta_scf* s, int atom, int njobs, const int* jobs, doubl
 int  dfta_scf_slater_fg(dfta_scf* s, int atom, int spin, double* F, double* G);
 /* E_H and E_x of an atom from one launch: the F^0 of all its shell pairs, the G^k of each channel, then the host sums above */
 int  dfta_scf_coulomb_exchange(dfta_scf* s, int atom, double* EH, double* EXX);
+
+/* ---- Bessel transforms: X-ray form factors and momentum-space orbitals (beyond the reference) -------------------------------------------
+ * With Q[.], s_i = dr/di and the weights of the orbital block, a row f of N doubles, x_i = q r_i (one product, rounded once) and w_i the
+ * weight of node i WITHOUT the factor 3/8 (1 at the two end nodes, 2 where i % 3 == 0, 3 elsewhere):
+ *   DFTA_BT_DENSITY  out = 4 pi Q[f r^2 j_l(q r) s]:        g_i = w_i (((f_i r_i) r_i) s_i),   out = ((Sum_i g_i j_l(x_i)) (3/8)) K_D
+ *   DFTA_BT_ORBITAL  out = sqrt(2/pi) Q[f r j_l(q r) s]:    g_i = w_i ((f_i r_i) s_i),         out = ((Sum_i g_i j_l(x_i)) (3/8)) K_O
+ * K_D and K_O are the doubles nearest 4 pi and sqrt(2 / pi); both constant factors are applied once, to the finished sum.  A node whose
+ * g_i is zero adds nothing (its Bessel values are not formed): nodes beyond an orbital's cut-off index, an underflowed density tail.
+ * With f = rho and l = 0 the first is the X-ray form factor f(q) = 4 pi Int rho(r) j_0(q r) r^2 dr (f(0): the electron count; with a
+ * spin density the magnetic form factor), with f = u_nl = r R_nl and l the orbital's the second is the momentum-space radial function
+ * R~_nl(p) = sqrt(2/pi) Int R_nl(r) j_l(p r) r^2 dr (sign as u's, no factor (-i)^l).
+ *
+ * j_l(x), 0 <= l <= DFTA_BESSEL_LMAX, x >= 0, as the device evaluates it:
+ *   x == 0 (q = 0 or node 0; -0 too): exactly 1 for l = 0, exactly 0 for l >= 1;
+ *   l = 0: sin(x) / x;
+ *   l >= 1, x < 3: the ascending series x^l / (2l+1)!! Sum_k t_k, t_0 = 1, t_k = t_{k-1} (-x^2 / 2) / (k (2l + 2k + 1)), 14 terms
+ *       (k = 0 .. 13), nested: with y = (x x) (-1/2), c_k the double nearest 1 / (k (2l + 2k + 1)) and d_l the double nearest
+ *       1 / (2l+1)!!:  h = 1 + y c_13;  h = 1 + (y c_k) h for k = 12 .. 1;  p = x, then l - 1 times p = p x;  j_l = (p d_l) h;
+ *   l >= 1, x >= 3: one sincos, rx = 1 / x, j_0 = sin rx, j_1 = (j_0 - cos) rx, and upward j_{k+1} = ((2k+1) rx) j_k - j_{k-1}.
+ * (At x = 3 both branches are within a few 1e-16 of j_l; the recurrence alone is 3e-4 wrong at x = 0.1 for l = 4, the series alone
+ * loses three digits by x = 6: tests/test_bessel_ref.py measures both on a dense ladder.)
+ *
+ * Sums have a fixed shape that depends on N alone (no floating-point atomics): a (row, q) value depends on that row's
+ * N numbers, its l, the kind, q and the grid -- not on the other rows or q's of the call, their number or order, or the run.  A NaN
+ * inside a row makes that row's outputs NaN and no other's.  The grid samples f j_l: q (r_{i+1} - r_i) << 1 is needed where f lives
+ * (a diffuse orbital at large q aliases -- a property of the grid, not of the sum).
+ * DFTA_ERR_INVALID: a NULL pointer, kind outside {0, 1}, an l outside 0 .. 4, a q (or x) that is negative, NaN or infinite, N < 5.
+ * nq == 0 or nrow == 0: DFTA_OK, nothing is written.  All four entries record the launch's time for dfta_ctx_last_kernel_ms. */
+#define DFTA_BT_DENSITY 0
+#define DFTA_BT_ORBITAL 1
+#define DFTA_BESSEL_LMAX 4
+/* pointwise j_l(x) of n arguments (tests and tools); host pointers */
+int  dfta_sph_bessel(dfta_ctx* ctx, int l, size_t n, const double* x, double* out);
+/* every (row, q) in one launch, on caller-supplied rows; host pointers.  l: nrow; f: nrow x N; q: nq; out: nrow x nq */
+int  dfta_bessel_transform(dfta_ctx* ctx, const dfta_grid* g, int kind, int nrow, const int* l, const double* f, int nq, const double* q,
+                           double* out);
+/* form factors of the densities of every atom of the batch, read in place, one launch: out natoms x nchan x nq (host), nchan = 1 for
+ * LDA (rho), 3 for LSDA (rho, rho_a, rho_b) -- the arrays dfta_scf_get_array(.., 0 / 1 / 2) returns at the time of the call (after a
+ * step: the mixed density, the next step's input).  Valid from creation on: the start density has a form factor too. */
+int  dfta_scf_form_factors(dfta_scf* s, int nq, const double* q, double* out);
+/* R~_nl(q) of every orbital of the batch, read in place, one launch: out njobs x nq (host), rows as dfta_scf_orbital_properties lists
+ * them, each with its own l.  Before the first dfta_scf_step: DFTA_ERR_INVALID. */
+int  dfta_scf_momentum_orbitals(dfta_scf* s, int nq, const double* q, double* out);
 
 /* ---- Aufbau -------------------------------------------------------------------------------------------------
  * AufbauPrinciple::GetSubshells + sort (AufbauPrinciple.h:36-75, DFTAtom.cpp:367); integer-only host code. */
