@@ -35,7 +35,9 @@ ORB_PROPS = 8
 ORB_NORM, ORB_RM1, ORB_R1, ORB_R2, ORB_R4, ORB_T, ORB_RPEAK, ORB_RM3 = range(8)
 SLATER_KMAX = 8                        # DFTA_SLATER_KMAX: largest k of a Slater integral R^k
 SLATER_F, SLATER_G = 0, 1              # kinds of slater_fg_jobs
-BT_DENSITY, BT_ORBITAL = 0, 1          # DFTA_BT_*: kinds of bessel_transform
+XP_COLS = 4                            # DFTA_XP_*: columns of a vbar row of exchange_potentials
+XP_HF, XP_S, XP_C, XP_KLI = range(4)   # <a|v_x^HF,a|a>, <a|vS|a>, the KLI constant c_a, <a|vKLI|a>
+BT_DENSITY, BT_ORBITAL = 0, 1         # DFTA_BT_*: kinds of bessel_transform
 BESSEL_LMAX = 4                        # DFTA_BESSEL_LMAX: largest order of sph_bessel / bessel_transform
 
 c_dp = C.POINTER(C.c_double)
@@ -167,6 +169,11 @@ SIGNATURES = {
     "dfta_scf_slater_rk": (C.c_int, [vp, C.c_int, C.c_int, c_ip, c_dp]),
     "dfta_scf_slater_fg": (C.c_int, [vp, C.c_int, C.c_int, c_dp, c_dp]),
     "dfta_scf_coulomb_exchange": (C.c_int, [vp, C.c_int, c_dp, c_dp]),
+    "dfta_exchange_jobs": (C.c_int, [C.c_int, c_ip, c_ip]),
+    "dfta_screening_yk": (C.c_int, [vp, vp, C.c_int, c_dp, C.c_int, c_ip, c_dp]),
+    "dfta_scf_screening_yk": (C.c_int, [vp, C.c_int, C.c_int, c_ip, c_dp]),
+    "dfta_exchange_potentials": (C.c_int, [vp, vp, C.c_int, c_ip, c_dp, C.c_int, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp]),
+    "dfta_scf_exchange_potentials": (C.c_int, [vp, C.c_int, C.c_int, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp, c_ip]),
     "dfta_sph_bessel": (C.c_int, [vp, C.c_int, C.c_size_t, c_dp, c_dp]),
     "dfta_bessel_transform": (C.c_int, [vp, vp, C.c_int, C.c_int, c_ip, c_dp, C.c_int, c_dp, c_dp]),
     "dfta_scf_form_factors": (C.c_int, [vp, C.c_int, c_dp, c_dp]),
@@ -626,6 +633,49 @@ def slater_rk(ctx, grid, u, jobs):
     return R
 
 
+def exchange_jobs(l):
+    """dfta_exchange_jobs (host-only): the y jobs of a spin channel with angular momenta l, (njobs, 3) int32 rows x, y, k -- a, then
+    b >= a, then k of the exchange sum ascending"""
+    lib = load()
+    l = _i32(np.atleast_1d(l))
+    n = lib.dfta_exchange_jobs(len(l), _ip(l), None)
+    if n < 0:
+        raise DftaError("dfta_exchange_jobs: angular momenta must lie in 0 .. 4")
+    jobs = np.zeros((n, 3), np.int32)
+    lib.dfta_exchange_jobs(len(l), _ip(l), _ip(jobs))
+    return jobs
+
+
+def screening_yk(ctx, grid, u, jobs):
+    """dfta_screening_yk: the screening functions y^k_xy(r) = Y^k_xy(r) / r of the rows (x, y, k) of jobs over orbitals u = r R of shape
+    (norb, N), every job in one launch: (njobs, N).  y^0_aa is the Hartree potential of one electron in orbital a."""
+    u = _f64(u).reshape(-1, grid.N)
+    jobs = _i32(jobs).reshape(-1, 3)
+    y = np.zeros((len(jobs), grid.N))
+    ctx.check(ctx.lib.dfta_screening_yk(ctx.h, grid.h, u.shape[0], _dp(u), len(jobs), _ip(jobs), _dp(y)))
+    return y
+
+
+def _xp_outputs(norb, N):
+    return {"X": np.zeros((norb, N)), "D": np.zeros(N), "vS": np.zeros(N), "vKLI": np.zeros(N), "vbar": np.zeros((norb, XP_COLS)),
+            "M": np.zeros((norb, norb))}
+
+
+def exchange_potentials(ctx, grid, l, occ, homo, u):
+    """dfta_exchange_potentials for one spin channel: shells with angular momenta l, channel occupations occ, HOMO index homo and
+    orbitals u (norb, N).  A dict: X (norb, N) the exchange operator applied to each orbital, D = Sum n u^2, vS Slater's potential,
+    vKLI the KLI potential (N each), vbar (norb, XP_COLS) with columns XP_HF, XP_S, XP_C, XP_KLI, M (norb, norb), homo."""
+    u = _f64(u).reshape(-1, grid.N)
+    l, occ = _i32(np.atleast_1d(l)), _f64(np.atleast_1d(occ))
+    if len(l) != u.shape[0] or len(occ) != u.shape[0]:
+        raise ValueError("%d angular momenta and %d occupations for %d orbitals" % (len(l), len(occ), u.shape[0]))
+    out = _xp_outputs(u.shape[0], grid.N)
+    ctx.check(ctx.lib.dfta_exchange_potentials(ctx.h, grid.h, u.shape[0], _ip(l), _dp(occ), int(homo), _dp(u), _dp(out["X"]), _dp(out["D"]),
+                                               _dp(out["vS"]), _dp(out["vKLI"]), _dp(out["vbar"]), _dp(out["M"])))
+    out["homo"] = int(homo)
+    return out
+
+
 def sph_bessel(ctx, l, x):
     """dfta_sph_bessel: the device's spherical Bessel function j_l (0 <= l <= BESSEL_LMAX) at the arguments x >= 0, in x's shape"""
     x = _f64(x)
@@ -822,6 +872,30 @@ class Scf:
         eh, ex = C.c_double(), C.c_double()
         self.ctx.check(self.ctx.lib.dfta_scf_coulomb_exchange(self.h, int(atom), C.byref(eh), C.byref(ex)))
         return eh.value, ex.value
+
+    def screening_yk(self, atom, jobs):
+        """y^k_xy(r) of the rows (x, y, k) of jobs over the orbitals of `atom`, read in place: (njobs, N); indices count the atom's rows
+        of orbital_jobs(): alpha levels, then beta levels"""
+        jobs = _i32(jobs).reshape(-1, 3)
+        y = np.zeros((len(jobs), self.grid.N))
+        self.ctx.check(self.ctx.lib.dfta_scf_screening_yk(self.h, int(atom), len(jobs), _ip(jobs), _dp(y)))
+        return y
+
+    def exchange_potentials(self, atom=0, spin=0):
+        """exchange_potentials() of the levels of (atom, spin), read in place: channel occupations N (LSDA) or N / 2 (LDA), the HOMO the
+        occupied level of highest eigenvalue (the higher index on ties).  The dict also holds "occ", the channel occupations.
+        None for a channel without levels."""
+        cnt = max(self.ctx.lib.dfta_scf_num_levels(self.h, atom, spin), 0)
+        out = _xp_outputs(cnt, self.grid.N)
+        homo = C.c_int(-1)
+        self.ctx.check(self.ctx.lib.dfta_scf_exchange_potentials(self.h, int(atom), int(spin), _dp(out["X"]), _dp(out["D"]), _dp(out["vS"]),
+                                                                 _dp(out["vKLI"]), _dp(out["vbar"]), _dp(out["M"]), C.byref(homo)))
+        if cnt == 0:
+            return None
+        out["homo"] = homo.value
+        occ = self.levels(atom, spin)["occupation"]
+        out["occ"] = occ if self.lsda else 0.5 * occ
+        return out
 
     def form_factors(self, q):
         """(natoms, nchan, nq): f(q) = 4 pi Q[rho j_0(q r) r^2 dr/di] of every atom's densities as array(0 / 1 / 2) holds them now, read

@@ -22,6 +22,7 @@ int DFTAtom::mixing = DFTA_MIX_LINEAR;     // --mixing=anderson: Anderson densit
 std::ostream* DFTAtom::jsonOut = nullptr;
 bool DFTAtom::orbitalTable = false;        // --orbital-table
 bool DFTAtom::slaterTable = false;         // --slater-table
+bool DFTAtom::exchangeTable = false;       // --exchange-table
 bool DFTAtom::formFactorTable = false;     // --form-factor-table[=smax:ns]
 double DFTAtom::formFactorSmax = 2.0;
 int DFTAtom::formFactorPoints = 41;
@@ -135,6 +136,42 @@ void print_slater_table(dfta_scf* scf, bool lsda)
     std::cout << "EHartree = " << std::fixed << std::setprecision(6) << EH << " EXX = " << EXX << std::endl << std::endl;
 }
 
+// --exchange-table: per channel one line per shell with its eigenvalue, <a|v_x^HF,a|a>, <a|vS|a>, <a|vKLI|a> and the KLI constant c_a
+// (dfta_scf_exchange_potentials: one call per channel), then E_x = 1/2 Sum n vbarHF over the channels (LDA: twice the one channel's) and
+// r vKLI at the outermost node where the channel's density is positive
+void print_exchange_table(dfta_scf* scf, const dfta_grid* grid, bool lsda)
+{
+    const int N = dfta_grid_num_nodes(grid);
+    std::vector<double> r(N), D(N), vKLI(N);
+    if (dfta_grid_get_r(grid, r.data()) != DFTA_OK) throw std::runtime_error("dfta_grid_get_r");
+    double ex = 0;
+    std::vector<std::pair<int, double>> tails;      // per channel: spin, r vKLI
+    for (int spin = 0; spin < (lsda ? 2 : 1); ++spin) {
+        const std::vector<LevelLine> lv = fetch_levels(scf, spin);
+        const size_t n = lv.size();
+        if (n == 0) continue;
+        std::vector<double> vbar(DFTA_XP_COLS * n);
+        if (dfta_scf_exchange_potentials(scf, 0, spin, nullptr, D.data(), nullptr, vKLI.data(), vbar.data(), nullptr, nullptr) != DFTA_OK)
+            throw std::runtime_error("dfta_scf_exchange_potentials");
+        double sum = 0;
+        for (size_t a = 0; a < n; ++a) {
+            const double* v = vbar.data() + DFTA_XP_COLS * a;
+            sum += (lsda ? lv[a].occ : 0.5 * lv[a].occ) * v[DFTA_XP_HF];
+            std::cout << "Exchange " << (lsda ? (spin == 0 ? "alpha " : "beta ") : "") << lv[a].n + 1 << DFTAtom::orb[lv[a].l] << ": E = " << std::fixed
+                      << std::setprecision(6) << lv[a].E << " vbarHF = " << v[DFTA_XP_HF] << " vbarS = " << v[DFTA_XP_S] << " vbarKLI = " << v[DFTA_XP_KLI]
+                      << " c = " << v[DFTA_XP_C] << std::endl;
+        }
+        ex += lsda ? 0.5 * sum : sum;
+        int last = -1;
+        for (int i = 0; i < N; ++i)
+            if (D[i] > 0) last = i;
+        if (last >= 0) tails.push_back({spin, r[last] * vKLI[last]});
+    }
+    std::cout << "EXX = " << std::fixed << std::setprecision(6) << ex;
+    for (const auto& t : tails) std::cout << " r*vKLI" << (lsda ? (t.first == 0 ? "(alpha)" : "(beta)") : "") << " = " << t.second;
+    std::cout << std::endl << std::endl;
+}
+
 // --form-factor-table: f(q) of the converged density at s_k = smax k / (ns - 1), q = ((4 pi) s) 0.529177210903 (s in 1 / Angstrom, q in
 // atomic units), every q in one launch (dfta_scf_form_factors); LSDA: the magnetic form factor f_a - f_b beside it
 void print_form_factor_table(dfta_scf* scf, bool lsda)
@@ -213,6 +250,7 @@ void DFTAtom::Run(bool lsda, bool uniform, int Z, int MultigridLevels, double al
             std::cout << std::endl << "Finished!" << std::endl << std::endl;
             if (orbitalTable) print_orbital_table(scf, lsda);
             if (slaterTable) print_slater_table(scf, lsda);
+            if (exchangeTable) print_exchange_table(scf, grid, lsda);
             if (formFactorTable) print_form_factor_table(scf, lsda);
             break;
         }

@@ -48,6 +48,9 @@ public:
     // after "Finished!" (and the orbital table), one line per F^k / G^k of the levels' Slater integrals, then E_H and the exact-exchange
     // energy of the orbitals (dfta_scf_slater_fg, dfta_scf_coulomb_exchange)
     static bool slaterTable;
+    // after "Finished!" (and the Slater table), one line per shell and channel with its eigenvalue and the orbital averages of the Fock,
+    // Slater and KLI exchange potentials, then E_x and r vKLI at the outermost node of the density (dfta_scf_exchange_potentials)
+    static bool exchangeTable;
     // after "Finished!" (and the other tables), the X-ray form factor of the converged density on formFactorPoints values of
     // s = sin(theta) / lambda from 0 to formFactorSmax (1 / Angstrom), one line each; LSDA adds f_a - f_b (dfta_scf_form_factors)
     static bool formFactorTable;

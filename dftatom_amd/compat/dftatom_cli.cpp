@@ -17,6 +17,10 @@
 // --slater-table: after "Finished!" (and the orbital table), one line per Slater integral F^k(a,b), G^k(a,b) of the levels (per spin
 //                channel with LSDA), then one line with the Hartree energy and the exact-exchange energy of the orbitals (atomic units;
 //                include/dftatom_hip.h: dfta_scf_slater_fg, dfta_scf_coulomb_exchange).  Without it the output is unchanged.
+// --exchange-table: after "Finished!" (and the Slater table), one line per shell (per spin channel with LSDA) with its eigenvalue, the
+//                orbital averages vbarHF, vbarS, vbarKLI of the Fock, Slater and KLI exchange potentials and the KLI constant c, then one
+//                line with E_x = 1/2 Sum n vbarHF and r vKLI at the outermost node where the channel's density is positive (atomic
+//                units; include/dftatom_hip.h: dfta_scf_exchange_potentials).  Without it the output is unchanged.
 // --form-factor-table[=smax:ns]: after "Finished!" (and the other tables), one line per s = sin(theta) / lambda = smax k / (ns - 1), k = 0 ..
 //                ns - 1 (1 / Angstrom; default 0 .. 2 in 41 points): s, q = 4 pi s 0.529177210903 (atomic units) and the X-ray form factor
 //                f(q) of the converged density; LSDA adds the magnetic form factor f_a - f_b (include/dftatom_hip.h:
@@ -100,6 +104,8 @@ int main(int argc, char** argv)
             DFT::DFTAtom::orbitalTable = true;
         } else if (a == "--slater-table") {
             DFT::DFTAtom::slaterTable = true;
+        } else if (a == "--exchange-table") {
+            DFT::DFTAtom::exchangeTable = true;
         } else if (a == "--form-factor-table") {
             DFT::DFTAtom::formFactorTable = true;
         } else if (a.rfind("--form-factor-table=", 0) == 0) {
@@ -164,6 +170,7 @@ int main(int argc, char** argv)
                   << "       --mixing=linear (default) | anderson: Anderson density mixing, fewer SCF steps\n"
                   << "       --orbital-table: after Finished!, one line per level with <r>, <r^2>, T and r_peak of its orbital\n"
                   << "       --slater-table: after Finished!, the Slater integrals F^k, G^k of the levels, then E_H and the exact-exchange energy\n"
+                  << "       --exchange-table: after Finished!, per shell its eigenvalue, the orbital averages of the Fock, Slater and KLI exchange potentials and the KLI constant, then E_x and r vKLI at the density's outermost node\n"
                   << "       --form-factor-table[=smax:ns]: after Finished!, the X-ray form factor f(q) at ns values of s = sin(theta)/lambda in 0 .. smax 1/Angstrom (default 2:41)\n"
                   << "       --charge=q: the cation (q > 0); --config: an electron configuration, fractional occupations allowed\n";
         return 2;

@@ -199,6 +199,25 @@ struct dfta_slater_scratch {               // job table and results on the devic
     // uploads the table (host), launches, copies the njobs results to R (host) and synchronises
     int run(dfta_ctx* ctx, const dfta_grid* g, const double* dU, int njobs, const int* jobs, double* R);
 };
+// exchange.hip: screening functions y^k_xy and the exchange potentials of a spin channel (device pointers; jobs: rows x,y,k, validated
+// by the caller -- exchange_plan.h: check_jobs)
+namespace dfta_exchange { struct ChannelPlan; }
+int dfta_launch_screening_yk(dfta_ctx* ctx, const dfta_grid* g, const double* dU, int njobs, const int* dJobs, double* dY);
+struct dfta_exchange_scratch {             // tables, y rows and the channel's rows on the device: empty until the first run, grown as needed
+    int job_cap = 0, orb_cap = 0, tab_cap = 0;
+    size_t node_cap = 0, row_cap = 0;      // nodes the y rows / the channel's rows were made for
+    DevBuf<int> d_jobs, d_first, d_tab, d_red;
+    DevBuf<double> d_y;                    // njobs x N: 1 MB per job at 131 073 nodes
+    DevBuf<double> d_X, d_rows;            // norb x N; D, vS, vKLI
+    DevBuf<double> d_occ, d_coef, d_redout;
+    int upload_jobs(dfta_ctx* ctx, const dfta_grid* g, int njobs, const int* jobs);
+    // uploads the table (host), launches, copies the njobs x N rows to y (host) and synchronises; records the launch's time
+    int run_yk(dfta_ctx* ctx, const dfta_grid* g, const double* dU, int njobs, const int* jobs, double* y);
+    // the whole sequence of dfta_exchange_potentials for a planned channel (occ, outputs: host; any output may be null); the events of
+    // dfta_ctx_last_kernel_ms bracket it
+    int run_potentials(dfta_ctx* ctx, const dfta_grid* g, const double* dU, const dfta_exchange::ChannelPlan& plan, const double* occ, int homo,
+                       double* X, double* D, double* vS, double* vKLI, double* vbar, double* M);
+};
 // bessel.hip: Bessel transforms of radial arrays (device pointers; dRows: nrow device addresses of N doubles each; kind, l and q
 // validated by the caller -- bessel_plan.h: check_transform); dOut: nrow x nq; records the launch's time for dfta_ctx_last_kernel_ms
 int dfta_launch_bessel_transform(dfta_ctx* ctx, const dfta_grid* g, int kind, int nrow, const int* dL, const double* const* dRows, int nq,

@@ -1,5 +1,5 @@
 // scf_api.cpp -- the read-only C ABI of the SCF layer (include/dftatom_hip.h): the accessors of a batch's state (scf_state.h) and the
-// post-SCF analysis entries on its orbitals and densities (orbitals.hip, slater.hip, bessel.hip).  Host code only: what runs on the device is launched through the
+// post-SCF analysis entries on its orbitals and densities (orbitals.hip, slater.hip, exchange.hip, bessel.hip).  Host code only: what runs on the device is launched through the
 // dfta_launch_* helpers (internal.h).  What an entry accepts and rejects is its own and stays in the entry.
 #include <hip/hip_runtime.h>
 
@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "bessel_plan.h"
+#include "exchange_plan.h"
 #include "scf_state.h"
 #include "slater_plan.h"
 #include "xc.h"             // dfta_poisson_group_state
@@ -270,7 +271,55 @@ int dfta_scf_coulomb_exchange(dfta_scf* s, int atom, double* EH, double* EXX)
     return DFTA_OK;
 }
 
-// ---- Bessel transforms of the SCF's arrays (bessel.hip; densities and orbitals are read in place) -------------------------------------
+// ---- screening functions and exchange potentials of the SCF's orbitals (exchange.hip; the orbitals are read in place) -----------------
+int dfta_scf_screening_yk(dfta_scf* s, int atom, int njobs, const int* jobs, double* y)
+{
+    if (!s) return DFTA_ERR_INVALID;
+    dfta_ctx* ctx = s->ctx;
+    DFTA_ENTER(ctx);
+    DFTA_REQUIRE(ctx, s->steps_done > 0, "no SCF step has run yet: there are no orbitals");
+    DFTA_REQUIRE(ctx, atom >= 0 && atom < s->natoms, "atom");
+    DFTA_REQUIRE(ctx, s->g->N >= 5, "screening functions need a grid of 5 nodes");
+    const auto [k0, norb] = s->atom_jobs(atom);
+    DFTA_REQUIRE(ctx, njobs >= 0, "njobs");
+    if (njobs == 0) return DFTA_OK;
+    DFTA_REQUIRE(ctx, jobs && y, "jobs / y");
+    if (const char* msg = dfta_exchange::check_jobs(norb, njobs, jobs)) DFTA_REQUIRE(ctx, false, msg);
+    return s->exchange.run_yk(ctx, s->g, s->solver.d_Psi + (size_t)k0 * s->g->N, njobs, jobs, y);
+}
+
+int dfta_scf_exchange_potentials(dfta_scf* s, int atom, int spin, double* X, double* D, double* vS, double* vKLI, double* vbar, double* M,
+                                 int* homo)
+{
+    if (!s) return DFTA_ERR_INVALID;
+    dfta_ctx* ctx = s->ctx;
+    DFTA_ENTER(ctx);
+    DFTA_REQUIRE(ctx, s->steps_done > 0, "no SCF step has run yet: there are no orbitals");
+    DFTA_REQUIRE(ctx, atom >= 0 && atom < s->natoms && spin >= 0 && spin < s->nspin, "atom/spin");
+    DFTA_REQUIRE(ctx, s->g->N >= 5, "exchange potentials need a grid of 5 nodes");
+    const auto [c0, cnt] = s->channel(atom, spin);
+    if (cnt == 0) {
+        if (homo) *homo = -1;
+        return DFTA_OK;
+    }
+    std::vector<int> l(cnt);
+    std::vector<double> occ(cnt), E(cnt);
+    for (int a = 0; a < cnt; ++a) {
+        l[a] = s->h_jobs[c0 + a].l;
+        E[a] = s->h_jobs[c0 + a].E;
+        occ[a] = s->lsda ? s->solver.h_occ[c0 + a] : 0.5 * s->solver.h_occ[c0 + a];
+    }
+    const int h = dfta_exchange::pick_homo(cnt, E.data(), occ.data());
+    if (const char* msg = dfta_exchange::check_channel(cnt, l.data(), occ.data(), h)) DFTA_REQUIRE(ctx, false, msg);
+    dfta_exchange::ChannelPlan plan;
+    DFTA_REQUIRE(ctx, dfta_exchange::plan_channel(cnt, l.data(), occ.data(), &plan) == 0, "exchange potentials: the channel");
+    const int rc = s->exchange.run_potentials(ctx, s->g, s->solver.d_Psi + (size_t)c0 * s->g->N, plan, occ.data(), h, X, D, vS, vKLI, vbar, M);
+    if (rc) return rc;
+    if (homo) *homo = h;
+    return DFTA_OK;
+}
+
+// ---- Bessel transforms of the SCF's arrays(bessel.hip; densities and orbitals are read in place) -------------------------------------
 int dfta_scf_form_factors(dfta_scf* s, int nq, const double* q, double* out)
 {
     if (!s) return DFTA_ERR_INVALID;

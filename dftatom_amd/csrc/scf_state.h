@@ -59,7 +59,8 @@ struct dfta_scf {
     DevBuf<double> d_orb_props;           // njobs x DFTA_ORB_PROPS
     dfta_orbital_scratch orb_scratch;     // of dfta_scf_orbital_matrix, sized for the longest channel of the batch
     dfta_slater_scratch slater;           // of the Slater-integral calls (slater.hip): job table and results, made by the first such call
-    dfta_bessel_scratch bessel;           // of the form-factor and momentum-orbital calls (bessel.hip), made by the first such call
+    dfta_exchange_scratch exchange;       // of the screening-function and exchange-potential calls (exchange.hip), made by the first such call
+    dfta_bessel_scratch bessel;          // of the form-factor and momentum-orbital calls (bessel.hip), made by the first such call
 
     // first job and number of levels of (atom, spin), and of the atom (alpha levels, then beta levels)
     struct Jobs { int k0, cnt; };

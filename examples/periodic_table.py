@@ -10,6 +10,7 @@ costs nothing more (dfta_scf_step).  The fixed-size result records are gathered 
     python examples/periodic_table.py --mixing anderson     # Anderson density mixing: about half the SCF steps
     python examples/periodic_table.py --charge 1            # the cations X+ (Z > charge)
     python examples/periodic_table.py --exx                 # E_H, the exact-exchange energy of the orbitals and the functional's E_xc per atom
+    python examples/periodic_table.py --kli                 # E_x from the Fock averages and the tail r vKLI of the KLI exchange potential per atom
     python examples/periodic_table.py --form-factors        # X-ray form factors f(q) of every atom, one launch per shard
     python examples/periodic_table.py --ionization          # IE = E(X+) - E(X): neutral atom and cation of every Z in ONE batch per rank
 """
@@ -53,6 +54,9 @@ def main():
     ap.add_argument("--exx", action="store_true",
                     help="add the Hartree energy E_H, the exact-exchange (Hartree-Fock) energy of the Kohn-Sham orbitals and the functional's "
                          "own exchange-correlation energy to every atom's row: Scf.coulomb_exchange()")
+    ap.add_argument("--kli", action="store_true",
+                    help="add E_x = 1/2 Sum n <a|v_x^HF|a> and r vKLI at the outermost node of the density (alpha channel) to every atom's row: "
+                         "Scf.exchange_potentials()")
     ap.add_argument("--form-factors", action="store_true",
                     help="after the table, every atom's X-ray form factor f(q) at s = sin(theta)/lambda = 0 .. 2 1/Angstrom in 41 points "
                          "(q = 4 pi s 0.529177210903 a.u.; LSDA adds f_a - f_b), one launch per shard: Scf.form_factors()")
@@ -62,6 +66,7 @@ def main():
                          "IE = E(+1) - E(0) per Z (H+ has no electron: E = 0)")
     args = ap.parse_args()
 
+    import numpy as np
     import torch
     import torch.distributed as dist
     import dftatom_amd as D
@@ -163,6 +168,25 @@ def main():
             parts = [None] * world
             dist.all_gather_object(parts, exx)
             exx = {z: v for p in parts for z, v in p.items()}
+    kli = {}
+    if args.kli:                                # per channel the y rows, the pointwise pass and the reductions; r of the grid for the tail
+        r = grid.r()
+        for a, z in enumerate(mine):
+            ex, tail = 0.0, None
+            for spin in ((0, 1) if args.lsda else (0,)):
+                p = scf.exchange_potentials(a, spin)
+                if p is None:
+                    continue
+                half = float(np.sum(p["occ"] * p["vbar"][:, D.XP_HF]))
+                ex += 0.5 * half if args.lsda else half
+                if spin == 0:
+                    i = int(np.nonzero(p["D"] > 0)[0][-1])
+                    tail = float(r[i] * p["vKLI"][i])
+            kli[int(z)] = {"E_x_from_vbarHF": ex, "r_vKLI_tail": tail}
+        if world > 1:
+            parts = [None] * world
+            dist.all_gather_object(parts, kli)
+            kli = {z: v for p in parts for z, v in p.items()}
     ff = {}
     ff_s = [2.0 * k / 40 for k in range(41)]    # sin(theta) / lambda in 1 / Angstrom, as dftatom_cli --form-factor-table
     if args.form_factors:                       # one launch for every density of this rank's batch
@@ -184,9 +208,11 @@ def main():
             ref = NIST_LDA.get(r["Z"])
             o = outer.get(r["Z"])
             x = exx.get(r["Z"])
-            print("Z %3d  Etotal %16.6f  steps %3d  finished %d%s%s%s" % (r["Z"], r["Etotal"], r["steps"], r["finished"],
+            kl = kli.get(r["Z"])
+            print("Z %3d  Etotal %16.6f  steps %3d  finished %d%s%s%s%s" % (r["Z"], r["Etotal"], r["steps"], r["finished"],
                   "   %d%s <r> %.4f r_peak %.4f" % (o["n"], "spdf"[o["l"]], o["r_mean"], o["r_peak"]) if o else "",
                   "   E_H %.6f E_x(EXX) %.6f E_xc %.6f" % (x["E_H"], x["E_x_EXX"], x["E_xc"]) if x else "",
+                  "   E_x(vbarHF) %.6f r*vKLI %.6f" % (kl["E_x_from_vbarHF"], kl["r_vKLI_tail"]) if kl else "",
                   "   NIST LDA %.6f (diff %.1e)" % (ref, r["Etotal"] - ref) if ref else ""))
         for r in rows:                          # the table of dftatom_cli --form-factor-table, per atom
             t = ff.get(r["Z"])
@@ -202,6 +228,7 @@ def main():
                            "atoms": [dict({"Z": r["Z"], "Etotal": r["Etotal"], "steps": r["steps"], "finished": r["finished"]},
                                           **({"outermost": outer[r["Z"]]} if r["Z"] in outer else {}),
                                           **({"exx": exx[r["Z"]]} if r["Z"] in exx else {}),
+                                          **({"kli": kli[r["Z"]]} if r["Z"] in kli else {}),
                                           **({"form_factor": ff[r["Z"]]} if r["Z"] in ff else {})) for r in rows]},
                           f, indent=1)
     scf.close()

@@ -495,6 +495,79 @@ int  dfta_scf_slater_fg(dfta_scf* s, int atom, int spin, double* F, double* G);
 /* E_H and E_x of an atom from one launch: the F^0 of all its shell pairs, the G^k of each channel, then the host sums above */
 int  dfta_scf_coulomb_exchange(dfta_scf* s, int atom, double* EH, double* EXX);
 
+/* ---- exchange potentials from orbitals: screening functions y^k, the Fock operator, Slater's and the KLI potential (beyond the reference)
+ * In the notation of the Slater block (s_i = dr/di, P_xy,i = u_x,i u_y,i with the lower-indexed orbital first, p_i = r_i^k formed as
+ * p = 1, then k times p = p * r_i, the increments d_i(g) of the three stencils there, Q[.] with the Simpson 3/8 weights), and with
+ * inv_i = 1 / (p_i r_i) for i >= 1, inv_0 = 0:
+ *
+ * Screening function of a pair x <= y, 0 <= k <= DFTA_SLATER_KMAX:
+ *   y^k_xy(r) = Y^k_xy(r) / r = r^(-k-1) Z^k_xy(r) + r^k W^k_xy(r),  Z(r) = Int_0^r t^k P(t) dt,  W(r) = Int_r^inf t^(-k-1) P(t) dt
+ *   Z_i exactly as in the Slater block: g_i = (p_i P_i) s_i, Z_0 = 0, Z_i = Sum_{j <= i} d_j(g);
+ *   h_i = (P_i inv_i) s_i (so h_0 = 0), e_j = d_j(h) with the same three stencils, W_{N-1} = 0, W_i = Sum_{j > i} e_j: a REVERSE
+ *   cumulative sum taken from the outside in, never "total minus prefix";
+ *   y_i = Z_i inv_i + p_i W_i for i >= 1 (two products, one sum);  y_0 = W_0 for k = 0 and 0 for k > 0.
+ * Y^0_aa / r is the Hartree potential of the density of one electron in orbital a.  Both scans have a fixed shape that depends on N alone
+ * (no atomics): a row's bits depend on its two orbitals, k and N -- not on the other jobs of the call, its position
+ * among them, or the run; a job (x, y, k) is computed under x <= y, so (y, x, k) returns the same bits.  Nodes beyond an orbital's
+ * cut-off are zeros like any others; an all-zero pair gives exactly 0 everywhere.  Any k in 0 .. 8 is accepted; for k > l_x + l_y the
+ * integrand of W is singular at the origin (P ~ r^(l_x + l_y + 2)) and the values near the origin are only as good as the grid.  N >= 5.
+ *
+ * Exchange operator of ONE spin channel with shells a = 0 .. n-1 (n <= 32), angular momenta l_a (0 .. 4), channel occupations n_a >= 0
+ * (LSDA: N_a; LDA: N_a / 2) and c_abk = (l_a k l_b; 0 0 0)^2 = dfta_gaunt_3j2, k over the exchange sum of the Slater block:
+ *   X_a,i = Sum_b Sum_k (n_b c_abk) (y^k_ab,i u_b,i)     one accumulator from 0.0, b ascending (every b of the channel), then k ascending
+ *   D_i   = Sum_a n_a (u_a,i u_a,i)                      one accumulator from 0.0, a ascending       (= 4 pi r^2 rho_sigma)
+ *   num_i = Sum_a n_a (u_a,i X_a,i)                      the same
+ *   vS_i  = -(num_i / D_i) where D_i > 0, else 0.0       Slater's averaged exchange potential
+ *   vbarHF_a = -Q[(u_a X_a) s]                           <a| v_x^HF,a |a>
+ *   vbarS_a  = Q[((u_a u_a) vS) s]
+ *   S_ab     = Q[(((u_a u_a) (u_b u_b)) / D) s]          the term is 0 where D_i = 0; computed once per a <= b and mirrored
+ *   M_ab     = S_ab n_b
+ * (u_a X_a is the radial part of u_a times the Fock exchange operator applied to orbital a, sign included in vbarHF.)
+ * KLI (Krieger, Li, Iafrate): with h the HOMO of the channel, c_h = 0 and the other c solve (I - M)_red c = (vbarS - vbarHF)_red, rows and
+ * columns h removed: host arithmetic in double, Gaussian elimination with partial pivoting -- for every column j ascending the pivot is
+ * the row p >= j of largest |A_pj| (the lowest on ties), rows j and p are exchanged; for every row i > j ascending f = A_ij / A_jj, for
+ * m > j ascending A_im = A_im - f A_jm, then b_i = b_i - f b_j; back substitution for i descending: t = b_i, for m > i ascending
+ * t = t - A_im x_m, x_i = t / A_ii.  Then
+ *   vKLI_i = vS_i + (Sum_{a != h} (n_a (u_a,i u_a,i)) c_a) / D_i     one accumulator from 0.0, a ascending; 0.0 where D_i is not > 0
+ *   vbarKLI_a = Q[((u_a u_a) vKLI) s]
+ * A channel of one shell has an empty system: vKLI = vS bit for bit.  The spherical average treats a shell as a unit (one orbital per
+ * shell, occupation n_a), the convention of E_x above.  Up to rounding: Sum_a n_a vbarS_a = Sum_a n_a vbarHF_a; Sum_b M_ab = NORM_a;
+ * n_h (vbarKLI_h - vbarHF_h) = Sum_{b != h} n_b c_b (NORM_b - 1), the row that was dropped: vbarKLI_h = vbarHF_h for orbitals normalised
+ * under Q.  Sum_a n_a vbarHF_a = 2 E_x of the channel up to the grid's order: Q[P p W s] here and Q[P Z inv s] of the Slater block are two
+ * discretisations of one integral (4.5e-15 apart, relative, for a neon-like channel at 4097 logarithmic nodes).  The HOMO of an SCF
+ * channel is the shell of highest eigenvalue among those with n_a > 0, the higher index on ties.
+ * Q's sums have the fixed shape of the orbital block: lane t of 256 adds the terms of the nodes t, t + 256, ..., then the tree. */
+#define DFTA_XP_COLS 4
+#define DFTA_XP_HF   0   /* columns of a vbar row: vbarHF_a */
+#define DFTA_XP_S    1   /* vbarS_a  */
+#define DFTA_XP_C    2   /* the KLI constant c_a (0 for the HOMO) */
+#define DFTA_XP_KLI  3   /* vbarKLI_a */
+/* host-only: the y jobs of a channel with angular momenta l (0 .. 4), rows x, y, k of three ints: a, then b >= a, then k = |l_a - l_b|,
+ * |l_a - l_b| + 2 .. l_a + l_b ascending (b == a: k = 0, 2 .. 2 l_a).  Returns the number of jobs (jobs may be NULL: count only), or -1
+ * for norb < 0, l NULL or an l outside 0 .. 4. */
+int  dfta_exchange_jobs(int norb, const int* l, int* jobs);
+/* every job (x, y, k) of the table in one launch, on caller-supplied orbitals; host pointers.  u: norb x N; y: njobs x N.  njobs == 0:
+ * DFTA_OK, nothing is written.  Records the launch's time for dfta_ctx_last_kernel_ms. */
+int  dfta_screening_yk(dfta_ctx* ctx, const dfta_grid* g, int norb, const double* u, int njobs, const int* jobs, double* y);
+/* ... on the orbitals of an atom of the SCF, read in place; indices count the atom's orbitals, alpha levels then beta levels, as in
+ * dfta_scf_slater_rk.  Before the first dfta_scf_step: DFTA_ERR_INVALID.  The job table and the y rows are kept on the device from the
+ * first such call on, grown when a longer table comes: njobs x N doubles (at 131 073 nodes 1 MB per job). */
+int  dfta_scf_screening_yk(dfta_scf* s, int atom, int njobs, const int* jobs, double* y);
+/* the potentials of one channel on caller-supplied orbitals; host pointers.  l, occ: norb; homo: 0 .. norb-1; u: norb x N.  Outputs, any
+ * of which may be NULL: X norb x N; D, vS, vKLI N each; vbar norb x DFTA_XP_COLS; M norb x norb, row-major.  Launches: the y jobs of
+ * dfta_exchange_jobs, the pointwise pass, the reductions; after the host solve the KLI pass and its reductions.  The events of
+ * dfta_ctx_last_kernel_ms bracket the whole sequence.  DFTA_ERR_INVALID: a NULL input, norb outside 1 .. 32, an l outside 0 .. 4, a
+ * negative occupation, homo out of range, N < 5, a singular system. */
+int  dfta_exchange_potentials(dfta_ctx* ctx, const dfta_grid* g, int norb, const int* l, const double* occ, int homo, const double* u,
+                              double* X, double* D, double* vS, double* vKLI, double* vbar, double* M);
+/* ... of channel (atom, spin) of the SCF, orbitals read in place, n_a = N_a (LSDA) or N_a / 2 (LDA: spin 0 only), the HOMO by the rule
+ * above from the level's eigenvalues (homo, may be NULL: its index).  A channel without levels: DFTA_OK, nothing is written (homo: -1).
+ * Before the first dfta_scf_step: DFTA_ERR_INVALID.  A frozen atom keeps its orbitals, hence its potentials.  Device scratch from the
+ * first such call on, grown as needed: the y rows of the channel (Rn LDA: 176 jobs, 1 MB each at 131 073 nodes), X (norb x N) and five
+ * rows of N. */
+int  dfta_scf_exchange_potentials(dfta_scf* s, int atom, int spin, double* X, double* D, double* vS, double* vKLI, double* vbar,
+                                  double* M, int* homo);
+
 /* ---- Bessel transforms: X-ray form factors and momentum-space orbitals (beyond the reference) -------------------------------------------
  * With Q[.], s_i = dr/di and the weights of the orbital block, a row f of N doubles, x_i = q r_i (one product, rounded once) and w_i the
  * weight of node i WITHOUT the factor 3/8 (1 at the two end nodes, 2 where i % 3 == 0, 3 elsewhere):
