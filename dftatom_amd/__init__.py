@@ -37,6 +37,7 @@ SLATER_KMAX = 8                        # DFTA_SLATER_KMAX: largest k of a Slater
 SLATER_F, SLATER_G = 0, 1              # kinds of slater_fg_jobs
 XP_COLS = 4                            # DFTA_XP_*: columns of a vbar row of exchange_potentials
 XP_HF, XP_S, XP_C, XP_KLI = range(4)   # <a|v_x^HF,a|a>, <a|vS|a>, the KLI constant c_a, <a|vKLI|a>
+EXCHANGE_FUNCTIONAL, EXCHANGE_KLI = 0, 1   # dfta_scf_set_exchange: v_xc of the functional / exchange-only KLI from the step's orbitals
 BT_DENSITY, BT_ORBITAL = 0, 1         # DFTA_BT_*: kinds of bessel_transform
 BESSEL_LMAX = 4                        # DFTA_BESSEL_LMAX: largest order of sph_bessel / bessel_transform
 
@@ -174,6 +175,10 @@ SIGNATURES = {
     "dfta_scf_screening_yk": (C.c_int, [vp, C.c_int, C.c_int, c_ip, c_dp]),
     "dfta_exchange_potentials": (C.c_int, [vp, vp, C.c_int, c_ip, c_dp, C.c_int, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp]),
     "dfta_scf_exchange_potentials": (C.c_int, [vp, C.c_int, C.c_int, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp, c_ip]),
+    "dfta_scf_set_exchange": (C.c_int, [vp, C.c_int]),
+    "dfta_scf_get_exchange": (C.c_int, [vp, C.c_int, C.c_int, c_dp, c_dp, c_dp]),
+    "dfta_scf_exchange_ms": (C.c_int, [vp, C.POINTER(C.c_float)]),
+    "dfta_kli_channels": (C.c_int, [vp, vp, C.c_int, c_ip, c_ip, c_dp, c_dp, c_dp, C.c_int, C.c_double, c_dp, c_dp, c_dp, c_dp, c_ip, c_dp]),
     "dfta_sph_bessel": (C.c_int, [vp, C.c_int, C.c_size_t, c_dp, c_dp]),
     "dfta_bessel_transform": (C.c_int, [vp, vp, C.c_int, C.c_int, c_ip, c_dp, C.c_int, c_dp, c_dp]),
     "dfta_scf_form_factors": (C.c_int, [vp, C.c_int, c_dp, c_dp]),
@@ -676,6 +681,29 @@ def exchange_potentials(ctx, grid, l, occ, homo, u):
     return out
 
 
+def kli_channels(ctx, grid, norb, l, occ, E, u, first_step=True, alpha=0.5, vx=None):
+    """dfta_kli_channels: the batched exchange stage of a KLI step on caller-supplied spin channels.  norb: shells per channel; l, occ
+    (channel occupations), E (eigenvalues, for the HOMO rule): the channels' shells end to end; u (sum norb, N) their orbitals.
+    first_step: vx = v_raw; otherwise vx (nch, N) is mixed as alpha vx + (1 - alpha) v_raw.  A dict: vx, v_raw (nch, N), vbarHF, c (per
+    shell), homo, Ex (per channel: 0.5 Sum n vbarHF)."""
+    norb = _i32(np.atleast_1d(norb))
+    nch, tot = len(norb), int(np.sum(norb))
+    l, occ, E = _i32(np.atleast_1d(l)), _f64(np.atleast_1d(occ)), _f64(np.atleast_1d(E))
+    u = _f64(u).reshape(-1, grid.N)
+    if not (len(l) == len(occ) == len(E) == u.shape[0] == tot):
+        raise ValueError("%d shells: %d l, %d occ, %d E, %d orbitals" % (tot, len(l), len(occ), len(E), u.shape[0]))
+    if first_step:
+        vx = np.zeros((nch, grid.N))
+    else:
+        vx = _f64(vx).reshape(nch, grid.N).copy()
+    out = {"vx": vx, "v_raw": np.zeros((nch, grid.N)), "vbarHF": np.zeros(max(tot, 1)), "c": np.zeros(max(tot, 1)),
+           "homo": np.zeros(nch, np.int32), "Ex": np.zeros(nch)}
+    ctx.check(ctx.lib.dfta_kli_channels(ctx.h, grid.h, nch, _ip(norb), _ip(l), _dp(occ), _dp(E), _dp(u), int(bool(first_step)), float(alpha),
+                                        _dp(out["vx"]), _dp(out["v_raw"]), _dp(out["vbarHF"]), _dp(out["c"]), _ip(out["homo"]), _dp(out["Ex"])))
+    out["vbarHF"], out["c"] = out["vbarHF"][:tot], out["c"][:tot]
+    return out
+
+
 def sph_bessel(ctx, l, x):
     """dfta_sph_bessel: the device's spherical Bessel function j_l (0 <= l <= BESSEL_LMAX) at the arguments x >= 0, in x's shape"""
     x = _f64(x)
@@ -740,12 +768,14 @@ class Scf:
 
     def __init__(self, ctx, grid, Z, lsda=False, alpha=0.5, levels_mode=LEVELS_BATCHED, tree_depth=0, integrator=INT_SIMPSON38,
                  functional=XC_VWN, aufbau=AUFBAU_REFERENCE, poisson_mode=POISSON_DEFAULT, sweep_mode=SWEEPS_EXACT, config=None,
-                 charge=None, mixing=MIX_LINEAR, mix_history=0, mix_warmup=0):
+                 charge=None, exchange=EXCHANGE_FUNCTIONAL, mixing=MIX_LINEAR, mix_history=0, mix_warmup=0):
         """mixing: MIX_LINEAR (the reference's) or MIX_ANDERSON (include/dftatom_hip.h: about half the steps); mix_history: pairs kept per
         atom (1 .. 8, 0: 4); mix_warmup: linear steps before the first accelerated one (0: 3).
         config: an electron configuration (parse_config's text, or its result) for every atom, or a list of them, one per atom;
         charge: an int for every atom, or a list of ints (ion_config: cations).  Neither: the Aufbau configuration of each Z.
-        The nuclear charge stays Z; the electron count sets the start density and the Poisson boundary U(Rmax)."""
+        The nuclear charge stays Z; the electron count sets the start density and the Poisson boundary U(Rmax).
+        exchange: EXCHANGE_KLI makes every step take its exchange potential from its own orbitals (exchange-only KLI, no correlation;
+        functional XC_VWN and MIX_LINEAR only): set_exchange() right after creation."""
         self.ctx, self.grid = ctx, grid
         self.Z = _i32(np.atleast_1d(Z))
         self.natoms = len(self.Z)
@@ -785,6 +815,12 @@ class Scf:
         d, nj, tr = C.c_int(), C.c_int(), C.c_long()
         ctx.check(ctx.lib.dfta_scf_info(h, C.byref(d), C.byref(nj), C.byref(tr)))
         self.tree_depth, self.njobs, self.trials_per_round = d.value, nj.value, tr.value
+        if exchange != EXCHANGE_FUNCTIONAL:
+            try:
+                self.set_exchange(exchange)
+            except Exception:
+                self.close()
+                raise
 
     def step(self, want_stats=True):
         st = StepStats()
@@ -916,6 +952,22 @@ class Scf:
     def set_integrator(self, rule):
         """INT_TRAPEZOID .. INT_ROMBERG: quadrature of the energy integrals and of the orbitals' normalisation."""
         self.ctx.check(self.ctx.lib.dfta_scf_set_integrator(self.h, int(rule)))
+
+    def set_exchange(self, exchange):
+        """EXCHANGE_FUNCTIONAL or EXCHANGE_KLI, before the first step (dfta_scf_set_exchange)."""
+        self.ctx.check(self.ctx.lib.dfta_scf_set_exchange(self.h, int(exchange)))
+
+    def exchange(self, atom=0, spin=0):
+        """under EXCHANGE_KLI, after a step: {"vx", "v_raw"} (N each) of channel (atom, spin) and "Ex", the atom's exchange energy"""
+        vx, vr, ex = np.zeros(self.grid.N), np.zeros(self.grid.N), C.c_double()
+        self.ctx.check(self.ctx.lib.dfta_scf_get_exchange(self.h, int(atom), int(spin), _dp(vx), _dp(vr), C.byref(ex)))
+        return {"vx": vx, "v_raw": vr, "Ex": ex.value}
+
+    def exchange_ms(self):
+        """HIP-event time of the last step's exchange stage, ms"""
+        ms = C.c_float()
+        self.ctx.check(self.ctx.lib.dfta_scf_exchange_ms(self.h, C.byref(ms)))
+        return ms.value
 
     def poisson_info(self):
         g, d, a = C.c_int(), C.c_int(), C.c_int()

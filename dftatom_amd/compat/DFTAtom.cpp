@@ -19,6 +19,7 @@ int DFTAtom::charge = 0;
 std::string DFTAtom::config;
 int DFTAtom::poissonMode = -1;      // as dfta_poisson_create: exact unless $DFTA_DEBUG POISSON_MODE (--poisson= overrides)
 int DFTAtom::mixing = DFTA_MIX_LINEAR;     // --mixing=anderson: Anderson density mixing, default history and warm-up
+int DFTAtom::exchange = DFTA_EXCHANGE_FUNCTIONAL;   // --exchange=kli: dfta_scf_set_exchange right after creation
 std::ostream* DFTAtom::jsonOut = nullptr;
 bool DFTAtom::orbitalTable = false;        // --orbital-table
 bool DFTAtom::slaterTable = false;         // --slater-table
@@ -227,6 +228,7 @@ void DFTAtom::Run(bool lsda, bool uniform, int Z, int MultigridLevels, double al
         dfta_compat::check(dfta_scf_create_config(rt.ctx(), grid, lsda ? 1 : 0, 1, &Z, nlev.data(), n.data(), l.data(), occ.data(), alpha, levelsMode, 0,
                                                   &opt, &scf), rt.ctx(), "dfta_scf_create_config");
     }
+    if (exchange != DFTA_EXCHANGE_FUNCTIONAL) dfta_compat::check(dfta_scf_set_exchange(scf, exchange), rt.ctx(), "dfta_scf_set_exchange");
     const int maxSteps = lsda ? 150 : 100;                                  // DFTAtom.cpp:396 / 908
     for (int sp = 0; sp < maxSteps; ++sp) {
         std::cout << "Step: " << sp << std::endl;

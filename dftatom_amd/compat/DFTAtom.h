@@ -33,6 +33,7 @@ public:
     static int sweepMode;       // DFTA_SWEEPS_EXACT (default) / DFTA_SWEEPS_TOLERANCE (transfer-matrix scans; logarithmic grids of 12 .. 20 levels)
     static int poissonMode;     // -1 (default): as dfta_poisson_create, i.e. exact unless $DFTA_DEBUG POISSON_MODE says otherwise; DFTA_POISSON_EXACT / _TOLERANCE / _ADAPTIVE
     static int mixing;          // DFTA_MIX_LINEAR (default: the reference's mixing, DFTAtom.cpp:332-342) / DFTA_MIX_ANDERSON (about half the SCF steps)
+    static int exchange;        // DFTA_EXCHANGE_FUNCTIONAL (default) / DFTA_EXCHANGE_KLI: self-consistent exchange-only KLI (functional VWN, linear mixing)
     static int functional;      // DFTA_XC_VWN (default: what the reference runs), _CHACHIYO, _CHACHIYO_IMPROVED (LDA only), _PW92, _PBE (logarithmic grid)
     // electron configuration (not in the reference, which runs the neutral Aufbau atom): charge q > 0 runs the cation of dfta_ion_config,
     // a non-empty config the text of dfta_config_parse ("[Ne] 3s2 3p5.5", "2p3/1" LSDA splits); both unset (default): the Aufbau atom

@@ -27,6 +27,8 @@
 //                dfta_scf_form_factors, one launch for the table).  Without it the output is unchanged.
 // --sweeps=exact|tolerance, --poisson=exact|tolerance|adaptive: the opt-in tolerance modes of the device path (include/dftatom_hip.h).
 // --mixing=linear (default, the reference's density mixing) | anderson (Anderson acceleration: about half the SCF steps, same protocol).
+// --exchange=functional (default) | kli: self-consistent exchange-only KLI -- every step's exchange potential from its own orbitals, no
+//                correlation (with --xc=vwn and --mixing=linear only); same protocol, --exchange-table works on top of it.
 // --xc=vwn (default, what the reference runs) | chachiyo | chachiyo-improved (LDA only) | pw92 | pbe (logarithmic grid only).
 // --charge=q: the cation X^q+ (electrons leave the subshell of highest n, then highest l: Fe+ = [Ar] 3d6 4s1);
 // --config="[Ne] 3s2 3p5.5": an explicit, possibly fractional configuration ("2p3/1": LSDA alpha / beta split).  An invalid
@@ -125,6 +127,11 @@ int main(int argc, char** argv)
             DFT::DFTAtom::poissonMode = a == "--poisson=tolerance" ? DFTA_POISSON_TOLERANCE : (a == "--poisson=adaptive" ? DFTA_POISSON_ADAPTIVE : DFTA_POISSON_EXACT);
         } else if (a == "--mixing=linear" || a == "--mixing=anderson") {
             DFT::DFTAtom::mixing = a == "--mixing=anderson" ? DFTA_MIX_ANDERSON : DFTA_MIX_LINEAR;
+        } else if (a == "--exchange=kli" || a == "--exchange=functional") {
+            DFT::DFTAtom::exchange = a == "--exchange=kli" ? DFTA_EXCHANGE_KLI : DFTA_EXCHANGE_FUNCTIONAL;
+        } else if (a.rfind("--exchange=", 0) == 0) {
+            std::cerr << "unknown exchange " << a.substr(11) << std::endl;
+            bad = true;
         } else if (a.rfind("--mixing=", 0) == 0) {
             std::cerr << "unknown mixing " << a.substr(9) << std::endl;
             bad = true;
@@ -168,6 +175,7 @@ int main(int argc, char** argv)
                   << "       " << argv[0] << " --ini DFTAtom.ini [--uniform] [chained] [--integrator=NAME] [--xc=NAME] [--charge=q | --config=TEXT]\n"
                   << "       --xc=vwn (default) | chachiyo | chachiyo-improved | pw92 | pbe\n"
                   << "       --mixing=linear (default) | anderson: Anderson density mixing, fewer SCF steps\n"
+                  << "       --exchange=functional (default) | kli: self-consistent exchange-only KLI (no correlation; --xc=vwn, --mixing=linear)\n"
                   << "       --orbital-table: after Finished!, one line per level with <r>, <r^2>, T and r_peak of its orbital\n"
                   << "       --slater-table: after Finished!, the Slater integrals F^k, G^k of the levels, then E_H and the exact-exchange energy\n"
                   << "       --exchange-table: after Finished!, per shell its eigenvalue, the orbital averages of the Fock, Slater and KLI exchange potentials and the KLI constant, then E_x and r vKLI at the density's outermost node\n"

@@ -14,12 +14,14 @@
 //   k_exchange_kli        one lane per node: vKLI from vS, D and the constants c.
 //   k_exchange_reduce     one workgroup per quadrature (vbarHF_a, vbarS_a, vbarKLI_a, S_ab): lane t adds the weighted terms of the nodes
 //                         t, t + 256, ... to one accumulator; the end is k_orbital_properties' tree.
+// The per-node and per-quadrature arithmetic of the last three is exchange_device.h's, shared with the batched stage of kli_stage.hip.
 // Every shape is a function of N alone.  No floating-point atomics; no workgroup waits for another.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <vector>
 
+#include "exchange_device.h"
 #include "exchange_plan.h"
 #include "internal.h"
 
@@ -30,11 +32,8 @@ constexpr int kYkPer = 4;                            // consecutive nodes per la
 constexpr int kYkTile = kYkThreads * kYkPer;         // nodes per tile
 constexpr int kYkHalo = 3;                           // nodes staged in front of and behind a tile: the reach of the end stencils
 constexpr int kYkSlots = kYkTile + 2 * kYkHalo;      // slot q of the running tile [t0, t0 + kYkTile) holds node t0 - kYkHalo + q
-constexpr int kPwThreads = 256;
-constexpr int kRedThreads = 256;
-
-// Simpson 3/8 weight of node i without the factor 3/8 (Integral.h:50-73)
-__device__ __forceinline__ double simpson38_weight(int i, int N) { return (i == 0 || i == N - 1) ? 1. : (i % 3 == 0 ? 2. : 3.); }
+using dfta_exchange_dev::kPwThreads;
+using dfta_exchange_dev::kRedThreads;
 
 // the increment d_i of a cumulative integral at node i, 1 <= i <= N-1, from the slots around q (the header states these orders)
 __device__ __forceinline__ double increment(const double* g, int q, int i, int N)
@@ -172,20 +171,10 @@ __global__ __launch_bounds__(kPwThreads) void k_exchange_pointwise(int N, int no
 {
     const int i = blockIdx.x * kPwThreads + threadIdx.x;
     if (i >= N) return;
-    double den = 0., num = 0.;
-    for (int a = 0; a < norb; ++a) {
-        double acc = 0.;
-        for (int e = first[a]; e < first[a + 1]; ++e) {
-            const int b = tab[dfta_exchange::kTabInts * e + 1], row = tab[dfta_exchange::kTabInts * e + 3];
-            acc += coef[e] * (Y[(size_t)row * N + i] * U[(size_t)b * N + i]);
-        }
-        X[(size_t)a * N + i] = acc;
-        const double ua = U[(size_t)a * N + i];
-        den += occ[a] * (ua * ua);
-        num += occ[a] * (ua * acc);
-    }
+    double den, v;
+    dfta_exchange_dev::pointwise_node(N, i, norb, U, occ, first, tab, coef, Y, X, &den, &v);
     D[i] = den;
-    vS[i] = den > 0. ? -(num / den) : 0.;
+    vS[i] = v;
 }
 
 __global__ __launch_bounds__(kPwThreads) void k_exchange_kli(int N, int norb, int homo, const double* __restrict__ U, const double* __restrict__ occ,
@@ -194,14 +183,7 @@ __global__ __launch_bounds__(kPwThreads) void k_exchange_kli(int N, int norb, in
 {
     const int i = blockIdx.x * kPwThreads + threadIdx.x;
     if (i >= N) return;
-    double acc = 0.;
-    for (int a = 0; a < norb; ++a) {
-        if (a == homo) continue;
-        const double ua = U[(size_t)a * N + i];
-        acc += (occ[a] * (ua * ua)) * c[a];
-    }
-    const double den = D[i];
-    vKLI[i] = den > 0. ? vS[i] + acc / den : 0.;
+    vKLI[i] = dfta_exchange_dev::kli_node(N, i, norb, homo, U, occ, c, D[i], vS[i]);
 }
 
 // one quadrature per workgroup: red rows kind, a, b
@@ -211,34 +193,11 @@ __global__ __launch_bounds__(kRedThreads) void k_exchange_reduce(int N, double h
                                                                  const int* __restrict__ red, double* __restrict__ out)
 {
     __shared__ double part[kRedThreads / 64];
-    const int tid = threadIdx.x;
     const int kind = red[dfta_exchange::kRedInts * blockIdx.x], a = red[dfta_exchange::kRedInts * blockIdx.x + 1],
               b = red[dfta_exchange::kRedInts * blockIdx.x + 2];
-    const double* __restrict__ ua = U + (size_t)a * N;
-    const double* __restrict__ ub = U + (size_t)b * N;
-    const double* __restrict__ xa = X + (size_t)a * N;
-    const double* __restrict__ v = kind == dfta_exchange::kRedKLI ? vKLI : vS;
-    double acc = 0.;
-    for (int i = tid; i < N; i += kRedThreads) {
-        const double sc = cnst[i] * hstep, w = simpson38_weight(i, N), u = ua[i];
-        double t;
-        if (kind == dfta_exchange::kRedHF) t = (u * xa[i]) * sc;
-        else if (kind == dfta_exchange::kRedPair) {
-            const double den = D[i], u2 = ub[i];
-            t = den == 0. ? 0. : (((u * u) * (u2 * u2)) / den) * sc;
-        } else t = ((u * u) * v[i]) * sc;
-        acc += w * t;
-    }
-    // the tree: lanes of a wave by xor shuffles 32 .. 1, then the four waves as (w0 + w1) + (w2 + w3)
-    for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
-    if ((tid & 63) == 0) part[tid >> 6] = acc;
-    __syncthreads();
-    if (tid == 0) {
-        const double sum = (part[0] + part[1]) + (part[2] + part[3]);
-        constexpr double coef = 3. / 8.;
-        const double q = sum * coef;
-        out[blockIdx.x] = kind == dfta_exchange::kRedHF ? -q : q;
-    }
+    const double q = dfta_exchange_dev::reduce_block(N, hstep, cnst, U + (size_t)a * N, U + (size_t)b * N, X + (size_t)a * N, D,
+                                                     kind == dfta_exchange::kRedKLI ? vKLI : vS, kind, part);
+    if (threadIdx.x == 0) out[blockIdx.x] = q;
 }
 
 }  // namespace

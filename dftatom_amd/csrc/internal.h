@@ -230,6 +230,8 @@ struct dfta_bessel_scratch {               // the tables of a transform and its 
     // uploads l, the rows' device addresses and q (host arrays), launches, copies the nrow x nq results to out (host) and synchronises
     int run(dfta_ctx* ctx, const dfta_grid* g, int kind, int nrow, const int* l, const double* const* rows, int nq, const double* q, double* out);
 };
+// kli_stage.hip: the budget of a chunk's y rows in MiB: DFTA_DEBUG KLI_Y_MB, or the default
+double dfta_kli_budget_mb();
 // scf.hip: the k_mix launch (DFTA_MIX_LINEAR), same arguments
 int dfta_launch_linear_mix(dfta_ctx* ctx, const dfta_grid* g, int lsda, int natoms, double alpha, double oneMinusAlpha, double* newDensity,
                            double* density, double* dA, double* dB, const int* fin);

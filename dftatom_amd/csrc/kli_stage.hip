@@ -1,0 +1,365 @@
+// kli_stage.hip -- the exchange stage of a self-consistent KLI step: every live spin channel of a batch through one sequence of launches
+// per chunk of whole channels, no host synchronisation in between (include/dftatom_hip.h states the rule; DESIGN.md 4.12 the shapes).
+//
+//   y launch            k_screening_yk of exchange.hip itself, one workgroup per job, the jobs of every channel of the chunk in one launch
+//                       (the job table counts the batch's orbital rows).
+//   k_kli_pointwise     grid (node tile, channel): X_a, D, vS -- the node arithmetic of k_exchange_pointwise (exchange_device.h).
+//   k_kli_reduce        grid (quadrature of the chunk): vbarHF_a, vbarS_a, S_ab -- the lane chains and trees of k_exchange_reduce.
+//   k_kli_solve         one wave per channel: the HOMO from the eigenvalues and occupations, the reduced system (I - M) c = vbarS - vbarHF in
+//                       LDS, Gaussian elimination with partial pivoting in the header's order -- row i of an elimination step is lane i's,
+//                       an element's operations do not depend on that --, back substitution by lane 0; then E_x of the channel, the last
+//                       node with D > 0 and v_raw r there.
+//   k_kli_update        grid (node tile, channel): the KLI pass, the Coulomb tail beyond the last node with D > 0, the mix into vx.
+//   k_kli_assemble      grid (node tile, atom), once per step: Vexc / va / vb / eexc from vx and the mixed densities; E_x of the atom.
+// Every shape is a function of N alone; no floating-point atomics; no workgroup waits for another: a channel's bits do not depend on the
+// batch, its position in it, the chunking or the run.  Built, as everything here, without FMA contraction: the solve repeats the host
+// solve of exchange_plan.cpp operation by operation.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstdlib>
+#include <vector>
+
+#include "exchange_device.h"
+#include "internal.h"
+#include "kli_stage.h"
+
+namespace {
+
+using dfta_exchange_dev::kPwThreads;
+using dfta_exchange_dev::kRedThreads;
+using dfta_kli::Channel;
+constexpr int kSolveThreads = 64;
+constexpr int kSolveLd = 32;                 // row stride of the system in LDS
+
+// X, D, vS of the chunk's channels [c0, c0 + gridDim.y); chunk rows: Y from job j0, X from orbital row u0, D / vS from channel c0
+__global__ __launch_bounds__(kPwThreads) void k_kli_pointwise(int N, int c0, int j0, int u0, const Channel* __restrict__ chs,
+                                                              const double* __restrict__ U, const double* __restrict__ occ,
+                                                              const int* __restrict__ first, const int* __restrict__ tab,
+                                                              const double* __restrict__ coef, const double* __restrict__ Y,
+                                                              double* __restrict__ X, double* __restrict__ D, double* __restrict__ vS)
+{
+    const Channel ch = chs[c0 + blockIdx.y];
+    const int i = blockIdx.x * kPwThreads + threadIdx.x;
+    if (ch.norb == 0 || i >= N) return;
+    double den, v;
+    dfta_exchange_dev::pointwise_node(N, i, ch.norb, U + (size_t)ch.u0 * N, occ + ch.u0, first + ch.first0,
+                                      tab + (size_t)dfta_kli::kTabInts * ch.tab0, coef + ch.tab0, Y + (size_t)(ch.job0 - j0) * N,
+                                      X + (size_t)(ch.u0 - u0) * N, &den, &v);
+    D[(size_t)blockIdx.y * N + i] = den;
+    vS[(size_t)blockIdx.y * N + i] = v;
+}
+
+// quadrature q0 + blockIdx.x of the batch's table
+__global__ __launch_bounds__(kRedThreads) void k_kli_reduce(int N, double hstep, int q0, int c0, int u0, const Channel* __restrict__ chs,
+                                                            const int* __restrict__ red, const double* __restrict__ cnst,
+                                                            const double* __restrict__ U, const double* __restrict__ X,
+                                                            const double* __restrict__ D, const double* __restrict__ vS, double* __restrict__ out)
+{
+    __shared__ double part[kRedThreads / 64];
+    const int* row = red + (size_t)dfta_kli::kRedInts * (q0 + blockIdx.x);
+    const int kind = row[0], a = row[1], b = row[2], c = row[3];
+    const Channel ch = chs[c];
+    const double* Uc = U + (size_t)ch.u0 * N;
+    const double q = dfta_exchange_dev::reduce_block(N, hstep, cnst, Uc + (size_t)a * N, Uc + (size_t)b * N, X + (size_t)(ch.u0 - u0 + a) * N,
+                                                     D + (size_t)(c - c0) * N, vS + (size_t)(c - c0) * N, kind, part);
+    if (threadIdx.x == 0) out[q0 + blockIdx.x] = q;
+}
+
+// the constants c of channel c0 + blockIdx.x, its HOMO, E_x, last node with D > 0 and v_raw r there
+__global__ __launch_bounds__(kSolveThreads) void k_kli_solve(int N, int c0, const Channel* __restrict__ chs, const double* __restrict__ occ,
+                                                             const char* __restrict__ Ebase, size_t Estride, const double* __restrict__ redout,
+                                                             const double* __restrict__ r, const double* __restrict__ U,
+                                                             const double* __restrict__ D, const double* __restrict__ vS,
+                                                             double* __restrict__ cOut, double* __restrict__ vbarHF, int* __restrict__ homoOut,
+                                                             double* __restrict__ ExCh, int* __restrict__ ilastOut, double* __restrict__ tailOut,
+                                                             int* __restrict__ status)
+{
+    __shared__ double A[dfta_kli::kSolveMax * kSolveLd], rhs[kSolveLd], sol[kSolveLd], sOcc[kSolveLd], sE[kSolveLd], sC[kSolveLd];
+    __shared__ int idx[kSolveLd];
+    const int lane = threadIdx.x, c = c0 + blockIdx.x;
+    const Channel ch = chs[c];
+    const int n = ch.norb;
+    if (n == 0) return;                      // homo, E_x, ilast keep what creation wrote: -1, 0, -1
+    if (lane < n) {
+        sOcc[lane] = occ[ch.u0 + lane];
+        sE[lane] = *reinterpret_cast<const double*>(Ebase + (size_t)(ch.u0 + lane) * Estride);
+    }
+    __syncthreads();
+    int h = -1;                              // every lane alike: the highest eigenvalue among the occupied shells, ties to the higher index
+    for (int a = 0; a < n; ++a)
+        if (sOcc[a] > 0. && (h < 0 || sE[a] >= sE[h])) h = a;
+    const int H = n - 1;
+    const double* vHF = redout + ch.red0;
+    const double* vSb = vHF + n;
+    const double* S = vSb + n;               // pair (a <= b) at a n - a (a - 1) / 2 + (b - a)
+    if (lane < H) {
+        const int a = lane < h ? lane : lane + 1;
+        idx[lane] = a;
+        rhs[lane] = vSb[a] - vHF[a];
+    }
+    if (lane < n) sC[lane] = 0.;
+    __syncthreads();
+    for (int e = lane; e < H * H; e += kSolveThreads) {
+        const int i = e / H, j = e % H, a = idx[i], b = idx[j];
+        const int lo = a < b ? a : b, hi = a < b ? b : a;
+        const double M = S[lo * n - lo * (lo - 1) / 2 + (hi - lo)] * sOcc[b];
+        A[i * kSolveLd + j] = (i == j ? 1. : 0.) - M;
+    }
+    __syncthreads();
+    bool bad = false;
+    for (int j = 0; j < H; ++j) {
+        int p = j;                           // every lane alike
+        for (int i = j + 1; i < H; ++i)
+            if (fabs(A[i * kSolveLd + j]) > fabs(A[p * kSolveLd + j])) p = i;
+        __syncthreads();
+        if (p != j) {
+            if (lane < H) { const double t = A[j * kSolveLd + lane]; A[j * kSolveLd + lane] = A[p * kSolveLd + lane]; A[p * kSolveLd + lane] = t; }
+            if (lane == kSolveThreads - 1) { const double t = rhs[j]; rhs[j] = rhs[p]; rhs[p] = t; }
+        }
+        __syncthreads();
+        const double piv = A[j * kSolveLd + j];
+        if (piv == 0. || !isfinite(piv)) { bad = true; break; }
+        if (lane > j && lane < H) {
+            const double f = A[lane * kSolveLd + j] / piv;
+            for (int m = j + 1; m < H; ++m) A[lane * kSolveLd + m] = A[lane * kSolveLd + m] - f * A[j * kSolveLd + m];
+            rhs[lane] = rhs[lane] - f * rhs[j];
+        }
+        __syncthreads();
+    }
+    if (lane == 0) {
+        if (!bad)
+            for (int i = H - 1; i >= 0; --i) {
+                double t = rhs[i];
+                for (int m = i + 1; m < H; ++m) t = t - A[i * kSolveLd + m] * sol[m];
+                sol[i] = t / A[i * kSolveLd + i];
+            }
+        for (int i = 0; i < H; ++i) sC[idx[i]] = bad ? nan("") : sol[i];
+        double acc = 0.;
+        for (int a = 0; a < n; ++a) acc += sOcc[a] * vHF[a];
+        ExCh[c] = 0.5 * acc;
+        homoOut[c] = h;
+        status[c] = bad ? 1 : 0;
+    }
+    __syncthreads();
+    if (lane < n) {
+        cOut[ch.u0 + lane] = sC[lane];
+        vbarHF[ch.u0 + lane] = vHF[lane];
+    }
+    const double* Dc = D + (size_t)blockIdx.x * N;
+    int il = -1;
+    for (int i = lane; i < N; i += kSolveThreads)
+        if (Dc[i] > 0.) il = i;              // ascending: the lane's last one stays
+    for (int off = 32; off > 0; off >>= 1) il = max(il, __shfl_xor(il, off));
+    if (lane == 0) {
+        ilastOut[c] = il;
+        double tail = 0.;
+        if (il >= 0) {
+            const double v = dfta_exchange_dev::kli_node(N, il, n, h, U + (size_t)ch.u0 * N, sOcc, sC, Dc[il], vS[(size_t)blockIdx.x * N + il]);
+            tail = v * r[il];
+        }
+        tailOut[c] = tail;
+    }
+}
+
+// v_raw and vx of the chunk's channels
+__global__ __launch_bounds__(kPwThreads) void k_kli_update(int N, int c0, const Channel* __restrict__ chs, const double* __restrict__ occ,
+                                                           const double* __restrict__ U, const double* __restrict__ cArr,
+                                                           const int* __restrict__ homo, const double* __restrict__ D,
+                                                           const double* __restrict__ vS, const int* __restrict__ ilast,
+                                                           const double* __restrict__ tail, const double* __restrict__ r, int first, double alpha,
+                                                           double oneMinusAlpha, double* __restrict__ vx, double* __restrict__ vraw)
+{
+    const int c = c0 + blockIdx.y;
+    const Channel ch = chs[c];
+    const int i = blockIdx.x * kPwThreads + threadIdx.x;
+    if (ch.norb == 0 || i >= N) return;
+    const size_t o = (size_t)blockIdx.y * N + i, oc = (size_t)c * N + i;
+    double v = dfta_exchange_dev::kli_node(N, i, ch.norb, homo[c], U + (size_t)ch.u0 * N, occ + ch.u0, cArr + ch.u0, D[o], vS[o]);
+    const int il = ilast[c];
+    if (il >= 0 && i > il) v = tail[c] / r[i];           // the Coulomb tail, continuous at il
+    vraw[oc] = v;
+    vx[oc] = first ? v : alpha * vx[oc] + oneMinusAlpha * v;
+}
+
+__global__ __launch_bounds__(kPwThreads) void k_kli_assemble(int N, int lsda, const int* __restrict__ fin, const double* __restrict__ vx,
+                                                             const double* __restrict__ ExCh, const double* __restrict__ density,
+                                                             const double* __restrict__ dA, const double* __restrict__ dB,
+                                                             double* __restrict__ Vexc, double* __restrict__ va, double* __restrict__ vb,
+                                                             double* __restrict__ eexc, double* __restrict__ ExAtom)
+{
+    const int a = blockIdx.y;
+    if (fin[a]) return;                      // a finished atom keeps its potential and its E_x
+    const int i = blockIdx.x * kPwThreads + threadIdx.x;
+    if (i == 0) ExAtom[a] = lsda ? ExCh[2 * a] + ExCh[2 * a + 1] : 2. * ExCh[a];
+    if (i >= N) return;
+    const size_t o = (size_t)a * N + i;
+    double v;
+    if (!lsda) v = vx[o];
+    else {
+        const double x = vx[((size_t)2 * a) * N + i], y = vx[((size_t)2 * a + 1) * N + i];
+        const double rho = density[o];
+        va[o] = x;
+        vb[o] = y;
+        v = rho > 0. ? (dA[o] * x + dB[o] * y) / rho : 0.;
+    }
+    Vexc[o] = v;
+    eexc[o] = -v;
+}
+
+}  // namespace
+
+void dfta_kli_stage::reset()
+{
+    plan = dfta_kli::Plan();
+    max_rows = 0; caps = {0, 0, 0}; N = 0; natoms = 0; timed = false;
+    d_ch.reset();
+    for (DevBuf<int>* b : {&d_jobs, &d_first, &d_tab, &d_red, &d_homo, &d_ilast, &d_status}) b->reset();
+    for (DevBuf<double>* b : {&d_coef, &d_occ, &d_y, &d_X, &d_DvS, &d_redout, &d_vx, &d_vraw, &d_vbarHF, &d_c, &d_tail, &d_ExCh, &d_ExAtom}) b->reset();
+    h_status.clear(); bounds.clear();
+}
+
+int dfta_kli_stage::create(dfta_ctx* ctx, const dfta_grid* g, int nch, const int* norb, const int* l, const double* occ, const int* atom,
+                           int natoms_, double y_mb)
+{
+    reset();
+    if (const char* msg = dfta_kli::check_channels(nch, norb, l, occ)) DFTA_REQUIRE(ctx, false, msg);
+    DFTA_REQUIRE(ctx, g->N >= 5, "KLI channels: the grid needs 5 nodes");
+    DFTA_REQUIRE(ctx, nch >= 1 && nch <= 65535, "KLI channels: 1 .. 65535 channels");
+    DFTA_REQUIRE(ctx, dfta_kli::plan_channels(nch, norb, l, occ, atom, &plan) == 0, "KLI channels: the tables");
+    hipStream_t st = ctx->stream;
+    const size_t n = g->N, no = std::max(plan.norb_total, 1);
+    max_rows = dfta_kli::budget_rows(y_mb, g->N);
+    caps = dfta_kli::capacities(plan, max_rows);
+    hipError_t e = hipSuccess;
+    auto al = [&](auto& buf, size_t cnt) { if (e == hipSuccess) e = buf.alloc(std::max<size_t>(cnt, 1)); };
+    al(d_ch, nch); al(d_jobs, plan.jobs.size()); al(d_first, plan.first.size()); al(d_tab, plan.tab.size()); al(d_red, plan.red.size());
+    al(d_coef, plan.coef.size()); al(d_occ, no);
+    al(d_y, (size_t)caps.yrows * n); al(d_X, (size_t)caps.xrows * n); al(d_DvS, 2 * (size_t)caps.chans * n); al(d_redout, plan.nred());
+    al(d_vx, (size_t)nch * n); al(d_vraw, (size_t)nch * n); al(d_vbarHF, no); al(d_c, no); al(d_tail, nch); al(d_ExCh, nch);
+    al(d_ExAtom, natoms_); al(d_homo, nch); al(d_ilast, nch); al(d_status, nch);
+    for (auto& v : ev) if (e == hipSuccess && !v.e) e = hipEventCreate(&v.e);
+    if (e != hipSuccess) {
+        snprintf(ctx->err, sizeof(ctx->err), "KLI stage alloc: %s", hipGetErrorString(e));
+        reset();
+        (void)hipGetLastError();
+        return e == hipErrorOutOfMemory ? DFTA_ERR_NOMEM : DFTA_ERR_HIP;
+    }
+    auto up = [&](auto& buf, const auto& vec) {
+        if (e == hipSuccess && !vec.empty()) e = hipMemcpyAsync(buf.p, vec.data(), sizeof(vec[0]) * vec.size(), hipMemcpyHostToDevice, st);
+    };
+    up(d_ch, plan.ch); up(d_jobs, plan.jobs); up(d_first, plan.first); up(d_tab, plan.tab); up(d_red, plan.red); up(d_coef, plan.coef);
+    if (e == hipSuccess && plan.norb_total > 0) e = hipMemcpyAsync(d_occ.p, occ, sizeof(double) * plan.norb_total, hipMemcpyHostToDevice, st);
+    auto zero = [&](auto& buf, int byte) { if (e == hipSuccess) e = hipMemsetAsync(buf.p, byte, sizeof(*buf.p) * buf.n, st); };
+    zero(d_vx, 0); zero(d_vraw, 0); zero(d_vbarHF, 0); zero(d_c, 0); zero(d_tail, 0); zero(d_ExCh, 0); zero(d_ExAtom, 0); zero(d_status, 0);
+    zero(d_homo, 0xff); zero(d_ilast, 0xff);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);                   // occ is the caller's; the plan's vectors stay
+    if (e != hipSuccess) {
+        snprintf(ctx->err, sizeof(ctx->err), "KLI stage tables: %s", hipGetErrorString(e));
+        reset();
+        return DFTA_ERR_HIP;
+    }
+    N = g->N; natoms = natoms_;
+    h_status.assign(nch, 0);
+    return DFTA_OK;
+}
+
+int dfta_kli_stage::run(dfta_ctx* ctx, const dfta_grid* g, const double* dU, const void* Ebase, size_t Estride, const unsigned char* live,
+                        bool first, double alpha, double oneMinusAlpha)
+{
+    hipStream_t st = ctx->stream;
+    const double hstep = g->uniform ? g->h : 1.0;
+    const int nblk = (N + kPwThreads - 1) / kPwThreads;
+    double* dD = d_DvS.p;
+    double* dvS = d_DvS.p + (size_t)caps.chans * N;
+    dfta_kli::plan_chunks(plan, live, max_rows, &bounds);
+    DFTA_HIP(ctx, hipEventRecord(ev[0], st));
+    for (size_t k = 0; k + 1 < bounds.size(); k += 2) {
+        const int c0 = bounds[k], c1 = bounds[k + 1], nc = c1 - c0;
+        const dfta_kli::Channel& a = plan.ch[c0];
+        const dfta_kli::Channel& z = plan.ch[c1 - 1];
+        const int njobs = z.job0 + z.njobs - a.job0, nred = z.red0 + z.nred - a.red0, norb = z.u0 + z.norb - a.u0;
+        DFTA_REQUIRE(ctx, njobs <= caps.yrows && norb <= caps.xrows && nc <= caps.chans, "KLI stage: a chunk beyond its buffers");
+        int rc = dfta_launch_screening_yk(ctx, g, dU, njobs, d_jobs.p + (size_t)dfta_kli::kJobInts * a.job0, d_y.p);
+        if (rc) return rc;
+        hipLaunchKernelGGL(k_kli_pointwise, dim3(nblk, nc), dim3(kPwThreads), 0, st, N, c0, a.job0, a.u0, d_ch.p, dU, d_occ.p, d_first.p, d_tab.p,
+                           d_coef.p, d_y.p, d_X.p, dD, dvS);
+        DFTA_CHECK_LAUNCH(ctx);
+        hipLaunchKernelGGL(k_kli_reduce, dim3(nred), dim3(kRedThreads), 0, st, N, hstep, a.red0, c0, a.u0, d_ch.p, d_red.p, g->d_cnst.p, dU, d_X.p, dD,
+                           dvS, d_redout.p);
+        DFTA_CHECK_LAUNCH(ctx);
+        hipLaunchKernelGGL(k_kli_solve, dim3(nc), dim3(kSolveThreads), 0, st, N, c0, d_ch.p, d_occ.p, static_cast<const char*>(Ebase), Estride,
+                           d_redout.p, g->d_r.p, dU, dD, dvS, d_c.p, d_vbarHF.p, d_homo.p, d_ExCh.p, d_ilast.p, d_tail.p, d_status.p);
+        DFTA_CHECK_LAUNCH(ctx);
+        hipLaunchKernelGGL(k_kli_update, dim3(nblk, nc), dim3(kPwThreads), 0, st, N, c0, d_ch.p, d_occ.p, dU, d_c.p, d_homo.p, dD, dvS, d_ilast.p,
+                           d_tail.p, g->d_r.p, first ? 1 : 0, alpha, oneMinusAlpha, d_vx.p, d_vraw.p);
+        DFTA_CHECK_LAUNCH(ctx);
+    }
+    DFTA_HIP(ctx, hipEventRecord(ev[1], st));
+    timed = true;
+    DFTA_HIP(ctx, hipMemcpyAsync(h_status.data(), d_status.p, sizeof(int) * plan.nch(), hipMemcpyDeviceToHost, st));
+    return DFTA_OK;
+}
+
+int dfta_kli_stage::assemble(dfta_ctx* ctx, const dfta_grid* g, int lsda, const double* density, const double* dA, const double* dB,
+                             const int* fin, double* Vexc, double* va, double* vb, double* eexc)
+{
+    hipLaunchKernelGGL(k_kli_assemble, dim3((N + kPwThreads - 1) / kPwThreads, natoms), dim3(kPwThreads), 0, ctx->stream, N, lsda, fin, d_vx.p,
+                       d_ExCh.p, density, dA, dB, Vexc, va, vb, eexc, d_ExAtom.p);
+    DFTA_CHECK_LAUNCH(ctx);
+    return DFTA_OK;
+}
+
+double dfta_kli_budget_mb()
+{
+    const char* v = dfta_knob("KLI_Y_MB");
+    return v && *v ? atof(v) : kKliDefaultYMB;
+}
+
+// ---- the stage on caller-supplied channels (host pointers) ---------------------------------------------------------------------------
+extern "C" {
+
+int dfta_kli_channels(dfta_ctx* ctx, const dfta_grid* g, int nch, const int* norb, const int* l, const double* occ, const double* E,
+                      const double* u, int first_step, double alpha, double* vx_inout, double* v_raw, double* vbarHF, double* c, int* homo,
+                      double* Ex)
+{
+    if (!ctx || !g) return DFTA_ERR_INVALID;
+    DFTA_ENTER(ctx);
+    DFTA_REQUIRE(ctx, nch >= 0, "dfta_kli_channels: nch");
+    if (nch == 0) return DFTA_OK;
+    DFTA_REQUIRE(ctx, norb, "dfta_kli_channels: norb");
+    DFTA_REQUIRE(ctx, alpha >= 0 && alpha <= 1, "dfta_kli_channels: alpha");
+    long total = 0;
+    for (int k = 0; k < nch; ++k) total += norb[k] > 0 ? norb[k] : 0;
+    DFTA_REQUIRE(ctx, total == 0 || (l && occ && E && u), "dfta_kli_channels: l / occ / E / u");
+    DFTA_REQUIRE(ctx, first_step || vx_inout, "dfta_kli_channels: a later step mixes into vx_inout");
+    dfta_kli_stage stage;
+    int rc = stage.create(ctx, g, nch, norb, l, occ, nullptr, 0, dfta_kli_budget_mb());
+    if (rc) return rc;
+    hipStream_t st = ctx->stream;
+    const size_t N = g->N, no = stage.plan.norb_total;
+    DevBuf<double> dU, dE;
+    DFTA_HIP(ctx, dU.alloc(std::max<size_t>(no * N, 1)));
+    DFTA_HIP(ctx, dE.alloc(std::max<size_t>(no, 1)));
+    if (no) {
+        DFTA_HIP(ctx, hipMemcpyAsync(dU.p, u, sizeof(double) * no * N, hipMemcpyHostToDevice, st));
+        DFTA_HIP(ctx, hipMemcpyAsync(dE.p, E, sizeof(double) * no, hipMemcpyHostToDevice, st));
+    }
+    if (!first_step) DFTA_HIP(ctx, hipMemcpyAsync(stage.d_vx.p, vx_inout, sizeof(double) * nch * N, hipMemcpyHostToDevice, st));
+    DFTA_HIP(ctx, hipEventRecord(ctx->ev[0], st));     // dfta_ctx_last_kernel_ms: the whole stage
+    rc = stage.run(ctx, g, dU.p, dE.p, sizeof(double), nullptr, first_step != 0, alpha, 1. - alpha);
+    if (rc) return rc;
+    DFTA_HIP(ctx, hipEventRecord(ctx->ev[1], st));
+    ctx->have_kernel_time = true;
+    if (vx_inout) DFTA_HIP(ctx, hipMemcpyAsync(vx_inout, stage.d_vx.p, sizeof(double) * nch * N, hipMemcpyDeviceToHost, st));
+    if (v_raw) DFTA_HIP(ctx, hipMemcpyAsync(v_raw, stage.d_vraw.p, sizeof(double) * nch * N, hipMemcpyDeviceToHost, st));
+    if (vbarHF && no) DFTA_HIP(ctx, hipMemcpyAsync(vbarHF, stage.d_vbarHF.p, sizeof(double) * no, hipMemcpyDeviceToHost, st));
+    if (c && no) DFTA_HIP(ctx, hipMemcpyAsync(c, stage.d_c.p, sizeof(double) * no, hipMemcpyDeviceToHost, st));
+    if (homo) DFTA_HIP(ctx, hipMemcpyAsync(homo, stage.d_homo.p, sizeof(int) * nch, hipMemcpyDeviceToHost, st));
+    if (Ex) DFTA_HIP(ctx, hipMemcpyAsync(Ex, stage.d_ExCh.p, sizeof(double) * nch, hipMemcpyDeviceToHost, st));
+    DFTA_HIP(ctx, hipStreamSynchronize(st));
+    return DFTA_OK;
+}
+
+}  // extern "C"

@@ -148,8 +148,10 @@ __global__ void k_tail(const AtomState* __restrict__ atoms, int lsda, int N, con
 }
 
 // energy assembly and the reference's stop test (DFTAtom.cpp:459-481 / 985-1006); one thread per atom
+// Ex: null, or per atom the exchange energy of an orbital-dependent exchange (DFTA_EXCHANGE_KLI), added to eExcDif
 __global__ void k_energies(AtomState* __restrict__ atoms, int natoms, const dfta::Job* __restrict__ jobs,
-                           const double* __restrict__ occ, const double* __restrict__ integrals, double* __restrict__ records, int* __restrict__ fin)
+                           const double* __restrict__ occ, const double* __restrict__ integrals, double* __restrict__ records, int* __restrict__ fin,
+                           const double* __restrict__ Ex)
 {
     const int a = blockIdx.x * blockDim.x + threadIdx.x;
     if (a >= natoms) return;
@@ -164,7 +166,7 @@ __global__ void k_energies(AtomState* __restrict__ atoms, int natoms, const dfta
     const double* I = integrals + (size_t)a * 5;
     const double Enuclear = -fourM_PI * I[0];
     double Exc = fourM_PI * I[1];
-    const double eExcDif = fourM_PI * I[2];
+    const double eExcDif = Ex ? fourM_PI * I[2] + Ex[a] : fourM_PI * I[2];
     Exc += eExcDif;
     const double Ehartree = -2 * kPi * I[3];
     const double Epotential = fourM_PI * I[4];
@@ -212,6 +214,20 @@ __global__ void k_scatter_rows(const double* __restrict__ src, const int* __rest
     const double* s = src + (size_t)blockIdx.y * N;
     double* d = dst + (size_t)idx[blockIdx.y] * N;
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < N; i += gridDim.x * blockDim.x) d[i] = s[i];
+}
+
+// DFTA_EXCHANGE_KLI, in place of scf_xc: the exchange stage on the step's orbitals for every live channel, then Vexc / va / vb / eexc
+static int scf_kli(dfta_scf* s)
+{
+    const int nspin = s->nspin;
+    s->h_live_ch.resize((size_t)s->nV);
+    for (int a = 0; a < s->natoms; ++a)
+        for (int sp = 0; sp < nspin; ++sp) s->h_live_ch[(size_t)a * nspin + sp] = s->h_atoms[a].finished ? 0 : 1;
+    const dfta::Job* jobs = s->solver.d_jobs.p;
+    int rc = s->kli.run(s->ctx, s->g, s->solver.d_Psi.p, &jobs->E, sizeof(dfta::Job), s->h_live_ch.data(), s->steps_done == 1, s->alpha,
+                        1. - s->alpha);
+    if (rc) return rc;
+    return s->kli.assemble(s->ctx, s->g, s->lsda, s->d_density.p, s->d_dA.p, s->d_dB.p, s->d_fin.p, s->d_Vexc.p, s->d_va.p, s->d_vb.p, s->d_eexc.p);
 }
 
 static int scf_xc(dfta_scf* s)
@@ -326,6 +342,7 @@ int dfta_scf_create_config(dfta_ctx* ctx, const dfta_grid* g, int lsda, int nato
     rc = dfta_poisson_take_vcycles(s->poisson, &dummy);
     if (rc) return rc;
     s->debug_levels = dfta_knob("DEBUG_LEVELS") != nullptr;
+    s->kli_y_mb = dfta_kli_budget_mb();
     s->h_frozen.assign(s->cfg.specs.size(), 0);
     guard.s = nullptr;
     *out = s;
@@ -528,7 +545,8 @@ int dfta_scf_step(dfta_scf* s, dfta_step_stats* stats)
         }
     }
     dfta_range r_tail("dfta: XC + integrands + ordered integrals + energies");
-    rc = scf_xc(s);
+    const bool kli = s->exchange_mode == DFTA_EXCHANGE_KLI;
+    rc = kli ? scf_kli(s) : scf_xc(s);
     if (rc) return rc;
     hipLaunchKernelGGL(k_tail, grid, block, 0, st, s->d_atoms.p, s->lsda, N, g->d_r, g->d_cnst, s->d_density.p, s->d_dA.p, s->d_dB.p, s->d_U.p,
                        s->d_Vexc.p, s->d_va.p, s->d_vb.p, s->d_eexc.p, s->d_V.p, s->d_integrands.p, g->uniform);
@@ -542,12 +560,15 @@ int dfta_scf_step(dfta_scf* s, dfta_step_stats* stats)
         rc = dfta_launch_integrate_ordered(ctx, s->solver.integ_rule, g->uniform ? g->h : 1.0, s->d_integrands, N, natoms * 5, (size_t)N, s->d_integrals);
     if (rc) return rc;
     hipLaunchKernelGGL(k_energies, dim3((natoms + 63) / 64), dim3(64), 0, st, s->d_atoms.p, natoms, s->solver.d_jobs.p, s->solver.d_occ.p, s->d_integrals.p,
-                       s->d_records.p, s->d_fin.p);
+                       s->d_records.p, s->d_fin.p, kli ? s->kli.d_ExAtom.p : nullptr);
     DFTA_CHECK_LAUNCH(ctx);
     DFTA_HIP(ctx, hipEventRecord(s->ev[3], st));
     // the step ends synchronised with the atoms' state on the host: the next step freezes what has finished
     DFTA_HIP(ctx, hipMemcpyAsync(s->h_atoms.data(), s->d_atoms, sizeof(AtomState) * natoms, hipMemcpyDeviceToHost, st));
     DFTA_HIP(ctx, hipStreamSynchronize(st));
+    if (kli)
+        for (int c = 0; c < s->nV; ++c)
+            DFTA_REQUIRE(ctx, !(s->h_live_ch[c] && s->kli.h_status[c]), "exchange stage: the KLI system of a channel is singular or not finite");
     return stats ? scf_fill_stats(s, ls, ps, stats) : DFTA_OK;
 }
 

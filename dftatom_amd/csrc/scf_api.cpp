@@ -319,6 +319,70 @@ int dfta_scf_exchange_potentials(dfta_scf* s, int atom, int spin, double* X, dou
     return DFTA_OK;
 }
 
+// ---- self-consistent exchange-only KLI: the switch and the accessors of the batched exchange stage (kli_stage.hip) -------------------
+int dfta_scf_set_exchange(dfta_scf* s, int exchange)
+{
+    if (!s) return DFTA_ERR_INVALID;
+    dfta_ctx* ctx = s->ctx;
+    DFTA_ENTER(ctx);
+    DFTA_REQUIRE(ctx, s->steps_done == 0, "dfta_scf_set_exchange: after the first step");
+    DFTA_REQUIRE(ctx, exchange == DFTA_EXCHANGE_FUNCTIONAL || exchange == DFTA_EXCHANGE_KLI, "exchange (DFTA_EXCHANGE_FUNCTIONAL or DFTA_EXCHANGE_KLI)");
+    if (exchange == DFTA_EXCHANGE_FUNCTIONAL) {
+        s->kli.reset();
+        s->exchange_mode = exchange;
+        return DFTA_OK;
+    }
+    DFTA_REQUIRE(ctx, s->functional == DFTA_XC_VWN, "DFTA_EXCHANGE_KLI: functional must be DFTA_XC_VWN (exchange-only: no correlation is added)");
+    DFTA_REQUIRE(ctx, s->mixing == DFTA_MIX_LINEAR, "DFTA_EXCHANGE_KLI: mixing must be DFTA_MIX_LINEAR");
+    if (s->exchange_mode == DFTA_EXCHANGE_KLI) return DFTA_OK;
+    // the channels of the batch, atom-major, nspin per atom; occupations N_a (LSDA) or N_a / 2 (LDA)
+    std::vector<int> norb, atom, l;
+    std::vector<double> occ;
+    for (int a = 0; a < s->natoms; ++a)
+        for (int sp = 0; sp < s->nspin; ++sp) {
+            const auto [k0, cnt] = s->channel(a, sp);
+            DFTA_REQUIRE(ctx, k0 == (int)l.size(), "DFTA_EXCHANGE_KLI: the batch's levels are not laid out channel by channel");
+            norb.push_back(cnt);
+            atom.push_back(a);
+            for (int k = 0; k < cnt; ++k) {
+                l.push_back(s->cfg.specs[k0 + k].l);
+                occ.push_back(s->lsda ? s->solver.h_occ[k0 + k] : 0.5 * s->solver.h_occ[k0 + k]);
+            }
+        }
+    const int rc = s->kli.create(ctx, s->g, s->nV, norb.data(), l.data(), occ.data(), atom.data(), s->natoms, s->kli_y_mb);
+    if (rc) return rc;
+    s->exchange_mode = exchange;
+    return DFTA_OK;
+}
+
+int dfta_scf_get_exchange(dfta_scf* s, int atom, int spin, double* vx, double* v_raw, double* Ex)
+{
+    if (!s) return DFTA_ERR_INVALID;
+    dfta_ctx* ctx = s->ctx;
+    DFTA_ENTER(ctx);
+    DFTA_REQUIRE(ctx, s->exchange_mode == DFTA_EXCHANGE_KLI, "dfta_scf_get_exchange: the exchange switch is not DFTA_EXCHANGE_KLI");
+    DFTA_REQUIRE(ctx, s->steps_done > 0, "no SCF step has run yet: there is no exchange potential");
+    DFTA_REQUIRE(ctx, atom >= 0 && atom < s->natoms && spin >= 0 && spin < s->nspin, "atom/spin");
+    const size_t N = s->g->N, c = (size_t)atom * s->nspin + spin;
+    hipStream_t st = ctx->stream;
+    if (vx) DFTA_HIP(ctx, hipMemcpyAsync(vx, s->kli.d_vx.p + c * N, sizeof(double) * N, hipMemcpyDeviceToHost, st));
+    if (v_raw) DFTA_HIP(ctx, hipMemcpyAsync(v_raw, s->kli.d_vraw.p + c * N, sizeof(double) * N, hipMemcpyDeviceToHost, st));
+    if (Ex) DFTA_HIP(ctx, hipMemcpyAsync(Ex, s->kli.d_ExAtom.p + atom, sizeof(double), hipMemcpyDeviceToHost, st));
+    DFTA_HIP(ctx, hipStreamSynchronize(st));
+    return DFTA_OK;
+}
+
+int dfta_scf_exchange_ms(dfta_scf* s, float* ms)
+{
+    if (!s) return DFTA_ERR_INVALID;
+    dfta_ctx* ctx = s->ctx;
+    DFTA_ENTER(ctx);
+    DFTA_REQUIRE(ctx, ms, "ms");
+    DFTA_REQUIRE(ctx, s->exchange_mode == DFTA_EXCHANGE_KLI && s->kli.timed, "dfta_scf_exchange_ms: no exchange stage has run");
+    DFTA_HIP(ctx, hipEventElapsedTime(ms, s->kli.ev[0], s->kli.ev[1]));
+    return DFTA_OK;
+}
+
 // ---- Bessel transforms of the SCF's arrays(bessel.hip; densities and orbitals are read in place) -------------------------------------
 int dfta_scf_form_factors(dfta_scf* s, int nq, const double* q, double* out)
 {

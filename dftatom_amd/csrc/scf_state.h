@@ -3,6 +3,7 @@
 #include <vector>
 
 #include "internal.h"
+#include "kli_stage.h"
 #include "levels.h"
 
 struct AtomState {          // per atom, device
@@ -61,6 +62,12 @@ struct dfta_scf {
     dfta_slater_scratch slater;           // of the Slater-integral calls (slater.hip): job table and results, made by the first such call
     dfta_exchange_scratch exchange;       // of the screening-function and exchange-potential calls (exchange.hip), made by the first such call
     dfta_bessel_scratch bessel;          // of the form-factor and momentum-orbital calls (bessel.hip), made by the first such call
+    // dfta_scf_set_exchange: DFTA_EXCHANGE_KLI replaces the functional's launch of a step by the batched exchange stage (kli_stage.hip);
+    // nothing of it is allocated otherwise
+    int exchange_mode = DFTA_EXCHANGE_FUNCTIONAL;
+    double kli_y_mb = kKliDefaultYMB;     // DFTA_DEBUG KLI_Y_MB, read at creation
+    dfta_kli_stage kli;
+    std::vector<unsigned char> h_live_ch; // per channel (atom x nspin): its atom is live in this step
 
     // first job and number of levels of (atom, spin), and of the atom (alpha levels, then beta levels)
     struct Jobs { int k0, cnt; };

@@ -568,6 +568,57 @@ int  dfta_exchange_potentials(dfta_ctx* ctx, const dfta_grid* g, int norb, const
 int  dfta_scf_exchange_potentials(dfta_scf* s, int atom, int spin, double* X, double* D, double* vS, double* vKLI, double* vbar,
                                   double* M, int* homo);
 
+/* ---- self-consistent exchange-only KLI (beyond the reference) ---------------------------------------------------------------------------
+ * A switch on a created SCF, on the model of dfta_scf_set_integrator: with DFTA_EXCHANGE_KLI a step takes its exchange potential from its
+ * own orbitals -- the KLI potential of the block above, per spin channel -- instead of v_xc of dfta_scf_options::functional, and adds no
+ * correlation.  DFTA_ERR_INVALID (text in dfta_last_error): after the first dfta_scf_step; an unknown value; functional != DFTA_XC_VWN;
+ * mixing != DFTA_MIX_LINEAR.  Both kinds of grid.  Creation is unchanged: the start potential is VWN's on the flat start density.  With
+ * the switch untouched (or DFTA_EXCHANGE_FUNCTIONAL) every launch and every bit of a step is what it was, and nothing is allocated.
+ *
+ * A step under DFTA_EXCHANGE_KLI, per live atom:
+ *  1. level search and density mix as ever; the orbitals u_a are those of the step's input potential.
+ *  2. exchange stage, for every live channel (atom, sigma) with at least one level: occupations and HOMO rule of
+ *     dfta_scf_exchange_potentials (LSDA n_a = N_a; LDA spin 0, n_a = N_a / 2); y rows, X_a, D, vS, the quadratures, the reduced system, c
+ *     and vKLI as the block above defines them: v_raw, vbarHF and c are bit for bit what dfta_scf_exchange_potentials(s, atom, sigma, ..)
+ *     returns on the same state (vKLI; the columns DFTA_XP_HF and DFTA_XP_C of vbar), except:
+ *     tail: with i_last the largest node with D > 0, v_raw,i = (v_raw,i_last r_i_last) / r_i for i > i_last -- the Coulomb tail, continuous
+ *       at i_last, in place of the 0.0 of vKLI there (one product, one quotient); node 0 and every node i < i_last with D = 0 keep 0.0;
+ *     mix: on the first step vx_sigma = v_raw; later vx_sigma,i = alpha vx_sigma,i + (1 - alpha) v_raw,i with the two doubles alpha and
+ *       1 - alpha of the density mix, the products rounded separately;
+ *     energy: E_x,sigma = 0.5 (Sum_a n_a vbarHF_a), a ascending, one accumulator from 0.0; E_x = 2 E_x,0 (LDA), E_x,alpha + E_x,beta
+ *       (LSDA); a channel without levels contributes 0.
+ *     A pivot of the reduced system that is zero or not finite: dfta_scf_step returns DFTA_ERR_INVALID.
+ *  3. Poisson as ever.
+ *  4. in place of the functional's launch: LDA Vexc = vx_0; LSDA va = vx_alpha, vb = vx_beta (a channel without levels: 0),
+ *     Vexc = (dA va + dB vb) / rho where rho > 0, else 0 (two products, one sum, one quotient); both: eexc = -Vexc.  The potential and
+ *     the integrands follow as ever.
+ *  5. energies as ever with eExcDif = 4 pi I[2] + E_x, so that Exc = E_x and Etotal = Eelectronic + Ehartree + eExcDif.
+ * A frozen atom is skipped by every kernel of the stage and keeps vx, v_raw and E_x.  All live channels of a step go through one sequence
+ * of launches per chunk -- whole channels whose y rows fit a budget (DFTA_DEBUG KLI_Y_MB, MiB, default 1024, read at creation; at least
+ * one channel per chunk) -- with no host synchronisation inside the stage; the solve runs on the device and repeats the host solve of
+ * the block above operation by operation.  Shapes depend on N alone, no floating-point atomics: a channel's bits do not depend on the
+ * batch, its position in it, the chunking or the run.
+ * Limits: exchange only (no correlation is added); open-shell atoms whose Aufbau configuration puts a level near zero may not converge
+ * (Fe LSDA oscillates). */
+#define DFTA_EXCHANGE_FUNCTIONAL 0   /* default: v_xc of dfta_scf_options::functional */
+#define DFTA_EXCHANGE_KLI        1   /* exchange-only KLI from the step's orbitals, no correlation */
+int  dfta_scf_set_exchange(dfta_scf* s, int exchange);
+/* vx, v_raw (N each) of channel (atom, spin) and E_x of the atom after the last step in which the atom was live; any pointer may be NULL.
+ * A channel without levels: zeros.  DFTA_ERR_INVALID before the first step or without the switch. */
+int  dfta_scf_get_exchange(dfta_scf* s, int atom, int spin, double* vx, double* v_raw, double* Ex);
+/* HIP-event time of the last step's exchange stage (all chunks), ms */
+int  dfta_scf_exchange_ms(dfta_scf* s, float* ms);
+/* the same stage on caller-supplied channels; host pointers.  norb: nch shell counts (0 .. 32; a channel of 0 shells gives zeros, homo -1);
+ * l, occ (the channel occupations n_a), E (the eigenvalues the HOMO rule reads): the channels' shells end to end; u: their orbitals end
+ * to end, N each.  Every channel with shells needs an occupied one.  first_step != 0: vx = v_raw, vx_inout is written only; otherwise
+ * vx_inout (nch x N) is mixed with alpha and 1 - alpha.  Outputs, any of which may be NULL: v_raw nch x N; vbarHF, c per shell; homo and
+ * Ex (E_x,sigma) per channel.  A channel whose reduced system has a pivot that is zero or not finite gets c = NaN (hence v_raw = NaN);
+ * the other channels are not touched by it.  Chunks as in the SCF (DFTA_DEBUG KLI_Y_MB, read by the call).  The events of
+ * dfta_ctx_last_kernel_ms bracket the stage. */
+int  dfta_kli_channels(dfta_ctx* ctx, const dfta_grid* g, int nch, const int* norb, const int* l, const double* occ, const double* E,
+                       const double* u, int first_step, double alpha, double* vx_inout, double* v_raw, double* vbarHF, double* c, int* homo,
+                       double* Ex);
+
 /* ---- Bessel transforms: X-ray form factors and momentum-space orbitals (beyond the reference) -------------------------------------------
  * With Q[.], s_i = dr/di and the weights of the orbital block, a row f of N doubles, x_i = q r_i (one product, rounded once) and w_i the
  * weight of node i WITHOUT the factor 3/8 (1 at the two end nodes, 2 where i % 3 == 0, 3 elsewhere):
