@@ -38,6 +38,7 @@ SLATER_F, SLATER_G = 0, 1              # kinds of slater_fg_jobs
 XP_COLS = 4                            # DFTA_XP_*: columns of a vbar row of exchange_potentials
 XP_HF, XP_S, XP_C, XP_KLI = range(4)   # <a|v_x^HF,a|a>, <a|vS|a>, the KLI constant c_a, <a|vKLI|a>
 EXCHANGE_FUNCTIONAL, EXCHANGE_KLI = 0, 1   # dfta_scf_set_exchange: v_xc of the functional / exchange-only KLI from the step's orbitals
+EXCHANGE_SIC_KLI = 2                       # ... / VWN plus the Perdew-Zunger self-interaction correction as one KLI potential per channel
 BT_DENSITY, BT_ORBITAL = 0, 1         # DFTA_BT_*: kinds of bessel_transform
 BESSEL_LMAX = 4                        # DFTA_BESSEL_LMAX: largest order of sph_bessel / bessel_transform
 
@@ -179,6 +180,8 @@ SIGNATURES = {
     "dfta_scf_get_exchange": (C.c_int, [vp, C.c_int, C.c_int, c_dp, c_dp, c_dp]),
     "dfta_scf_exchange_ms": (C.c_int, [vp, C.POINTER(C.c_float)]),
     "dfta_kli_channels": (C.c_int, [vp, vp, C.c_int, c_ip, c_ip, c_dp, c_dp, c_dp, C.c_int, C.c_double, c_dp, c_dp, c_dp, c_dp, c_ip, c_dp]),
+    "dfta_sic_channels": (C.c_int, [vp, vp, C.c_int, c_ip, c_ip, c_dp, c_dp, c_dp, C.c_int, C.c_double] + [c_dp] * 12 + [c_ip, c_dp, c_dp, c_dp]),
+    "dfta_scf_sic_table": (C.c_int, [vp, C.c_int, C.c_int, c_dp, c_dp, c_dp, c_dp, c_ip]),
     "dfta_sph_bessel": (C.c_int, [vp, C.c_int, C.c_size_t, c_dp, c_dp]),
     "dfta_bessel_transform": (C.c_int, [vp, vp, C.c_int, C.c_int, c_ip, c_dp, C.c_int, c_dp, c_dp]),
     "dfta_scf_form_factors": (C.c_int, [vp, C.c_int, c_dp, c_dp]),
@@ -704,6 +707,38 @@ def kli_channels(ctx, grid, norb, l, occ, E, u, first_step=True, alpha=0.5, vx=N
     return out
 
 
+def sic_channels(ctx, grid, norb, l, occ, E, u, first_step=True, alpha=0.5, vx=None):
+    """dfta_sic_channels: the SIC-KLI stage of a step on caller-supplied spin channels, arguments as kli_channels.  A dict: y0, vorb, eps,
+    X (sum norb, N): the Hartree potential, the fully polarised VWN potential and energy density of each shell's one-electron density and
+    X_a = (y0_a + v_a) u_a; D, vS, v_raw, vx (nch, N); vbar, vbarS, c, EH, EXC (per shell); M (a list of (norb, norb) matrices, one per
+    channel); homo, Esic (per channel)."""
+    norb = _i32(np.atleast_1d(norb))
+    nch, tot = len(norb), int(np.sum(norb))
+    l, occ, E = _i32(np.atleast_1d(l)), _f64(np.atleast_1d(occ)), _f64(np.atleast_1d(E))
+    u = _f64(u).reshape(-1, grid.N)
+    if not (len(l) == len(occ) == len(E) == u.shape[0] == tot):
+        raise ValueError("%d shells: %d l, %d occ, %d E, %d orbitals" % (tot, len(l), len(occ), len(E), u.shape[0]))
+    if first_step:
+        vx = np.zeros((nch, grid.N))
+    else:
+        vx = _f64(vx).reshape(nch, grid.N).copy()
+    rows, per = max(tot, 1), ("vbar", "vbarS", "c", "EH", "EXC")
+    flatM = np.zeros(max(int(np.sum(norb.astype(np.int64) ** 2)), 1))
+    out = {"vx": vx, "homo": np.zeros(nch, np.int32), "Esic": np.zeros(nch)}
+    out.update({k: np.zeros((rows, grid.N)) for k in ("y0", "vorb", "eps", "X")})
+    out.update({k: np.zeros((nch, grid.N)) for k in ("D", "vS", "v_raw")})
+    out.update({k: np.zeros(rows) for k in per})
+    ctx.check(ctx.lib.dfta_sic_channels(ctx.h, grid.h, nch, _ip(norb), _ip(l), _dp(occ), _dp(E), _dp(u), int(bool(first_step)), float(alpha),
+                                        _dp(out["vx"]), _dp(out["y0"]), _dp(out["vorb"]), _dp(out["eps"]), _dp(out["X"]), _dp(out["D"]),
+                                        _dp(out["vS"]), _dp(out["v_raw"]), _dp(out["vbar"]), _dp(out["c"]), _dp(out["EH"]), _dp(out["EXC"]),
+                                        _ip(out["homo"]), _dp(out["Esic"]), _dp(out["vbarS"]), _dp(flatM)))
+    for k in ("y0", "vorb", "eps", "X") + per:
+        out[k] = out[k][:tot]
+    ends = np.cumsum(norb.astype(np.int64) ** 2)
+    out["M"] = [flatM[e - n * n:e].reshape(n, n) for n, e in zip(norb, ends)]
+    return out
+
+
 def sph_bessel(ctx, l, x):
     """dfta_sph_bessel: the device's spherical Bessel function j_l (0 <= l <= BESSEL_LMAX) at the arguments x >= 0, in x's shape"""
     x = _f64(x)
@@ -775,7 +810,8 @@ class Scf:
         charge: an int for every atom, or a list of ints (ion_config: cations).  Neither: the Aufbau configuration of each Z.
         The nuclear charge stays Z; the electron count sets the start density and the Poisson boundary U(Rmax).
         exchange: EXCHANGE_KLI makes every step take its exchange potential from its own orbitals (exchange-only KLI, no correlation;
-        functional XC_VWN and MIX_LINEAR only): set_exchange() right after creation."""
+        functional XC_VWN and MIX_LINEAR only), EXCHANGE_SIC_KLI keeps VWN and adds the Perdew-Zunger self-interaction correction as
+        one KLI potential per spin channel (-1/r tail, HOMO near -IP; the same two conditions): set_exchange() right after creation."""
         self.ctx, self.grid = ctx, grid
         self.Z = _i32(np.atleast_1d(Z))
         self.natoms = len(self.Z)
@@ -954,14 +990,29 @@ class Scf:
         self.ctx.check(self.ctx.lib.dfta_scf_set_integrator(self.h, int(rule)))
 
     def set_exchange(self, exchange):
-        """EXCHANGE_FUNCTIONAL or EXCHANGE_KLI, before the first step (dfta_scf_set_exchange)."""
+        """EXCHANGE_FUNCTIONAL, EXCHANGE_KLI or EXCHANGE_SIC_KLI, before the first step (dfta_scf_set_exchange)."""
         self.ctx.check(self.ctx.lib.dfta_scf_set_exchange(self.h, int(exchange)))
 
     def exchange(self, atom=0, spin=0):
-        """under EXCHANGE_KLI, after a step: {"vx", "v_raw"} (N each) of channel (atom, spin) and "Ex", the atom's exchange energy"""
+        """under EXCHANGE_KLI or EXCHANGE_SIC_KLI, after a step: {"vx", "v_raw"} (N each) of channel (atom, spin) and "Ex", the atom's
+        exchange energy (EXCHANGE_SIC_KLI: E_SIC)"""
         vx, vr, ex = np.zeros(self.grid.N), np.zeros(self.grid.N), C.c_double()
         self.ctx.check(self.ctx.lib.dfta_scf_get_exchange(self.h, int(atom), int(spin), _dp(vx), _dp(vr), C.byref(ex)))
         return {"vx": vx, "v_raw": vr, "Ex": ex.value}
+
+    def sic_table(self, atom=0, spin=0):
+        """under EXCHANGE_SIC_KLI, after a step: per shell of channel (atom, spin) "EH", "EXC" (the self-Hartree and self-xc energy of one
+        electron in the shell), "vbar" (<a| v_a^SIC |a>), "c" (the KLI constant), and "homo"; None for a channel without levels"""
+        cnt = max(self.ctx.lib.dfta_scf_num_levels(self.h, atom, spin), 0)
+        out = {k: np.zeros(max(cnt, 1)) for k in ("EH", "EXC", "vbar", "c")}
+        homo = C.c_int(-1)
+        self.ctx.check(self.ctx.lib.dfta_scf_sic_table(self.h, int(atom), int(spin), _dp(out["EH"]), _dp(out["EXC"]), _dp(out["vbar"]),
+                                                       _dp(out["c"]), C.byref(homo)))
+        if cnt == 0:
+            return None
+        out = {k: v[:cnt] for k, v in out.items()}
+        out["homo"] = homo.value
+        return out
 
     def exchange_ms(self):
         """HIP-event time of the last step's exchange stage, ms"""

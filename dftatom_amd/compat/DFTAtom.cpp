@@ -19,11 +19,12 @@ int DFTAtom::charge = 0;
 std::string DFTAtom::config;
 int DFTAtom::poissonMode = -1;      // as dfta_poisson_create: exact unless $DFTA_DEBUG POISSON_MODE (--poisson= overrides)
 int DFTAtom::mixing = DFTA_MIX_LINEAR;     // --mixing=anderson: Anderson density mixing, default history and warm-up
-int DFTAtom::exchange = DFTA_EXCHANGE_FUNCTIONAL;   // --exchange=kli: dfta_scf_set_exchange right after creation
+int DFTAtom::exchange = DFTA_EXCHANGE_FUNCTIONAL;   // --exchange=kli / sic: dfta_scf_set_exchange right after creation
 std::ostream* DFTAtom::jsonOut = nullptr;
 bool DFTAtom::orbitalTable = false;        // --orbital-table
 bool DFTAtom::slaterTable = false;         // --slater-table
 bool DFTAtom::exchangeTable = false;       // --exchange-table
+bool DFTAtom::sicTable = false;            // --sic-table
 bool DFTAtom::formFactorTable = false;     // --form-factor-table[=smax:ns]
 double DFTAtom::formFactorSmax = 2.0;
 int DFTAtom::formFactorPoints = 41;
@@ -173,6 +174,27 @@ void print_exchange_table(dfta_scf* scf, const dfta_grid* grid, bool lsda)
     std::cout << std::endl << std::endl;
 }
 
+// --sic-table (with --exchange=sic): per channel one line per shell with its eigenvalue, the self-Hartree and self-xc energies EH_a and EXC_a
+// of one electron in the shell, <a|v_a^SIC|a> and the KLI constant c_a (dfta_scf_sic_table), then E_SIC (dfta_scf_get_exchange)
+void print_sic_table(dfta_scf* scf, bool lsda)
+{
+    for (int spin = 0; spin < (lsda ? 2 : 1); ++spin) {
+        const std::vector<LevelLine> lv = fetch_levels(scf, spin);
+        const size_t n = lv.size();
+        if (n == 0) continue;
+        std::vector<double> EH(n), EXC(n), vbar(n), c(n);
+        if (dfta_scf_sic_table(scf, 0, spin, EH.data(), EXC.data(), vbar.data(), c.data(), nullptr) != DFTA_OK)
+            throw std::runtime_error("dfta_scf_sic_table");
+        for (size_t a = 0; a < n; ++a)
+            std::cout << "SIC " << (lsda ? (spin == 0 ? "alpha " : "beta ") : "") << lv[a].n + 1 << DFTAtom::orb[lv[a].l] << ": E = " << std::fixed
+                      << std::setprecision(6) << lv[a].E << " EH = " << EH[a] << " EXC = " << EXC[a] << " vbar = " << vbar[a] << " c = " << c[a]
+                      << std::endl;
+    }
+    double esic = 0;
+    if (dfta_scf_get_exchange(scf, 0, 0, nullptr, nullptr, &esic) != DFTA_OK) throw std::runtime_error("dfta_scf_get_exchange");
+    std::cout << "ESIC = " << std::fixed << std::setprecision(6) << esic << std::endl << std::endl;
+}
+
 // --form-factor-table: f(q) of the converged density at s_k = smax k / (ns - 1), q = ((4 pi) s) 0.529177210903 (s in 1 / Angstrom, q in
 // atomic units), every q in one launch (dfta_scf_form_factors); LSDA: the magnetic form factor f_a - f_b beside it
 void print_form_factor_table(dfta_scf* scf, bool lsda)
@@ -253,6 +275,7 @@ void DFTAtom::Run(bool lsda, bool uniform, int Z, int MultigridLevels, double al
             if (orbitalTable) print_orbital_table(scf, lsda);
             if (slaterTable) print_slater_table(scf, lsda);
             if (exchangeTable) print_exchange_table(scf, grid, lsda);
+            if (sicTable && exchange == DFTA_EXCHANGE_SIC_KLI) print_sic_table(scf, lsda);
             if (formFactorTable) print_form_factor_table(scf, lsda);
             break;
         }

@@ -34,6 +34,7 @@ public:
     static int poissonMode;     // -1 (default): as dfta_poisson_create, i.e. exact unless $DFTA_DEBUG POISSON_MODE says otherwise; DFTA_POISSON_EXACT / _TOLERANCE / _ADAPTIVE
     static int mixing;          // DFTA_MIX_LINEAR (default: the reference's mixing, DFTAtom.cpp:332-342) / DFTA_MIX_ANDERSON (about half the SCF steps)
     static int exchange;        // DFTA_EXCHANGE_FUNCTIONAL (default) / DFTA_EXCHANGE_KLI: self-consistent exchange-only KLI (functional VWN, linear mixing)
+                                // / DFTA_EXCHANGE_SIC_KLI: VWN plus the Perdew-Zunger self-interaction correction through KLI (the same two)
     static int functional;      // DFTA_XC_VWN (default: what the reference runs), _CHACHIYO, _CHACHIYO_IMPROVED (LDA only), _PW92, _PBE (logarithmic grid)
     // electron configuration (not in the reference, which runs the neutral Aufbau atom): charge q > 0 runs the cation of dfta_ion_config,
     // a non-empty config the text of dfta_config_parse ("[Ne] 3s2 3p5.5", "2p3/1" LSDA splits); both unset (default): the Aufbau atom
@@ -52,6 +53,9 @@ public:
     // after "Finished!" (and the Slater table), one line per shell and channel with its eigenvalue and the orbital averages of the Fock,
     // Slater and KLI exchange potentials, then E_x and r vKLI at the outermost node of the density (dfta_scf_exchange_potentials)
     static bool exchangeTable;
+    // under DFTA_EXCHANGE_SIC_KLI, after "Finished!": one line per shell with its eigenvalue, EH_a, EXC_a, <a|v_a^SIC|a> and c_a, then E_SIC
+    // (dfta_scf_sic_table)
+    static bool sicTable;
     // after "Finished!" (and the other tables), the X-ray form factor of the converged density on formFactorPoints values of
     // s = sin(theta) / lambda from 0 to formFactorSmax (1 / Angstrom), one line each; LSDA adds f_a - f_b (dfta_scf_form_factors)
     static bool formFactorTable;

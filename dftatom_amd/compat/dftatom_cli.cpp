@@ -29,6 +29,10 @@
 // --mixing=linear (default, the reference's density mixing) | anderson (Anderson acceleration: about half the SCF steps, same protocol).
 // --exchange=functional (default) | kli: self-consistent exchange-only KLI -- every step's exchange potential from its own orbitals, no
 //                correlation (with --xc=vwn and --mixing=linear only); same protocol, --exchange-table works on top of it.
+// --exchange=sic: self-interaction-corrected LSDA -- VWN plus the Perdew-Zunger correction as one KLI potential per spin channel (-1/r tail,
+//                HOMO near -IP; --xc=vwn and --mixing=linear only); same protocol.
+// --sic-table:   with --exchange=sic, after "Finished!" one line per shell (per spin channel with LSDA) with its eigenvalue, the self-Hartree
+//                and self-xc energies EH, EXC of one electron in it, <a|v_a^SIC|a> and the KLI constant c, then E_SIC.  Changes nothing else.
 // --xc=vwn (default, what the reference runs) | chachiyo | chachiyo-improved (LDA only) | pw92 | pbe (logarithmic grid only).
 // --charge=q: the cation X^q+ (electrons leave the subshell of highest n, then highest l: Fe+ = [Ar] 3d6 4s1);
 // --config="[Ne] 3s2 3p5.5": an explicit, possibly fractional configuration ("2p3/1": LSDA alpha / beta split).  An invalid
@@ -127,8 +131,12 @@ int main(int argc, char** argv)
             DFT::DFTAtom::poissonMode = a == "--poisson=tolerance" ? DFTA_POISSON_TOLERANCE : (a == "--poisson=adaptive" ? DFTA_POISSON_ADAPTIVE : DFTA_POISSON_EXACT);
         } else if (a == "--mixing=linear" || a == "--mixing=anderson") {
             DFT::DFTAtom::mixing = a == "--mixing=anderson" ? DFTA_MIX_ANDERSON : DFTA_MIX_LINEAR;
+        } else if (a == "--sic-table") {
+            DFT::DFTAtom::sicTable = true;
         } else if (a == "--exchange=kli" || a == "--exchange=functional") {
             DFT::DFTAtom::exchange = a == "--exchange=kli" ? DFTA_EXCHANGE_KLI : DFTA_EXCHANGE_FUNCTIONAL;
+        } else if (a == "--exchange=sic") {
+            DFT::DFTAtom::exchange = DFTA_EXCHANGE_SIC_KLI;
         } else if (a.rfind("--exchange=", 0) == 0) {
             std::cerr << "unknown exchange " << a.substr(11) << std::endl;
             bad = true;
@@ -176,6 +184,8 @@ int main(int argc, char** argv)
                   << "       --xc=vwn (default) | chachiyo | chachiyo-improved | pw92 | pbe\n"
                   << "       --mixing=linear (default) | anderson: Anderson density mixing, fewer SCF steps\n"
                   << "       --exchange=functional (default) | kli: self-consistent exchange-only KLI (no correlation; --xc=vwn, --mixing=linear)\n"
+                  << "                  | sic: VWN plus the Perdew-Zunger self-interaction correction through KLI (--xc=vwn, --mixing=linear)\n"
+                  << "       --sic-table: with --exchange=sic, after Finished!, per shell its eigenvalue, EH, EXC, <v_SIC> and the KLI constant, then E_SIC\n"
                   << "       --orbital-table: after Finished!, one line per level with <r>, <r^2>, T and r_peak of its orbital\n"
                   << "       --slater-table: after Finished!, the Slater integrals F^k, G^k of the levels, then E_H and the exact-exchange energy\n"
                   << "       --exchange-table: after Finished!, per shell its eigenvalue, the orbital averages of the Fock, Slater and KLI exchange potentials and the KLI constant, then E_x and r vKLI at the density's outermost node\n"

@@ -62,6 +62,39 @@ int plan_channels(int nch, const int* norb, const int* l, const double* occ, con
     return 0;
 }
 
+int plan_channels_sic(int nch, const int* norb, const int* l, const double* occ, const int* atom, Plan* plan)
+{
+    if (check_channels(nch, norb, l, occ)) return -1;
+    *plan = Plan();
+    int u0 = 0;
+    auto put = [&](int kind, int a, int b, int c) {
+        const int e[kRedInts] = {kind, a, b, c};
+        plan->red.insert(plan->red.end(), e, e + kRedInts);
+    };
+    for (int c = 0; c < nch; ++c) {
+        Channel ch = {};
+        const int n = norb[c];
+        ch.u0 = u0; ch.norb = n;
+        ch.job0 = plan->njobs(); ch.red0 = plan->nred();
+        ch.atom = atom ? atom[c] : -1;
+        for (int a = 0; a < n; ++a) {
+            const int e[kJobInts] = {u0 + a, u0 + a, 0};
+            plan->jobs.insert(plan->jobs.end(), e, e + kJobInts);
+        }
+        for (int a = 0; a < n; ++a) put(dfta_exchange::kRedHF, a, a, c);
+        for (int a = 0; a < n; ++a) put(dfta_exchange::kRedS, a, a, c);
+        for (int a = 0; a < n; ++a)
+            for (int b = a; b < n; ++b) put(dfta_exchange::kRedPair, a, b, c);
+        for (int a = 0; a < n; ++a) put(kRedSicH, a, a, c);
+        for (int a = 0; a < n; ++a) put(kRedSicXC, a, a, c);
+        ch.njobs = n; ch.nred = plan->nred() - ch.red0;
+        plan->ch.push_back(ch);
+        u0 += n;
+    }
+    plan->norb_total = u0;
+    return 0;
+}
+
 long budget_rows(double mb, int N)
 {
     if (!(mb > 0.) || N <= 0) return 0;

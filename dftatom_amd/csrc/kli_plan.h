@@ -41,6 +41,13 @@ const char* check_channels(int nch, const int* norb, const int* l, const double*
 // the tables of the batch; atom may be null (-1 everywhere).  0, or -1: check_channels fails
 int plan_channels(int nch, const int* norb, const int* l, const double* occ, const int* atom, Plan* plan);
 
+// The tables of the self-interaction-corrected stage (SIC-KLI): per channel the y jobs are the diagonals (a, a, 0) alone, a ascending --
+// y row a of a channel is the Hartree potential of one electron in shell a --, there are no pointwise entries (first0 = tab0 = ntab = 0;
+// first, tab, coef stay empty), and the reductions are those of plan_channels (vbar_a, vbarS_a, S_ab: the solve reads the same layout)
+// followed by EH_a (kRedSicH, a ascending) and EXC_a (kRedSicXC).  Same refusals as plan_channels.
+enum { kRedSicH = 4, kRedSicXC = 5 };               // kinds of the reduction table beyond dfta_exchange's
+int plan_channels_sic(int nch, const int* norb, const int* l, const double* occ, const int* atom, Plan* plan);
+
 // y rows of N doubles that fit `mb` MiB, at least 0
 long budget_rows(double mb, int N);
 

@@ -11,6 +11,13 @@
 //                       node with D > 0 and v_raw r there.
 //   k_kli_update        grid (node tile, channel): the KLI pass, the Coulomb tail beyond the last node with D > 0, the mix into vx.
 //   k_kli_assemble      grid (node tile, atom), once per step: Vexc / va / vb / eexc from vx and the mixed densities; E_x of the atom.
+// Under DFTA_EXCHANGE_SIC_KLI (dfta_kli_stage::sic) the builder of X_a differs and the rest is shared:
+//   y launch            the diagonal jobs (a, a, 0) alone: one row per shell.
+//   k_sic_pointwise     grid (node tile, channel): rho_a, v_a and eps_a (vwn_device.h: k_vwn_lsda's own arithmetic at (rho_a, 0)),
+//                       X_a = (y0_a + v_a) u_a, D, vS.
+//   k_sic_reduce        k_kli_reduce plus the two quadratures EH_a and EXC_a, the same lane chains and trees.
+//   k_kli_solve, then k_sic_energy (one thread per channel: E_SIC of the channel in place of E_x, the per-shell table), k_kli_update.
+//   k_sic_assemble      once per step AFTER the functional's launch: adds vx to Vexc / va / vb, takes it from eexc; E_SIC of the atom.
 // Every shape is a function of N alone; no floating-point atomics; no workgroup waits for another: a channel's bits do not depend on the
 // batch, its position in it, the chunking or the run.  Built, as everything here, without FMA contraction: the solve repeats the host
 // solve of exchange_plan.cpp operation by operation.
@@ -24,6 +31,8 @@
 #include "exchange_device.h"
 #include "internal.h"
 #include "kli_stage.h"
+#include "vwn_device.h"
+#include "xc.h"
 
 namespace {
 
@@ -208,26 +217,130 @@ __global__ __launch_bounds__(kPwThreads) void k_kli_assemble(int N, int lsda, co
     eexc[o] = -v;
 }
 
+// ---- the self-interaction correction: the builder of X_a, the two energy quadratures, E_SIC and the additive assembly --------------------
+// rho_a, v_a, eps_a, X_a, D, vS of the chunk's channels [c0, c0 + gridDim.y); chunk rows: Y from job j0; vorb, eps, X from orbital row u0
+__global__ __launch_bounds__(kPwThreads) void k_sic_pointwise(int N, int c0, int j0, int u0, const Channel* __restrict__ chs,
+                                                              const double* __restrict__ U, const double* __restrict__ occ,
+                                                              const double* __restrict__ r, const double* __restrict__ Y, double cx,
+                                                              double cbrt2, double* __restrict__ vorb, double* __restrict__ eps,
+                                                              double* __restrict__ X, double* __restrict__ D, double* __restrict__ vS)
+{
+    const Channel ch = chs[c0 + blockIdx.y];
+    const int i = blockIdx.x * kPwThreads + threadIdx.x;
+    if (ch.norb == 0 || i >= N) return;
+    const dfta_vwn_dev::LsdaConsts k = dfta_vwn_dev::lsda_consts(cx, cbrt2);
+    const double* Uc = U + (size_t)ch.u0 * N;
+    const double* Yc = Y + (size_t)(ch.job0 - j0) * N;
+    const size_t row0 = (size_t)(ch.u0 - u0) * N;
+    const double ri = r[i];
+    const double fpr2 = (dfta_vwn_dev::kFourPi * ri) * ri;
+    double den = 0., num = 0.;
+    for (int a = 0; a < ch.norb; ++a) {
+        const double ua = Uc[(size_t)a * N + i];
+        const double rho = i >= 1 ? (ua * ua) / fpr2 : 0.;
+        const dfta_vwn_dev::LsdaPoint p = dfta_vwn_dev::lsda_point(k, rho, 0.);
+        const double x = (Yc[(size_t)a * N + i] + p.vup) * ua;
+        const size_t o = row0 + (size_t)a * N + i;
+        vorb[o] = p.vup;
+        eps[o] = p.common + p.e;
+        X[o] = x;
+        den += occ[ch.u0 + a] * (ua * ua);
+        num += occ[ch.u0 + a] * (ua * x);
+    }
+    D[(size_t)blockIdx.y * N + i] = den;
+    vS[(size_t)blockIdx.y * N + i] = den > 0. ? -(num / den) : 0.;
+}
+
+// quadrature q0 + blockIdx.x of the batch's table: the kinds of k_kli_reduce, and EH_a / EXC_a as the kRedS chain on y0_a / eps_a
+__global__ __launch_bounds__(kRedThreads) void k_sic_reduce(int N, double hstep, int q0, int c0, int j0, int u0, const Channel* __restrict__ chs,
+                                                            const int* __restrict__ red, const double* __restrict__ cnst,
+                                                            const double* __restrict__ U, const double* __restrict__ X,
+                                                            const double* __restrict__ D, const double* __restrict__ vS,
+                                                            const double* __restrict__ Y, const double* __restrict__ eps,
+                                                            double* __restrict__ out)
+{
+    __shared__ double part[kRedThreads / 64];
+    const int* row = red + (size_t)dfta_kli::kRedInts * (q0 + blockIdx.x);
+    const int kind = row[0], a = row[1], b = row[2], c = row[3];
+    const Channel ch = chs[c];
+    const double* Uc = U + (size_t)ch.u0 * N;
+    const double* v = vS + (size_t)(c - c0) * N;
+    int shape = kind;
+    if (kind == dfta_kli::kRedSicH) { v = Y + (size_t)(ch.job0 - j0 + a) * N; shape = dfta_exchange::kRedS; }
+    else if (kind == dfta_kli::kRedSicXC) { v = eps + (size_t)(ch.u0 - u0 + a) * N; shape = dfta_exchange::kRedS; }
+    double q = dfta_exchange_dev::reduce_block(N, hstep, cnst, Uc + (size_t)a * N, Uc + (size_t)b * N, X + (size_t)(ch.u0 - u0 + a) * N,
+                                               D + (size_t)(c - c0) * N, v, shape, part);
+    if (kind == dfta_kli::kRedSicH) q = 0.5 * q;
+    if (threadIdx.x == 0) out[q0 + blockIdx.x] = q;
+}
+
+// E_SIC of the channels [c0, c0 + nc) in place of the E_x k_kli_solve wrote, and their per-shell table; one thread per channel
+__global__ void k_sic_energy(int c0, int nc, const Channel* __restrict__ chs, const double* __restrict__ occ, const double* __restrict__ redout,
+                             double* __restrict__ EH, double* __restrict__ EXC, double* __restrict__ ExCh)
+{
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= nc) return;
+    const Channel ch = chs[c0 + k];
+    const int n = ch.norb;
+    if (n == 0) return;
+    const double* eh = redout + ch.red0 + 2 * n + n * (n + 1) / 2;
+    const double* exc = eh + n;
+    double acc = 0.;
+    for (int a = 0; a < n; ++a) {
+        acc += occ[ch.u0 + a] * (eh[a] + exc[a]);
+        EH[ch.u0 + a] = eh[a];
+        EXC[ch.u0 + a] = exc[a];
+    }
+    ExCh[c0 + k] = -acc;
+}
+
+__global__ __launch_bounds__(kPwThreads) void k_sic_assemble(int N, int lsda, const int* __restrict__ fin, const double* __restrict__ vx,
+                                                             const double* __restrict__ ExCh, const double* __restrict__ density,
+                                                             const double* __restrict__ dA, const double* __restrict__ dB,
+                                                             double* __restrict__ Vexc, double* __restrict__ va, double* __restrict__ vb,
+                                                             double* __restrict__ eexc, double* __restrict__ ExAtom)
+{
+    const int a = blockIdx.y;
+    if (fin[a]) return;                      // a finished atom keeps its potential and its E_SIC
+    const int i = blockIdx.x * kPwThreads + threadIdx.x;
+    if (i == 0) ExAtom[a] = lsda ? ExCh[2 * a] + ExCh[2 * a + 1] : 2. * ExCh[a];
+    if (i >= N) return;
+    const size_t o = (size_t)a * N + i;
+    double t;
+    if (!lsda) t = vx[o];
+    else {
+        const double x = vx[((size_t)2 * a) * N + i], y = vx[((size_t)2 * a + 1) * N + i];
+        const double rho = density[o];
+        va[o] = va[o] + x;
+        vb[o] = vb[o] + y;
+        t = rho > 0. ? (dA[o] * x + dB[o] * y) / rho : 0.;
+    }
+    Vexc[o] = Vexc[o] + t;
+    eexc[o] = eexc[o] - t;
+}
+
 }  // namespace
 
 void dfta_kli_stage::reset()
 {
     plan = dfta_kli::Plan();
-    max_rows = 0; caps = {0, 0, 0}; N = 0; natoms = 0; timed = false;
+    max_rows = 0; caps = {0, 0, 0}; N = 0; natoms = 0; timed = false; sic = false;
     d_ch.reset();
     for (DevBuf<int>* b : {&d_jobs, &d_first, &d_tab, &d_red, &d_homo, &d_ilast, &d_status}) b->reset();
-    for (DevBuf<double>* b : {&d_coef, &d_occ, &d_y, &d_X, &d_DvS, &d_redout, &d_vx, &d_vraw, &d_vbarHF, &d_c, &d_tail, &d_ExCh, &d_ExAtom}) b->reset();
+    for (DevBuf<double>* b : {&d_coef, &d_occ, &d_y, &d_X, &d_DvS, &d_redout, &d_vx, &d_vraw, &d_vbarHF, &d_c, &d_tail, &d_ExCh, &d_ExAtom, &d_vorb, &d_eps, &d_EH,
+                          &d_EXC}) b->reset();
     h_status.clear(); bounds.clear();
 }
 
 int dfta_kli_stage::create(dfta_ctx* ctx, const dfta_grid* g, int nch, const int* norb, const int* l, const double* occ, const int* atom,
-                           int natoms_, double y_mb)
+                           int natoms_, double y_mb, bool sic_)
 {
     reset();
     if (const char* msg = dfta_kli::check_channels(nch, norb, l, occ)) DFTA_REQUIRE(ctx, false, msg);
     DFTA_REQUIRE(ctx, g->N >= 5, "KLI channels: the grid needs 5 nodes");
     DFTA_REQUIRE(ctx, nch >= 1 && nch <= 65535, "KLI channels: 1 .. 65535 channels");
-    DFTA_REQUIRE(ctx, dfta_kli::plan_channels(nch, norb, l, occ, atom, &plan) == 0, "KLI channels: the tables");
+    DFTA_REQUIRE(ctx, (sic_ ? dfta_kli::plan_channels_sic(nch, norb, l, occ, atom, &plan) : dfta_kli::plan_channels(nch, norb, l, occ, atom, &plan)) == 0,
+                 "KLI channels: the tables");
     hipStream_t st = ctx->stream;
     const size_t n = g->N, no = std::max(plan.norb_total, 1);
     max_rows = dfta_kli::budget_rows(y_mb, g->N);
@@ -239,6 +352,7 @@ int dfta_kli_stage::create(dfta_ctx* ctx, const dfta_grid* g, int nch, const int
     al(d_y, (size_t)caps.yrows * n); al(d_X, (size_t)caps.xrows * n); al(d_DvS, 2 * (size_t)caps.chans * n); al(d_redout, plan.nred());
     al(d_vx, (size_t)nch * n); al(d_vraw, (size_t)nch * n); al(d_vbarHF, no); al(d_c, no); al(d_tail, nch); al(d_ExCh, nch);
     al(d_ExAtom, natoms_); al(d_homo, nch); al(d_ilast, nch); al(d_status, nch);
+    if (sic_) { al(d_vorb, (size_t)caps.xrows * n); al(d_eps, (size_t)caps.xrows * n); al(d_EH, no); al(d_EXC, no); }
     for (auto& v : ev) if (e == hipSuccess && !v.e) e = hipEventCreate(&v.e);
     if (e != hipSuccess) {
         snprintf(ctx->err, sizeof(ctx->err), "KLI stage alloc: %s", hipGetErrorString(e));
@@ -254,19 +368,20 @@ int dfta_kli_stage::create(dfta_ctx* ctx, const dfta_grid* g, int nch, const int
     auto zero = [&](auto& buf, int byte) { if (e == hipSuccess) e = hipMemsetAsync(buf.p, byte, sizeof(*buf.p) * buf.n, st); };
     zero(d_vx, 0); zero(d_vraw, 0); zero(d_vbarHF, 0); zero(d_c, 0); zero(d_tail, 0); zero(d_ExCh, 0); zero(d_ExAtom, 0); zero(d_status, 0);
     zero(d_homo, 0xff); zero(d_ilast, 0xff);
+    if (sic_) { zero(d_EH, 0); zero(d_EXC, 0); }
     if (e == hipSuccess) e = hipStreamSynchronize(st);                   // occ is the caller's; the plan's vectors stay
     if (e != hipSuccess) {
         snprintf(ctx->err, sizeof(ctx->err), "KLI stage tables: %s", hipGetErrorString(e));
         reset();
         return DFTA_ERR_HIP;
     }
-    N = g->N; natoms = natoms_;
+    N = g->N; natoms = natoms_; sic = sic_;
     h_status.assign(nch, 0);
     return DFTA_OK;
 }
 
 int dfta_kli_stage::run(dfta_ctx* ctx, const dfta_grid* g, const double* dU, const void* Ebase, size_t Estride, const unsigned char* live,
-                        bool first, double alpha, double oneMinusAlpha)
+                        bool first, double alpha, double oneMinusAlpha, const Dump* dump)
 {
     hipStream_t st = ctx->stream;
     const double hstep = g->uniform ? g->h : 1.0;
@@ -283,18 +398,42 @@ int dfta_kli_stage::run(dfta_ctx* ctx, const dfta_grid* g, const double* dU, con
         DFTA_REQUIRE(ctx, njobs <= caps.yrows && norb <= caps.xrows && nc <= caps.chans, "KLI stage: a chunk beyond its buffers");
         int rc = dfta_launch_screening_yk(ctx, g, dU, njobs, d_jobs.p + (size_t)dfta_kli::kJobInts * a.job0, d_y.p);
         if (rc) return rc;
-        hipLaunchKernelGGL(k_kli_pointwise, dim3(nblk, nc), dim3(kPwThreads), 0, st, N, c0, a.job0, a.u0, d_ch.p, dU, d_occ.p, d_first.p, d_tab.p,
-                           d_coef.p, d_y.p, d_X.p, dD, dvS);
-        DFTA_CHECK_LAUNCH(ctx);
-        hipLaunchKernelGGL(k_kli_reduce, dim3(nred), dim3(kRedThreads), 0, st, N, hstep, a.red0, c0, a.u0, d_ch.p, d_red.p, g->d_cnst.p, dU, d_X.p, dD,
-                           dvS, d_redout.p);
-        DFTA_CHECK_LAUNCH(ctx);
+        if (!sic) {
+            hipLaunchKernelGGL(k_kli_pointwise, dim3(nblk, nc), dim3(kPwThreads), 0, st, N, c0, a.job0, a.u0, d_ch.p, dU, d_occ.p, d_first.p, d_tab.p,
+                               d_coef.p, d_y.p, d_X.p, dD, dvS);
+            DFTA_CHECK_LAUNCH(ctx);
+            hipLaunchKernelGGL(k_kli_reduce, dim3(nred), dim3(kRedThreads), 0, st, N, hstep, a.red0, c0, a.u0, d_ch.p, d_red.p, g->d_cnst.p, dU, d_X.p,
+                               dD, dvS, d_redout.p);
+            DFTA_CHECK_LAUNCH(ctx);
+        } else {
+            hipLaunchKernelGGL(k_sic_pointwise, dim3(nblk, nc), dim3(kPwThreads), 0, st, N, c0, a.job0, a.u0, d_ch.p, dU, d_occ.p, g->d_r.p, d_y.p,
+                               dfta_vwn_cx(), dfta_vwn_cbrt2(), d_vorb.p, d_eps.p, d_X.p, dD, dvS);
+            DFTA_CHECK_LAUNCH(ctx);
+            hipLaunchKernelGGL(k_sic_reduce, dim3(nred), dim3(kRedThreads), 0, st, N, hstep, a.red0, c0, a.job0, a.u0, d_ch.p, d_red.p, g->d_cnst.p,
+                               dU, d_X.p, dD, dvS, d_y.p, d_eps.p, d_redout.p);
+            DFTA_CHECK_LAUNCH(ctx);
+        }
         hipLaunchKernelGGL(k_kli_solve, dim3(nc), dim3(kSolveThreads), 0, st, N, c0, d_ch.p, d_occ.p, static_cast<const char*>(Ebase), Estride,
                            d_redout.p, g->d_r.p, dU, dD, dvS, d_c.p, d_vbarHF.p, d_homo.p, d_ExCh.p, d_ilast.p, d_tail.p, d_status.p);
         DFTA_CHECK_LAUNCH(ctx);
+        if (sic) {
+            hipLaunchKernelGGL(k_sic_energy, dim3((nc + 63) / 64), dim3(64), 0, st, c0, nc, d_ch.p, d_occ.p, d_redout.p, d_EH.p, d_EXC.p, d_ExCh.p);
+            DFTA_CHECK_LAUNCH(ctx);
+        }
         hipLaunchKernelGGL(k_kli_update, dim3(nblk, nc), dim3(kPwThreads), 0, st, N, c0, d_ch.p, d_occ.p, dU, d_c.p, d_homo.p, dD, dvS, d_ilast.p,
                            d_tail.p, g->d_r.p, first ? 1 : 0, alpha, oneMinusAlpha, d_vx.p, d_vraw.p);
         DFTA_CHECK_LAUNCH(ctx);
+        if (dump) {                              // the chunk's rows into the caller's whole-batch arrays (device to device, on the stream)
+            auto keep = [&](double* dst, size_t row, const double* src, size_t rows) {
+                return dst && rows ? hipMemcpyAsync(dst + row * N, src, sizeof(double) * rows * N, hipMemcpyDeviceToDevice, st) : hipSuccess;
+            };
+            DFTA_HIP(ctx, keep(dump->y, a.job0, d_y.p, njobs));
+            DFTA_HIP(ctx, keep(dump->X, a.u0, d_X.p, norb));
+            DFTA_HIP(ctx, keep(dump->vorb, a.u0, d_vorb.p, sic ? norb : 0));
+            DFTA_HIP(ctx, keep(dump->eps, a.u0, d_eps.p, sic ? norb : 0));
+            DFTA_HIP(ctx, keep(dump->D, c0, dD, nc));
+            DFTA_HIP(ctx, keep(dump->vS, c0, dvS, nc));
+        }
     }
     DFTA_HIP(ctx, hipEventRecord(ev[1], st));
     timed = true;
@@ -306,6 +445,15 @@ int dfta_kli_stage::assemble(dfta_ctx* ctx, const dfta_grid* g, int lsda, const 
                              const int* fin, double* Vexc, double* va, double* vb, double* eexc)
 {
     hipLaunchKernelGGL(k_kli_assemble, dim3((N + kPwThreads - 1) / kPwThreads, natoms), dim3(kPwThreads), 0, ctx->stream, N, lsda, fin, d_vx.p,
+                       d_ExCh.p, density, dA, dB, Vexc, va, vb, eexc, d_ExAtom.p);
+    DFTA_CHECK_LAUNCH(ctx);
+    return DFTA_OK;
+}
+
+int dfta_kli_stage::assemble_sic(dfta_ctx* ctx, const dfta_grid* g, int lsda, const double* density, const double* dA, const double* dB,
+                                 const int* fin, double* Vexc, double* va, double* vb, double* eexc)
+{
+    hipLaunchKernelGGL(k_sic_assemble, dim3((N + kPwThreads - 1) / kPwThreads, natoms), dim3(kPwThreads), 0, ctx->stream, N, lsda, fin, d_vx.p,
                        d_ExCh.p, density, dA, dB, Vexc, va, vb, eexc, d_ExAtom.p);
     DFTA_CHECK_LAUNCH(ctx);
     return DFTA_OK;
@@ -359,6 +507,82 @@ int dfta_kli_channels(dfta_ctx* ctx, const dfta_grid* g, int nch, const int* nor
     if (homo) DFTA_HIP(ctx, hipMemcpyAsync(homo, stage.d_homo.p, sizeof(int) * nch, hipMemcpyDeviceToHost, st));
     if (Ex) DFTA_HIP(ctx, hipMemcpyAsync(Ex, stage.d_ExCh.p, sizeof(double) * nch, hipMemcpyDeviceToHost, st));
     DFTA_HIP(ctx, hipStreamSynchronize(st));
+    return DFTA_OK;
+}
+
+int dfta_sic_channels(dfta_ctx* ctx, const dfta_grid* g, int nch, const int* norb, const int* l, const double* occ, const double* E,
+                      const double* u, int first_step, double alpha, double* vx_inout, double* y0, double* vorb, double* eps, double* X,
+                      double* D, double* vS, double* v_raw, double* vbar, double* c, double* EH, double* EXC, int* homo, double* Esic,
+                      double* vbarS, double* M)
+{
+    if (!ctx || !g) return DFTA_ERR_INVALID;
+    DFTA_ENTER(ctx);
+    DFTA_REQUIRE(ctx, nch >= 0, "dfta_sic_channels: nch");
+    if (nch == 0) return DFTA_OK;
+    DFTA_REQUIRE(ctx, norb, "dfta_sic_channels: norb");
+    DFTA_REQUIRE(ctx, alpha >= 0 && alpha <= 1, "dfta_sic_channels: alpha");
+    long total = 0;
+    for (int k = 0; k < nch; ++k) total += norb[k] > 0 ? norb[k] : 0;
+    DFTA_REQUIRE(ctx, total == 0 || (l && occ && E && u), "dfta_sic_channels: l / occ / E / u");
+    DFTA_REQUIRE(ctx, first_step || vx_inout, "dfta_sic_channels: a later step mixes into vx_inout");
+    dfta_kli_stage stage;
+    int rc = stage.create(ctx, g, nch, norb, l, occ, nullptr, 0, dfta_kli_budget_mb(), true);
+    if (rc) return rc;
+    hipStream_t st = ctx->stream;
+    const size_t N = g->N, no = stage.plan.norb_total;
+    DevBuf<double> dU, dE, dRows[4], dChan[2];       // rows: y0, vorb, eps, X of every shell; D, vS of every channel
+    DFTA_HIP(ctx, dU.alloc(std::max<size_t>(no * N, 1)));
+    DFTA_HIP(ctx, dE.alloc(std::max<size_t>(no, 1)));
+    double* hostRows[4] = {y0, vorb, eps, X};
+    double* hostChan[2] = {D, vS};
+    for (int k = 0; k < 4; ++k)
+        if (hostRows[k] && no) DFTA_HIP(ctx, dRows[k].alloc(no * N));
+    for (int k = 0; k < 2; ++k)
+        if (hostChan[k]) {
+            DFTA_HIP(ctx, dChan[k].alloc((size_t)nch * N));
+            DFTA_HIP(ctx, hipMemsetAsync(dChan[k].p, 0, sizeof(double) * nch * N, st));      // a channel without shells: zeros
+        }
+    if (no) {
+        DFTA_HIP(ctx, hipMemcpyAsync(dU.p, u, sizeof(double) * no * N, hipMemcpyHostToDevice, st));
+        DFTA_HIP(ctx, hipMemcpyAsync(dE.p, E, sizeof(double) * no, hipMemcpyHostToDevice, st));
+    }
+    if (!first_step) DFTA_HIP(ctx, hipMemcpyAsync(stage.d_vx.p, vx_inout, sizeof(double) * nch * N, hipMemcpyHostToDevice, st));
+    dfta_kli_stage::Dump dump = {dRows[0].p, dRows[1].p, dRows[2].p, dRows[3].p, dChan[0].p, dChan[1].p};
+    DFTA_HIP(ctx, hipEventRecord(ctx->ev[0], st));     // dfta_ctx_last_kernel_ms: the whole stage
+    rc = stage.run(ctx, g, dU.p, dE.p, sizeof(double), nullptr, first_step != 0, alpha, 1. - alpha, &dump);
+    if (rc) return rc;
+    DFTA_HIP(ctx, hipEventRecord(ctx->ev[1], st));
+    ctx->have_kernel_time = true;
+    for (int k = 0; k < 4; ++k)
+        if (dRows[k].p) DFTA_HIP(ctx, hipMemcpyAsync(hostRows[k], dRows[k].p, sizeof(double) * no * N, hipMemcpyDeviceToHost, st));
+    for (int k = 0; k < 2; ++k)
+        if (dChan[k].p) DFTA_HIP(ctx, hipMemcpyAsync(hostChan[k], dChan[k].p, sizeof(double) * nch * N, hipMemcpyDeviceToHost, st));
+    if (vx_inout) DFTA_HIP(ctx, hipMemcpyAsync(vx_inout, stage.d_vx.p, sizeof(double) * nch * N, hipMemcpyDeviceToHost, st));
+    if (v_raw) DFTA_HIP(ctx, hipMemcpyAsync(v_raw, stage.d_vraw.p, sizeof(double) * nch * N, hipMemcpyDeviceToHost, st));
+    if (vbar && no) DFTA_HIP(ctx, hipMemcpyAsync(vbar, stage.d_vbarHF.p, sizeof(double) * no, hipMemcpyDeviceToHost, st));
+    if (c && no) DFTA_HIP(ctx, hipMemcpyAsync(c, stage.d_c.p, sizeof(double) * no, hipMemcpyDeviceToHost, st));
+    if (EH && no) DFTA_HIP(ctx, hipMemcpyAsync(EH, stage.d_EH.p, sizeof(double) * no, hipMemcpyDeviceToHost, st));
+    if (EXC && no) DFTA_HIP(ctx, hipMemcpyAsync(EXC, stage.d_EXC.p, sizeof(double) * no, hipMemcpyDeviceToHost, st));
+    if (homo) DFTA_HIP(ctx, hipMemcpyAsync(homo, stage.d_homo.p, sizeof(int) * nch, hipMemcpyDeviceToHost, st));
+    if (Esic) DFTA_HIP(ctx, hipMemcpyAsync(Esic, stage.d_ExCh.p, sizeof(double) * nch, hipMemcpyDeviceToHost, st));
+    std::vector<double> red((vbarS || M) ? stage.plan.nred() : 0);
+    if (!red.empty()) DFTA_HIP(ctx, hipMemcpyAsync(red.data(), stage.d_redout.p, sizeof(double) * red.size(), hipMemcpyDeviceToHost, st));
+    DFTA_HIP(ctx, hipStreamSynchronize(st));
+    if (!red.empty()) {
+        size_t m0 = 0;
+        for (const dfta_kli::Channel& ch : stage.plan.ch) {
+            const int n = ch.norb;
+            const double* S = red.data() + ch.red0 + 2 * n;     // pair (a <= b) at a n - a (a - 1) / 2 + (b - a)
+            for (int a = 0; a < n; ++a) {
+                if (vbarS) vbarS[ch.u0 + a] = red[ch.red0 + n + a];
+                for (int b = 0; M && b < n; ++b) {
+                    const int lo = a < b ? a : b, hi = a < b ? b : a;
+                    M[m0 + (size_t)a * n + b] = S[lo * n - lo * (lo - 1) / 2 + (hi - lo)] * occ[ch.u0 + b];
+                }
+            }
+            m0 += (size_t)n * n;
+        }
+    }
     return DFTA_OK;
 }
 

@@ -148,7 +148,8 @@ __global__ void k_tail(const AtomState* __restrict__ atoms, int lsda, int N, con
 }
 
 // energy assembly and the reference's stop test (DFTAtom.cpp:459-481 / 985-1006); one thread per atom
-// Ex: null, or per atom the exchange energy of an orbital-dependent exchange (DFTA_EXCHANGE_KLI), added to eExcDif
+// Ex: null, or per atom the exchange energy of an orbital-dependent exchange (DFTA_EXCHANGE_KLI) or E_SIC (DFTA_EXCHANGE_SIC_KLI), added
+// to eExcDif
 __global__ void k_energies(AtomState* __restrict__ atoms, int natoms, const dfta::Job* __restrict__ jobs,
                            const double* __restrict__ occ, const double* __restrict__ integrals, double* __restrict__ records, int* __restrict__ fin,
                            const double* __restrict__ Ex)
@@ -228,6 +229,22 @@ static int scf_kli(dfta_scf* s)
                         1. - s->alpha);
     if (rc) return rc;
     return s->kli.assemble(s->ctx, s->g, s->lsda, s->d_density.p, s->d_dA.p, s->d_dB.p, s->d_fin.p, s->d_Vexc.p, s->d_va.p, s->d_vb.p, s->d_eexc.p);
+}
+
+// DFTA_EXCHANGE_SIC_KLI, after scf_xc: the SIC stage on the step's orbitals for every live channel, then its potential on top of the
+// functional's Vexc / va / vb / eexc
+static int scf_sic(dfta_scf* s)
+{
+    const int nspin = s->nspin;
+    s->h_live_ch.resize((size_t)s->nV);
+    for (int a = 0; a < s->natoms; ++a)
+        for (int sp = 0; sp < nspin; ++sp) s->h_live_ch[(size_t)a * nspin + sp] = s->h_atoms[a].finished ? 0 : 1;
+    const dfta::Job* jobs = s->solver.d_jobs.p;
+    int rc = s->kli.run(s->ctx, s->g, s->solver.d_Psi.p, &jobs->E, sizeof(dfta::Job), s->h_live_ch.data(), s->steps_done == 1, s->alpha,
+                        1. - s->alpha);
+    if (rc) return rc;
+    return s->kli.assemble_sic(s->ctx, s->g, s->lsda, s->d_density.p, s->d_dA.p, s->d_dB.p, s->d_fin.p, s->d_Vexc.p, s->d_va.p, s->d_vb.p,
+                               s->d_eexc.p);
 }
 
 static int scf_xc(dfta_scf* s)
@@ -546,8 +563,13 @@ int dfta_scf_step(dfta_scf* s, dfta_step_stats* stats)
     }
     dfta_range r_tail("dfta: XC + integrands + ordered integrals + energies");
     const bool kli = s->exchange_mode == DFTA_EXCHANGE_KLI;
+    const bool sic = s->exchange_mode == DFTA_EXCHANGE_SIC_KLI;
     rc = kli ? scf_kli(s) : scf_xc(s);
     if (rc) return rc;
+    if (sic) {
+        rc = scf_sic(s);
+        if (rc) return rc;
+    }
     hipLaunchKernelGGL(k_tail, grid, block, 0, st, s->d_atoms.p, s->lsda, N, g->d_r, g->d_cnst, s->d_density.p, s->d_dA.p, s->d_dB.p, s->d_U.p,
                        s->d_Vexc.p, s->d_va.p, s->d_vb.p, s->d_eexc.p, s->d_V.p, s->d_integrands.p, g->uniform);
     DFTA_CHECK_LAUNCH(ctx);
@@ -560,13 +582,13 @@ int dfta_scf_step(dfta_scf* s, dfta_step_stats* stats)
         rc = dfta_launch_integrate_ordered(ctx, s->solver.integ_rule, g->uniform ? g->h : 1.0, s->d_integrands, N, natoms * 5, (size_t)N, s->d_integrals);
     if (rc) return rc;
     hipLaunchKernelGGL(k_energies, dim3((natoms + 63) / 64), dim3(64), 0, st, s->d_atoms.p, natoms, s->solver.d_jobs.p, s->solver.d_occ.p, s->d_integrals.p,
-                       s->d_records.p, s->d_fin.p, kli ? s->kli.d_ExAtom.p : nullptr);
+                       s->d_records.p, s->d_fin.p, kli || sic ? s->kli.d_ExAtom.p : nullptr);
     DFTA_CHECK_LAUNCH(ctx);
     DFTA_HIP(ctx, hipEventRecord(s->ev[3], st));
     // the step ends synchronised with the atoms' state on the host: the next step freezes what has finished
     DFTA_HIP(ctx, hipMemcpyAsync(s->h_atoms.data(), s->d_atoms, sizeof(AtomState) * natoms, hipMemcpyDeviceToHost, st));
     DFTA_HIP(ctx, hipStreamSynchronize(st));
-    if (kli)
+    if (kli || sic)
         for (int c = 0; c < s->nV; ++c)
             DFTA_REQUIRE(ctx, !(s->h_live_ch[c] && s->kli.h_status[c]), "exchange stage: the KLI system of a channel is singular or not finite");
     return stats ? scf_fill_stats(s, ls, ps, stats) : DFTA_OK;

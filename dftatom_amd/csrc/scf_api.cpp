@@ -326,15 +326,24 @@ int dfta_scf_set_exchange(dfta_scf* s, int exchange)
     dfta_ctx* ctx = s->ctx;
     DFTA_ENTER(ctx);
     DFTA_REQUIRE(ctx, s->steps_done == 0, "dfta_scf_set_exchange: after the first step");
-    DFTA_REQUIRE(ctx, exchange == DFTA_EXCHANGE_FUNCTIONAL || exchange == DFTA_EXCHANGE_KLI, "exchange (DFTA_EXCHANGE_FUNCTIONAL or DFTA_EXCHANGE_KLI)");
+    DFTA_REQUIRE(ctx, exchange == DFTA_EXCHANGE_FUNCTIONAL || exchange == DFTA_EXCHANGE_KLI || exchange == DFTA_EXCHANGE_SIC_KLI,
+                 "exchange (DFTA_EXCHANGE_FUNCTIONAL or DFTA_EXCHANGE_KLI or DFTA_EXCHANGE_SIC_KLI)");
+    const bool sic = exchange == DFTA_EXCHANGE_SIC_KLI;
     if (exchange == DFTA_EXCHANGE_FUNCTIONAL) {
         s->kli.reset();
         s->exchange_mode = exchange;
         return DFTA_OK;
     }
-    DFTA_REQUIRE(ctx, s->functional == DFTA_XC_VWN, "DFTA_EXCHANGE_KLI: functional must be DFTA_XC_VWN (exchange-only: no correlation is added)");
-    DFTA_REQUIRE(ctx, s->mixing == DFTA_MIX_LINEAR, "DFTA_EXCHANGE_KLI: mixing must be DFTA_MIX_LINEAR");
-    if (s->exchange_mode == DFTA_EXCHANGE_KLI) return DFTA_OK;
+    if (sic) {
+        DFTA_REQUIRE(ctx, s->functional == DFTA_XC_VWN, "DFTA_EXCHANGE_SIC_KLI: functional must be DFTA_XC_VWN (the correction is VWN's)");
+        DFTA_REQUIRE(ctx, s->mixing == DFTA_MIX_LINEAR, "DFTA_EXCHANGE_SIC_KLI: mixing must be DFTA_MIX_LINEAR");
+    } else {
+        DFTA_REQUIRE(ctx, s->functional == DFTA_XC_VWN, "DFTA_EXCHANGE_KLI: functional must be DFTA_XC_VWN (exchange-only: no correlation is added)");
+        DFTA_REQUIRE(ctx, s->mixing == DFTA_MIX_LINEAR, "DFTA_EXCHANGE_KLI: mixing must be DFTA_MIX_LINEAR");
+    }
+    if (s->exchange_mode == exchange) return DFTA_OK;
+    s->kli.reset();                          // from the other orbital-dependent value: its tables go
+    s->exchange_mode = DFTA_EXCHANGE_FUNCTIONAL;
     // the channels of the batch, atom-major, nspin per atom; occupations N_a (LSDA) or N_a / 2 (LDA)
     std::vector<int> norb, atom, l;
     std::vector<double> occ;
@@ -349,7 +358,7 @@ int dfta_scf_set_exchange(dfta_scf* s, int exchange)
                 occ.push_back(s->lsda ? s->solver.h_occ[k0 + k] : 0.5 * s->solver.h_occ[k0 + k]);
             }
         }
-    const int rc = s->kli.create(ctx, s->g, s->nV, norb.data(), l.data(), occ.data(), atom.data(), s->natoms, s->kli_y_mb);
+    const int rc = s->kli.create(ctx, s->g, s->nV, norb.data(), l.data(), occ.data(), atom.data(), s->natoms, s->kli_y_mb, sic);
     if (rc) return rc;
     s->exchange_mode = exchange;
     return DFTA_OK;
@@ -360,7 +369,8 @@ int dfta_scf_get_exchange(dfta_scf* s, int atom, int spin, double* vx, double* v
     if (!s) return DFTA_ERR_INVALID;
     dfta_ctx* ctx = s->ctx;
     DFTA_ENTER(ctx);
-    DFTA_REQUIRE(ctx, s->exchange_mode == DFTA_EXCHANGE_KLI, "dfta_scf_get_exchange: the exchange switch is not DFTA_EXCHANGE_KLI");
+    DFTA_REQUIRE(ctx, s->exchange_mode == DFTA_EXCHANGE_KLI || s->exchange_mode == DFTA_EXCHANGE_SIC_KLI,
+                 "dfta_scf_get_exchange: the exchange switch is not DFTA_EXCHANGE_KLI or DFTA_EXCHANGE_SIC_KLI");
     DFTA_REQUIRE(ctx, s->steps_done > 0, "no SCF step has run yet: there is no exchange potential");
     DFTA_REQUIRE(ctx, atom >= 0 && atom < s->natoms && spin >= 0 && spin < s->nspin, "atom/spin");
     const size_t N = s->g->N, c = (size_t)atom * s->nspin + spin;
@@ -378,8 +388,32 @@ int dfta_scf_exchange_ms(dfta_scf* s, float* ms)
     dfta_ctx* ctx = s->ctx;
     DFTA_ENTER(ctx);
     DFTA_REQUIRE(ctx, ms, "ms");
-    DFTA_REQUIRE(ctx, s->exchange_mode == DFTA_EXCHANGE_KLI && s->kli.timed, "dfta_scf_exchange_ms: no exchange stage has run");
+    DFTA_REQUIRE(ctx, s->exchange_mode != DFTA_EXCHANGE_FUNCTIONAL && s->kli.timed, "dfta_scf_exchange_ms: no exchange stage has run");
     DFTA_HIP(ctx, hipEventElapsedTime(ms, s->kli.ev[0], s->kli.ev[1]));
+    return DFTA_OK;
+}
+
+int dfta_scf_sic_table(dfta_scf* s, int atom, int spin, double* EH, double* EXC, double* vbar, double* c, int* homo)
+{
+    if (!s) return DFTA_ERR_INVALID;
+    dfta_ctx* ctx = s->ctx;
+    DFTA_ENTER(ctx);
+    DFTA_REQUIRE(ctx, s->exchange_mode == DFTA_EXCHANGE_SIC_KLI, "dfta_scf_sic_table: the exchange switch is not DFTA_EXCHANGE_SIC_KLI");
+    DFTA_REQUIRE(ctx, s->steps_done > 0, "no SCF step has run yet: there is no SIC table");
+    DFTA_REQUIRE(ctx, atom >= 0 && atom < s->natoms && spin >= 0 && spin < s->nspin, "atom/spin");
+    const auto rows = s->channel(atom, spin);
+    const int k0 = rows.k0, cnt = rows.cnt;
+    const size_t ch = (size_t)atom * s->nspin + spin;
+    hipStream_t st = ctx->stream;
+    auto get = [&](double* dst, const double* src) {
+        return dst && cnt > 0 ? hipMemcpyAsync(dst, src + k0, sizeof(double) * cnt, hipMemcpyDeviceToHost, st) : hipSuccess;
+    };
+    DFTA_HIP(ctx, get(EH, s->kli.d_EH.p));
+    DFTA_HIP(ctx, get(EXC, s->kli.d_EXC.p));
+    DFTA_HIP(ctx, get(vbar, s->kli.d_vbarHF.p));
+    DFTA_HIP(ctx, get(c, s->kli.d_c.p));
+    if (homo) DFTA_HIP(ctx, hipMemcpyAsync(homo, s->kli.d_homo.p + ch, sizeof(int), hipMemcpyDeviceToHost, st));
+    DFTA_HIP(ctx, hipStreamSynchronize(st));
     return DFTA_OK;
 }
 

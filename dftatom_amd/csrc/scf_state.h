@@ -65,6 +65,7 @@ struct dfta_scf {
     // dfta_scf_set_exchange: DFTA_EXCHANGE_KLI replaces the functional's launch of a step by the batched exchange stage (kli_stage.hip);
     // nothing of it is allocated otherwise
     int exchange_mode = DFTA_EXCHANGE_FUNCTIONAL;
+    // (DFTA_EXCHANGE_SIC_KLI: the functional's launch stays and the stage, built with its SIC tables, adds its potential after it)
     double kli_y_mb = kKliDefaultYMB;     // DFTA_DEBUG KLI_Y_MB, read at creation
     dfta_kli_stage kli;
     std::vector<unsigned char> h_live_ch; // per channel (atom x nspin): its atom is live in this step

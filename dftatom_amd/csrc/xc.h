@@ -5,6 +5,9 @@
 int dfta_launch_vwn_lda(dfta_ctx* ctx, const double* dN, size_t sz, double* dVexc, double* dEexc);
 int dfta_launch_vwn_lsda(dfta_ctx* ctx, const double* dNa, const double* dNb, size_t sz, double* dRes, double* dVa, double* dVb,
                          double* dEexc);
+// the two irrational constants of the VWN kernels as their launchers pass them: (3 / (2 pi))^(2/3) and 2^(1/3), from the host's libm
+double dfta_vwn_cx();
+double dfta_vwn_cbrt2();
 int dfta_launch_chachiyo_lda(dfta_ctx* ctx, int improved, const double* dN, size_t sz, double* dVexc, double* dEexc);
 // Slater exchange + PW92 correlation (xc.hip), same outputs as the VWN launchers
 int dfta_launch_pw92_lda(dfta_ctx* ctx, const double* dN, size_t sz, double* dVexc, double* dEexc);

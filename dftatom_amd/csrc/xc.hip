@@ -12,42 +12,17 @@
 
 #include "gga.h"
 #include "internal.h"
+#include "vwn_device.h"
 #include "xc.h"
 
 namespace {
 
-constexpr double kPi = 3.14159265358979323846;
-constexpr double kFourPi = 4. * kPi;
-constexpr double kThird = 1. / 3.;                                  // ExcCorBase.h:12
-
-// One Pade-like fit of VWN: eps(y) = A { ln(y^2/Y) + 2b/Q atan(Q/(2y+b)) - b y0/Y0 [ ln((y-y0)^2/Y) + 2(b+2y0)/Q atan(Q/(2y+b)) ] },
-// y = sqrt(rs), Y(y) = y^2 + b y + c, Q = sqrt(4c - b^2).  Three parameter sets (VWNExcCor.h:23-41): paramagnetic,
-// ferromagnetic, and the spin stiffness alpha_c.
-struct VwnFit { double A, y0, b, c; };
-constexpr VwnFit kPara{0.0310907, -0.10498, 3.72744, 12.93532};
-constexpr VwnFit kFerro{0.01554535, -0.325, 7.06042, 18.0578};
-constexpr VwnFit kStiff{-1. / (6. * kPi * kPi), -0.0047584, 1.13107, 13.0045};
-constexpr double poly_at(const VwnFit& p, double y) { return y * y + p.b * y + p.c; }
-
-struct FitValue { double eps, slope; };     // eps: the fit itself (VWNExcCor.h:43-50); slope: its rs-derivative term (VWNExcCor.h:52-55)
-
-// NESTED selects how Y(y) is rounded: the LDA routines write y*y + b*y + c (VWNExcCor.h:89,119), the LSDA ones y*(y + b) + c
-// (VWNExcCor.h:182,187,192) -- both kept so that each path rounds like the reference's
-template <bool NESTED>
-__device__ __forceinline__ FitValue eval_fit(const VwnFit p, double y)
-{
-    const double Y = NESTED ? y * (y + p.b) + p.c : y * y + p.b * y + p.c;
-    const double Y0 = poly_at(p, p.y0);
-    const double dy = y - p.y0;
-    const double Q = sqrt(4 * p.c - p.b * p.b);
-    const double at = atan(Q / (2. * y + p.b));
-    FitValue v;
-    v.eps = p.A * (log(y * y / Y) + 2. * p.b / Q * at - p.b * p.y0 / Y0 * (log(dy * dy / Y) + 2. * (p.b + 2. * p.y0) / Q * at));
-    v.slope = p.A * (p.c * dy - p.b * p.y0 * y) / (dy * Y);
-    return v;
-}
-
-__device__ __forceinline__ double wigner_seitz(double rho) { return pow(3. / (kFourPi * rho), kThird); }   // rs, eq 2 of the NIST note
+using dfta_vwn_dev::eval_fit;
+using dfta_vwn_dev::FitValue;
+using dfta_vwn_dev::kPara;
+using dfta_vwn_dev::kPi;
+using dfta_vwn_dev::kThird;
+using dfta_vwn_dev::wigner_seitz;
 
 // LDA (VWNExcCor.h:73-128): v_xc and the double-counting term eps_xc - v_xc, both from one evaluation of the paramagnetic fit
 __global__ void k_vwn_lda(const double* __restrict__ n, size_t sz, double* __restrict__ vexc, double* __restrict__ eexc, double cx)
@@ -66,51 +41,18 @@ __global__ void k_vwn_lda(const double* __restrict__ n, size_t sz, double* __res
     }
 }
 
-// LSDA (VWNExcCor.h:134-312).  With g(zeta) the spin interpolation of ExcCorBase.h:14-19, g''(0) = gdd and
-//     w(zeta) = g / gdd * (1 + beta zeta^4),   beta = gdd (eps_F - eps_P) / alpha_c - 1
-// the correlation energy is eps_P + alpha_c w (eqs 7-10 of the NIST note); the kernel forms its rs-derivative (`drs`) and
-// its zeta-derivative (`dz`) and assembles the common term and the two spin potentials from them.
+// LSDA (VWNExcCor.h:134-312): the node arithmetic is dfta_vwn_dev::lsda_point (vwn_device.h), which the orbital xc of the
+// self-interaction correction shares
 __global__ void k_vwn_lsda(const double* __restrict__ na, const double* __restrict__ nb, size_t sz, double* __restrict__ res,
                            double* __restrict__ va, double* __restrict__ vb, double* __restrict__ eexc, double cx, double cbrt2)
 {
-    const double gdd = 4. / (9. * (cbrt2 - 1.));
-    const double gscale = 1. / (2. * (cbrt2 - 1.)), dgscale = 2. / (3. * (cbrt2 - 1.));       // ExcCorBase.h:16,23
+    const dfta_vwn_dev::LsdaConsts k = dfta_vwn_dev::lsda_consts(cx, cbrt2);
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < sz; i += (size_t)gridDim.x * blockDim.x) {
-        const double up = na[i], dn = nb[i];
-        const double tot = up + dn;
-        double common = 0., vup = 0., vdn = 0., e = 0.;
-        if (!(tot < 1E-18)) {                                         // VWNExcCor.h:160,260
-            const double rs = wigner_seitz(tot);
-            const double z = (up - dn) / tot;
-            const double z3 = z * z * z, z4 = z3 * z;
-            const double g = gscale * (pow(1. + z, 4. * kThird) + pow(1. - z, 4. * kThird) - 2.);
-            const double dg = dgscale * (pow(1. + z, kThird) - pow(1. - z, kThird));
-            const double y = sqrt(rs);
-            const FitValue P = eval_fit<true>(kPara, y), F = eval_fit<true>(kFerro, y), S = eval_fit<true>(kStiff, y);
-
-            const double gap = F.eps - P.eps;                                             // VWNExcCor.h:202
-            const double beta = gdd * gap / S.eps - 1.;
-            const double env = 1. + beta * z4;
-            const double w = g / gdd * env;
-            const double dbeta = gdd / S.eps * (F.slope - P.slope - S.slope * gap / S.eps);   // VWNExcCor.h:208
-            const double dw = g / gdd * z4 * dbeta;
-            const double drs = kThird * (P.slope + S.slope * w + S.eps * dw);             // VWNExcCor.h:212-213
-            const double dz = S.eps / gdd * (4. * beta * z3 * g + env * dg);               // VWNExcCor.h:216
-
-            const double xP = -cx / rs;                                                    // exchange of the unpolarised gas ...
-            const double xF = cbrt2 * xP;                                                  // ... and of the fully polarised one
-            common = P.eps + S.eps * w - drs;                                              // VWNExcCor.h:219-231
-            vup = -(cx * cbrt2) / wigner_seitz(up) + common + (1. - z) * dz;               // VWNExcCor.h:233
-            vdn = -(cx * cbrt2) / wigner_seitz(dn) + common - (1. + z) * dz;               // VWNExcCor.h:234
-            common += (xP + (xF - xP) * g);                                                // VWNExcCor.h:236
-
-            const double xPd = (0.25 * cx) / rs;                                           // VWNExcCor.h:271-272
-            e = xPd + (cbrt2 * xPd - xPd) * g + drs;                                       // VWNExcCor.h:306-308
-        }
-        if (res) res[i] = common;
-        if (va) va[i] = vup;
-        if (vb) vb[i] = vdn;
-        if (eexc) eexc[i] = e;
+        const dfta_vwn_dev::LsdaPoint p = dfta_vwn_dev::lsda_point(k, na[i], nb[i]);
+        if (res) res[i] = p.common;
+        if (va) va[i] = p.vup;
+        if (vb) vb[i] = p.vdn;
+        if (eexc) eexc[i] = p.e;
     }
 }
 
@@ -168,6 +110,8 @@ __global__ void k_pw92_lsda(const double* __restrict__ na, const double* __restr
 // the two irrational constants are evaluated once on the host with libm, as the reference does (VWNExcCor.h:75,139-140)
 static double host_X1() { return pow(3. / (2. * kPi), 2. * kThird); }
 static double host_X2() { return pow(2., kThird); }
+double dfta_vwn_cx() { return host_X1(); }
+double dfta_vwn_cbrt2() { return host_X2(); }
 
 int dfta_launch_chachiyo_lda(dfta_ctx* ctx, int improved, const double* dN, size_t sz, double* dVexc, double* dEexc)
 {

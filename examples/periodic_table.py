@@ -11,6 +11,7 @@ costs nothing more (dfta_scf_step).  The fixed-size result records are gathered 
     python examples/periodic_table.py --charge 1            # the cations X+ (Z > charge)
     python examples/periodic_table.py --exx                 # E_H, the exact-exchange energy of the orbitals and the functional's E_xc per atom
     python examples/periodic_table.py --exchange kli --zmax 18 --levels 14   # self-consistent exchange-only KLI; lists the atoms that did not finish
+    python examples/periodic_table.py --exchange sic --zmax 18 --levels 14   # self-interaction-corrected LSDA (Perdew-Zunger SIC through KLI)
     python examples/periodic_table.py --kli                 # E_x from the Fock averages and the tail r vKLI of the KLI exchange potential per atom
     python examples/periodic_table.py --form-factors        # X-ray form factors f(q) of every atom, one launch per shard
     python examples/periodic_table.py --ionization          # IE = E(X+) - E(X): neutral atom and cation of every Z in ONE batch per rank
@@ -45,10 +46,12 @@ def main():
                     help="tolerance: the multigrid's tolerance mode; adaptive: that, and the V-cycles stop at the round-off floor")
     ap.add_argument("--mixing", choices=("linear", "anderson"), default="linear",
                     help="anderson: Anderson density mixing (DFTA_MIX_ANDERSON), about half the SCF steps per atom")
-    ap.add_argument("--exchange", choices=("functional", "kli"), default="functional",
+    ap.add_argument("--exchange", choices=("functional", "kli", "sic"), default="functional",
                     help="kli: self-consistent exchange-only KLI (DFTA_EXCHANGE_KLI: every step's exchange potential from its own orbitals, no "
                          "correlation; --xc vwn and --mixing linear only).  The step cap is --max-steps; atoms that have not met the stop test "
-                         "by then are listed (open-shell atoms such as Fe oscillate under this rule), not iterated further")
+                         "by then are listed (open-shell atoms such as Fe oscillate under this rule), not iterated further.  "
+                         "sic: self-interaction-corrected LSDA (DFTA_EXCHANGE_SIC_KLI: VWN plus the Perdew-Zunger correction as one KLI "
+                         "potential per spin channel; the same two conditions and the same listing)")
     ap.add_argument("--emulate-ranks", type=int, default=0,
                     help="one GPU, no launcher: run each of the N shards of an N-rank sweep alone, one after the other, and report the "
                          "per-shard wall times; their maximum PREDICTS the N-GPU wall time (shards never interact; the only collective "
@@ -146,7 +149,7 @@ def main():
     cap = max(len(s) for s in sweep.partition_atoms(Zs, world, cost=cost, model=cost_model))
     t0 = time.time()
     scf = D.Scf(ctx, grid, mine, lsda=args.lsda, charge=args.charge if args.charge else None,
-                exchange=D.EXCHANGE_KLI if args.exchange == "kli" else D.EXCHANGE_FUNCTIONAL, **modes)
+                exchange={"kli": D.EXCHANGE_KLI, "sic": D.EXCHANGE_SIC_KLI}.get(args.exchange, D.EXCHANGE_FUNCTIONAL), **modes)
     steps = 0
     while steps < args.max_steps:
         scf.step(want_stats=False)
@@ -154,8 +157,9 @@ def main():
         _, fin = scf.energies()
         if fin.all():
             break
-    if args.exchange == "kli" and not fin.all():
-        print("rank %d: not finished after %d steps under --exchange kli: Z = %s" % (rank, steps, [int(z) for z, f in zip(mine, fin) if not f]),
+    if args.exchange != "functional" and not fin.all():
+        print("rank %d: not finished after %d steps under --exchange %s: Z = %s"
+              % (rank, steps, args.exchange, [int(z) for z, f in zip(mine, fin) if not f]),
               flush=True)
     outer = {}
     if args.orbitals:                           # one launch for every orbital of this rank's batch; the row of each atom's outermost level

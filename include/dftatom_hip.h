@@ -619,6 +619,55 @@ int  dfta_kli_channels(dfta_ctx* ctx, const dfta_grid* g, int nch, const int* no
                        const double* u, int first_step, double alpha, double* vx_inout, double* v_raw, double* vbarHF, double* c, int* homo,
                        double* Ex);
 
+/* ---- self-interaction-corrected LSDA: Perdew-Zunger SIC through KLI (beyond the reference) ----------------------------------------------
+ * A third value of the switch above: with DFTA_EXCHANGE_SIC_KLI a step keeps the functional's v_xc (VWN) and adds to it ONE local potential
+ * per spin channel that stands for the orbital-dependent Perdew-Zunger corrections v_a^SIC = -(v_H[rho_a] + v_xc[rho_a, 0]), folded together
+ * by the KLI construction of the exchange block.  The potential has the -1/r tail and the HOMO eigenvalue approaches -IP; a one-electron
+ * atom is free of self-interaction (H: -0.5 Ha).  Refusals as DFTA_EXCHANGE_KLI: after the first dfta_scf_step; functional != DFTA_XC_VWN;
+ * mixing != DFTA_MIX_LINEAR.  Both kinds of grid.  Creation is unchanged.  With the switch at 0 or 1 every launch and every bit of a step
+ * is what it was.
+ *
+ * Per live channel (atom, sigma) with shells a = 0 .. n-1, channel occupations n_a (LSDA N_a; LDA spin 0, N_a / 2) and the HOMO rule of
+ * the exchange block, in the notation of that block (s_i = dr/di, Q[.] with the Simpson 3/8 weights and the fixed 256-lane shape):
+ *   rho_a,i = (u_a,i u_a,i) / ((K r_i) r_i) for i >= 1, K the double nearest 4 pi (one product, then the two products of the divisor,
+ *             one quotient); rho_a,0 = 0.0                       the density of ONE electron in shell a
+ *   y0_a    = y^0_aa: the row of job (a, a, 0) of dfta_screening_yk, bit for bit              (its Hartree potential)
+ *   v_a,i   = va of dfta_vwn_lsda at (rho_a,i, 0.0); eps_a,i = vexc + eexcdif of dfta_vwn_lsda there (one sum): the fully polarised LSDA
+ *             potential and energy density per electron of the orbital density, the kernel's own arithmetic (one device function)
+ *   X_a,i   = (y0_a,i + v_a,i) u_a,i                             one sum, one product
+ *   D, num, vS, vbar_a = -Q[(u_a X_a) s] (the column DFTA_XP_HF: now <a| v_a^SIC |a>), vbarS_a, S_ab, M, the reduced system, c, vKLI, the
+ *   Coulomb tail beyond the last node with D > 0 and the mix into vx: exactly those of the exchange block and of DFTA_EXCHANGE_KLI, the
+ *   same kernels for the solve and the update.  vS = -(num / D) is the density-weighted average of the v_a^SIC.
+ *   EH_a    = 0.5 Q[((u_a u_a) y0_a) s]                          (the factor applied to the finished quadrature)
+ *   EXC_a   = Q[((u_a u_a) eps_a) s]
+ *   E_SIC,sigma = -(Sum_a n_a (EH_a + EXC_a))                    one accumulator from 0.0, a ascending
+ *   E_SIC   = 2 E_SIC,0 (LDA), E_SIC,alpha + E_SIC,beta (LSDA); a channel without levels contributes 0.
+ * The step: level search, mix, Poisson and the functional's launch on the mixed densities as ever; then one more launch adds the SIC
+ * potential for every atom that has not finished:
+ *   LDA:  Vexc = Vexc + vx_0, eexc = eexc - vx_0;
+ *   LSDA: va = va + vx_alpha, vb = vb + vx_beta; t = (dA vx_alpha + dB vx_beta) / rho where rho > 0, else 0.0 (two products, one sum, one
+ *         quotient); Vexc = Vexc + t, eexc = eexc - t.
+ * The potential and the integrands follow as ever; the energies with eExcDif = 4 pi I[2] + E_SIC.  A frozen atom is in no launch of the
+ * stage and keeps vx, v_raw, E_SIC and its per-shell table.  A pivot that is zero or not finite: as DFTA_EXCHANGE_KLI.  Chunks: whole
+ * channels whose y rows (one per shell) fit the budget of DFTA_EXCHANGE_KLI (DFTA_DEBUG KLI_Y_MB); no host synchronisation inside the
+ * stage, no floating-point atomics, shapes depend on N alone: a channel's bits do not depend on the batch, its position, the chunking or
+ * the run.  dfta_scf_get_exchange and dfta_scf_exchange_ms work under this value (the E_x slot holds E_SIC).
+ * Limits: VWN only (no SIC of PW92 / PBE); spherically averaged shells as the orbitals (one orbital density per shell, no unitary
+ * optimisation of the orbitals); linear mixing only. */
+#define DFTA_EXCHANGE_SIC_KLI    2   /* v_xc of VWN plus the Perdew-Zunger self-interaction correction as one KLI potential per channel */
+/* per shell of channel (atom, spin) after the last step in which the atom was live: EH_a, EXC_a, vbar_a = <a| v_a^SIC |a>, c_a (cnt doubles
+ * each, cnt = dfta_scf_num_levels), homo: the HOMO's index (-1: no levels).  Any pointer may be NULL.  DFTA_ERR_INVALID before the first
+ * step or without DFTA_EXCHANGE_SIC_KLI. */
+int  dfta_scf_sic_table(dfta_scf* s, int atom, int spin, double* EH, double* EXC, double* vbar, double* c, int* homo);
+/* the stage on caller-supplied channels, arguments as dfta_kli_channels.  Further outputs, any of which may be NULL: y0, vorb, eps, X
+ * (shells x N each: y0_a, v_a, eps_a, X_a); D, vS (nch x N, before the tail: vS of a node with D = 0 is 0.0); EH, EXC and vbarS per
+ * shell; M: the channels' matrices end to end, norb x norb row-major each, M_ab = S_ab n_b formed on the host from the one S_ab of a pair;
+ * Esic (E_SIC,sigma) per channel. */
+int  dfta_sic_channels(dfta_ctx* ctx, const dfta_grid* g, int nch, const int* norb, const int* l, const double* occ, const double* E,
+                       const double* u, int first_step, double alpha, double* vx_inout, double* y0, double* vorb, double* eps, double* X,
+                       double* D, double* vS, double* v_raw, double* vbar, double* c, double* EH, double* EXC, int* homo, double* Esic,
+                       double* vbarS, double* M);
+
 /* ---- Bessel transforms: X-ray form factors and momentum-space orbitals (beyond the reference) -------------------------------------------
  * With Q[.], s_i = dr/di and the weights of the orbital block, a row f of N doubles, x_i = q r_i (one product, rounded once) and w_i the
  * weight of node i WITHOUT the factor 3/8 (1 at the two end nodes, 2 where i % 3 == 0, 3 elsewhere):
