@@ -115,6 +115,7 @@ SIGNATURES = {
     "dfta_poisson_solve": (C.c_int, [vp, c_ip, c_dp, c_dp, c_ip, c_dp]),
     "dfta_poisson_solve_dev": (C.c_int, [vp, vp, vp, vp]),
     "dfta_poisson_group_info": (C.c_int, [vp, c_ip, c_ip, c_ip]),
+    "dfta_poisson_predict_counts": (C.c_int, [vp, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]),
     "dfta_scf_poisson_info": (C.c_int, [vp, c_ip, c_ip, c_ip]),
     "dfta_poisson_level_size": (C.c_int, [vp, C.c_int]),
     "dfta_poisson_set_level": (C.c_int, [vp, C.c_int, c_dp, c_dp]),
@@ -485,6 +486,13 @@ class Poisson:
         g, d, a = C.c_int(), C.c_int(), C.c_int()
         self.ctx.check(self.ctx.lib.dfta_poisson_group_info(self.h, C.byref(g), C.byref(d), C.byref(a)))
         return g.value, bool(d.value), a.value
+
+    def predict_counts(self):
+        """(fused visits that ran with predicted start values and a hand-over check, visits whose check failed and that were repeated)
+        since the solver was created"""
+        c, r = C.c_ulonglong(), C.c_ulonglong()
+        self.ctx.check(self.ctx.lib.dfta_poisson_predict_counts(self.h, C.byref(c), C.byref(r)))
+        return c.value, r.value
 
     def level_size(self, lvl):
         return self.ctx.lib.dfta_poisson_level_size(self.h, lvl)

@@ -152,6 +152,7 @@ struct dfta_poisson : PoissonPlan {      // the plan it was built from (D, resid
     int aborts = 0;                 // solves that had to be repeated
     DevBuf<double> d_res_slots;     // resident: per atom res_slot_doubles() exchange slots (sentinel-filled before every launch)
     DevBuf<double> d_res_spill;     // res16: per member the two LDS images of level 0
+    DevBuf<unsigned long long> d_pred_ctr;   // fused visits with predicted start values: [0] checked, [1] repeated (D.pred_ctr)
     bool grouped() const { return D.G > 1 || resident; }
 };
 
@@ -315,6 +316,8 @@ static PoissonKnobs read_knobs(int batch)
     K.nofuse3 = set(dfta_knob("POISSON_NOFUSE3"));
     K.nofuse3_wave = set(dfta_knob("POISSON_NOFUSE3_WAVE"));
     K.nohalf129 = set(dfta_knob("POISSON_NOHALF129"));
+    K.nopredict = set(dfta_knob("POISSON_NOPREDICT"));
+    K.predict_fuzz = set(dfta_knob("POISSON_PREDICT_FUZZ"));
     K.nofold = set(dfta_knob("POISSON_NOFOLD"));
     K.nofold_lds = set(dfta_knob("POISSON_NOFOLD_LDS"));
     K.nofuse_coop = set(dfta_knob("POISSON_NOFUSE_COOP"));
@@ -336,6 +339,9 @@ static hipError_t allocate(dfta_poisson* p)
     TRY_HIP(p->d_phi1.alloc(P.n_level_store));
     TRY_HIP(p->d_src.alloc(P.n_level_store));
     TRY_HIP(p->d_cur.alloc(P.n_cur));
+    TRY_HIP(p->d_pred_ctr.alloc(2));
+    TRY_HIP(hipMemsetAsync(p->d_pred_ctr, 0, 2 * sizeof(unsigned long long), st));
+    p->D.pred_ctr = p->d_pred_ctr.p;
     TRY_HIP(p->d_desc.alloc(1));
     TRY_HIP(hipMemcpyAsync(p->d_desc, &p->D, sizeof(MgDesc), hipMemcpyHostToDevice, st));
     TRY_HIP(p->d_total_vcycles.alloc(1));
@@ -492,6 +498,22 @@ int dfta_poisson_solve_dev(dfta_poisson* p, const int* dZ, const double* dDensit
 int dfta_poisson_group_info(const dfta_poisson* p, int* G, int* degraded, int* aborts)
 {
     return dfta_poisson_group_state(p, G, degraded, aborts);
+}
+
+// fused visits of the one-wave levels that ran with predicted start values (checked) and those whose hand-over check failed and that
+// were run again with the full warm-up (repeated), since the solver was created; the one-workgroup fallback's visits included
+int dfta_poisson_predict_counts(dfta_poisson* p, unsigned long long* checked, unsigned long long* repeated)
+{
+    if (!p) return DFTA_ERR_INVALID;
+    dfta_ctx* ctx = p->ctx;
+    DFTA_ENTER(ctx);
+    unsigned long long a[2] = {0, 0}, b[2] = {0, 0};
+    DFTA_HIP(ctx, hipMemcpyAsync(a, p->d_pred_ctr, sizeof(a), hipMemcpyDeviceToHost, ctx->stream));
+    if (p->fallback) DFTA_HIP(ctx, hipMemcpyAsync(b, p->fallback->d_pred_ctr, sizeof(b), hipMemcpyDeviceToHost, ctx->stream));
+    DFTA_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (checked) *checked = a[0] + b[0];
+    if (repeated) *repeated = a[1] + b[1];
+    return DFTA_OK;
 }
 
 int dfta_poisson_level_size(const dfta_poisson* p, int lvl)

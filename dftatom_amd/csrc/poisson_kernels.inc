@@ -537,12 +537,16 @@ __device__ __forceinline__ double gs_point2y(double s, double y, double yp, doub
 }
 // RIGHT: the part has no halo column behind it (a member's staged part of a shared level): lane NT-1 takes the old values of the three
 // nodes behind its chunk and the sources of the first two from rightP[0..2] / rightS[0..1] instead.
-template <int LOGC, int RS, int NT, int KST, bool CAREFUL, bool RIGHT = false>
+// WARM: the warm-up's length.  PRED (cs_visit3, with a WARM shorter than kWarm3): the stages start from hs[0..2] -- predictions of twice
+// x1[lo-W-1], x2[lo-W-2], x3[lo-W-3] -- instead of from old values, and the lane reports its pipeline state (y1, y2, y3) as it enters its
+// chunk (hs[3..5]: twice x1[lo-1], x2[lo-2], x3[lo-3], from its warm-up) and as it leaves it (hs[6..8]: the same nodes of the lane
+// behind it, from its own chunk) for the caller's hand-over check.
+template <int LOGC, int RS, int NT, int KST, bool CAREFUL, bool RIGHT = false, int WARM = kWarm3, bool PRED = false>
 __device__ __forceinline__ void gs_lds3(const double* __restrict__ SSbase, double* __restrict__ PPbase, const int tid, const int lo_g,
                                         const bool last_lane, const double xN, const double dh, double& e1, double& e2, double& e3,
-                                        const double* rightP = nullptr, const double* rightS = nullptr)
+                                        const double* rightP = nullptr, const double* rightS = nullptr, double* hs = nullptr)
 {
-    constexpr int C = 1 << LOGC, Cm1 = C - 1, kH = 8, W = kWarm3;
+    constexpr int C = 1 << LOGC, Cm1 = C - 1, kH = 8, W = WARM;
     static_assert(C >= 4 && C <= 32 && W % (2 * kH) == 0, "fused pass: 4..32 nodes per lane");
     typedef __attribute__((address_space(3))) double lds_f64;
     typedef __attribute__((address_space(3))) const double lds_cf64;
@@ -620,7 +624,8 @@ __device__ __forceinline__ void gs_lds3(const double* __restrict__ SSbase, doubl
         }
     };
     if (active) {
-        y1 = 2.0 * pp[off(-W - 1)]; y2 = 2.0 * pp[off(-W - 2)]; y3 = 2.0 * pp[off(-W - 3)];
+        if constexpr (PRED) { y1 = hs[0]; y2 = hs[1]; y3 = hs[2]; }
+        else { y1 = 2.0 * pp[off(-W - 1)]; y2 = 2.0 * pp[off(-W - 2)]; y3 = 2.0 * pp[off(-W - 3)]; }
         sA = ps[off(-W - 1)]; sB = ps[off(-W - 2)];
         load(ax, as, -W);
         for (int r0 = -W; r0 < 0; r0 += 2 * kH) {
@@ -632,6 +637,7 @@ __device__ __forceinline__ void gs_lds3(const double* __restrict__ SSbase, doubl
             warm(bx, bv, r0 + kH);
         }
         y1p = y1; y2p = y2;
+        if constexpr (PRED) { hs[3] = y1; hs[4] = y2; hs[5] = y3; }
         // old values behind the chunk: the right neighbour overwrites them after the barrier
         xr0 = last_lane ? xN : pp[off(C)];
         xr1 = pp[off(C + 1)]; xr2 = pp[off(C + 2)];
@@ -654,6 +660,7 @@ __device__ __forceinline__ void gs_lds3(const double* __restrict__ SSbase, doubl
                 own(std::false_type{}, bx, bv, r0 + kH);
             }
         }
+        if constexpr (PRED) { hs[6] = y1; hs[7] = y2; hs[8] = y3; }
         if (KST >= 2) {
             // two steps behind the chunk: x1 (x2) of the right neighbour's first node(s) from the old values read above; a chunk that
             // ends at the level's last node finds the boundary value there
@@ -678,6 +685,27 @@ __device__ __forceinline__ void gs_lds3(const double* __restrict__ SSbase, doubl
         }
     }
     e1 = a1; e2 = 0.25 * a2; e3 = 0.25 * a3;
+}
+
+// ---- predicted start values of the one-wave levels' fused visits (exact mode; the argument stands above cs_visit3) ----------------
+constexpr int kPredW = 32;                         // the warm-up of a visit that starts from predictions
+constexpr bool kPredict = kWarm3 > kPredW;         // the tolerance kernels start from old values 32 nodes ahead by design
+
+// lane t <- v of lane t-1 (DPP wave_shr:1 on both halves), lane 0 keeps `keep`
+__device__ __forceinline__ double lane_shr1(double keep, double v)
+{
+    const long long k = __builtin_bit_cast(long long, keep), x = __builtin_bit_cast(long long, v);
+    const int lo = __builtin_amdgcn_update_dpp((int)k, (int)x, 0x138, 0xf, 0xf, false);
+    const int hi = __builtin_amdgcn_update_dpp((int)(k >> 32), (int)(x >> 32), 0x138, 0xf, 0xf, false);
+    return __builtin_bit_cast(double, ((long long)hi << 32) | (unsigned)lo);
+}
+// lane t <- v of lane t+1 (DPP wave_shl:1 on both halves), lane 63 keeps `keep`
+__device__ __forceinline__ double lane_shl1(double keep, double v)
+{
+    const long long k = __builtin_bit_cast(long long, keep), x = __builtin_bit_cast(long long, v);
+    const int lo = __builtin_amdgcn_update_dpp((int)k, (int)x, 0x130, 0xf, 0xf, false);
+    const int hi = __builtin_amdgcn_update_dpp((int)(k >> 32), (int)(x >> 32), 0x130, 0xf, 0xf, false);
+    return __builtin_bit_cast(double, ((long long)hi << 32) | (unsigned)lo);
 }
 
 // One sweep of an LDS-resident level by ONE thread, in the reference's order.  The loads of a batch (right neighbours,
@@ -1726,15 +1754,6 @@ __device__ __forceinline__ double seq_sweep_inplace(const double* __restrict__ S
     return err2;
 }
 
-// lane t <- v of lane t-1 (DPP wave_shr:1 on both halves), lane 0 keeps `keep`
-__device__ __forceinline__ double lane_shr1(double keep, double v)
-{
-    const long long k = __builtin_bit_cast(long long, keep), x = __builtin_bit_cast(long long, v);
-    const int lo = __builtin_amdgcn_update_dpp((int)k, (int)x, 0x138, 0xf, 0xf, false);
-    const int hi = __builtin_amdgcn_update_dpp((int)(k >> 32), (int)(x >> 32), 0x138, 0xf, 0xf, false);
-    return __builtin_bit_cast(double, ((long long)hi << 32) | (unsigned)lo);
-}
-
 // The same sweep (n <= 65 nodes, natural order) by the 64 lanes of a wave: lane t keeps S, the old right neighbour and the
 // old value of node t + 1 in registers and recomputes its node in every step from the candidate of lane t - 1, handed on
 // through a DPP lane shift (lane 0: from the boundary value).  The candidate of node i is final from step i on -- its
@@ -1861,11 +1880,99 @@ __device__ __forceinline__ double cs_sweep_scan_small(const double* __restrict__
 // When the reference would have stopped after the first or the second sweep (||dPhi|| < errorMin: PoissonSolver.cpp:66-77) the lane
 // puts its nodes back as they were and the caller runs the visit sweep by sweep.  Returns true when the visit is done.
 // (NT: the lanes that hold nodes -- 64, or 32 for the 129-node level, which is laid out 4 nodes per lane for this pass)
+//
+// Predicted start values (exact mode; POISSON_NOPREDICT: off).  The 112-node warm-up is 75 .. 95 % of the pass, and it is that long only
+// because the stages start from OLD values, which on a correction level are off by O(1) of themselves: 2^53 ulp to contract away at
+// b ~ 0.52 per node.  In exact arithmetic a sweep is the affine recurrence x_i = a x_(i-1) + c_i, a = (1 + dh) / 2,
+// c_i = (S_i + (1 - dh) x_old(i+1)) / 2 (dh = d / 2), so the new values can be PREDICTED to a few ulp of the level's scale without any
+// warm-up: every lane runs the recurrence over its chunk from zero (its offset), a log-depth scan over the lanes with the powers of a^C
+// gives the value entering each chunk, and one more multiply-add per node the values inside it (cs_predict3: three such stages, each
+// feeding on the one before -- ~12 C + 90 cheap instructions).  The fused pass then starts kPredW = 32 nodes in front of the chunk from
+// the predictions: an error of a few ulp is gone after ~10 nodes of contraction (the pipeline amplifies it by <= 2^5.4 on the way).
+// The prediction never reaches a result, because every visit is CHECKED: just before its first own step a lane's pipeline state must be,
+// bit for bit, what the lane in front of it has computed for those nodes inside its own chunk (x1[lo-1], x2[lo-2], x3[lo-3]).  Lane 0
+// starts on the level's boundary and the lanes up to node kPredW restart there, so by induction over the lanes a visit whose checks all
+// pass is the sequential result exactly -- a stronger statement than the statistical 96 / 112-node argument.  On any mismatch the lanes
+// put their nodes back and the visit is repeated with the full warm-up from old values; the error norms are the accepted pass's.
+
+// Predictions of the three sweeps of a visit at the nodes where the lanes' short warm-ups start.  old[0..C-1]: the lane's nodes, sv: their
+// sources (node lane * C + k), xN: the level's last node.  hs[0..2] = twice the predicted x1[lo-W-1], x2[lo-W-2], x3[lo-W-3], W = kPredW
+// (W is a multiple of C: they are the last three nodes of lane - W/C - 1).  fuzz: every prediction off by a relative 2^-20 (tests).
+template <int LOGC, int NT>
+__device__ __forceinline__ void cs_predict3(const double (&old)[1 << LOGC], const double (&sv)[1 << LOGC], const double xN, const double dh,
+                                            const int lane, const bool fuzz, double* hs)
+{
+    constexpr int C = 1 << LOGC;
+    static_assert(kPredW % C == 0 && C >= 4, "the start nodes are the last three of one lane");
+    const double a = 0.5 * (1.0 + dh), omd = 1.0 - dh;
+    // a^(k+1), k < C; the scan's ratios (a^C)^(2^s) inside a row of 16 lanes, and (a^C)^(j+1) for the lane j lanes behind a row's / a
+    // half-wave's last lane (the two steps across the rows)
+    double pw[C];
+    pw[0] = a;
+#pragma unroll
+    for (int k = 1; k < C; ++k) pw[k] = pw[k - 1] * a;
+    const double A1 = pw[C - 1], A2 = A1 * A1, A4 = A2 * A2, A8 = A4 * A4, A16 = A8 * A8, A32 = A16 * A16;
+    const int j31 = (lane & 31) + 1;
+    double P15 = (j31 & 1) ? A1 : 1.0;
+    P15 = (j31 & 2) ? P15 * A2 : P15;
+    P15 = (j31 & 4) ? P15 * A4 : P15;
+    P15 = (j31 & 8) ? P15 * A8 : P15;
+    double P31 = (j31 & 16) ? P15 * A16 : P15;
+    P31 = (j31 & 32) ? A32 : P31;
+    P15 = ((lane & 15) == 15) ? A16 : P15;          // j15 = (lane & 15) + 1 = 16 where j31 = 16 or 32
+    // one sweep: in[k] = the previous sweep's value of the lane's node k, in[C] = of the node behind the chunk
+    auto stage = [&](const double (&in)[C + 1], double (&out)[C]) {
+        double z[C];
+        double run = 0;
+#pragma unroll
+        for (int k = 0; k < C; ++k) {
+            const double c = 0.5 * __builtin_fma(omd, in[k + 1], sv[k]);
+            run = (k == 0 && lane == 0) ? in[0] : __builtin_fma(a, run, c);       // node 0 is the boundary value
+            z[k] = run;
+        }
+        double v = run;
+        v = __builtin_fma(A1, wt_dpp<0x111, 0xf>(v), v);      // row_shr:1 (lanes without a source get 0: no contribution)
+        v = __builtin_fma(A2, wt_dpp<0x112, 0xf>(v), v);      // row_shr:2
+        v = __builtin_fma(A4, wt_dpp<0x114, 0xf>(v), v);      // row_shr:4
+        v = __builtin_fma(A8, wt_dpp<0x118, 0xf>(v), v);      // row_shr:8
+        v = __builtin_fma(P15, wt_dpp<0x142, 0xa>(v), v);     // row_bcast:15 into rows 1 and 3
+        v = __builtin_fma(P31, wt_dpp<0x143, 0xc>(v), v);     // row_bcast:31 into rows 2 and 3
+        const double xin = lane_shr1(0.0, v);
+#pragma unroll
+        for (int k = 0; k < C; ++k) out[k] = (k == 0 && lane == 0) ? in[0] : __builtin_fma(pw[k], xin, z[k]);
+    };
+    double in[C + 1], x1[C], x2[C];
+#pragma unroll
+    for (int k = 0; k < C; ++k) in[k] = old[k];
+    in[C] = lane_shl1(xN, old[0]);
+    in[C] = (lane == NT - 1) ? xN : in[C];
+    stage(in, x1);
+#pragma unroll
+    for (int k = 0; k < C; ++k) in[k] = x1[k];
+    in[C] = lane_shl1(xN, x1[0]);
+    in[C] = (lane == NT - 1) ? xN : in[C];
+    stage(in, x2);
+#pragma unroll
+    for (int k = 0; k < C; ++k) in[k] = x2[k];
+    in[C] = lane_shl1(xN, x2[0]);
+    in[C] = (lane == NT - 1) ? xN : in[C];
+    double x3[C];
+    stage(in, x3);
+    constexpr int back = kPredW / C + 1;
+    const double g = fuzz ? 2.0 * (1.0 + 0x1p-20) : 2.0;
+    hs[0] = g * __shfl_up(x1[C - 1], back, 64);
+    hs[1] = g * __shfl_up(x2[C - 2], back, 64);
+    hs[2] = g * __shfl_up(x3[C - 3], back, 64);
+}
+
+// (predict: MgDesc::predict; ctr: the solver's counters of checked / repeated visits)
 template <int LOGC, int NT = 64>
-__device__ __forceinline__ bool cs_visit3(const double* __restrict__ S, double* __restrict__ P, const double dh, const double errorMin, double& err)
+__device__ __forceinline__ bool cs_visit3(const double* __restrict__ S, double* __restrict__ P, const double dh, const double errorMin, double& err,
+                                          const int predict, unsigned long long* ctr)
 {
     constexpr int C = 1 << LOGC;
     typedef __attribute__((address_space(3))) double lds_f64;
+    typedef __attribute__((address_space(3))) const double lds_cf64;
     lds_f64* pl = (lds_f64*)(P);
     const int lane = threadIdx.x & 63;
     double keep[C];
@@ -1873,7 +1980,38 @@ __device__ __forceinline__ bool cs_visit3(const double* __restrict__ S, double* 
     for (int k = 0; k < C; ++k) keep[k] = pl[(k << 6) + lane];
     const double xN = pl[C << 6];                   // the level's last node (cs_idx)
     double f1, f2, f3;
-    gs_lds3<LOGC, 64, NT, 3, true>(S, P, lane, lane << LOGC, lane == NT - 1, xN, dh, f1, f2, f3);
+    bool accepted = false;
+    if constexpr (kPredict) {
+        if (predict) {
+            double sv[C], hs[9] = {};
+#pragma unroll
+            for (int k = 0; k < C; ++k) sv[k] = ((lds_cf64*)(S))[(k << 6) + lane];
+            cs_predict3<LOGC, NT>(keep, sv, xN, dh, lane, predict == 2, hs);
+            gs_lds3<LOGC, 64, NT, 3, true, false, kPredW, true>(S, P, lane, lane << LOGC, lane == NT - 1, xN, dh, f1, f2, f3, nullptr, nullptr, hs);
+            // hand-over: what the lane in front left its chunk with (lane 0 has nobody in front: it compares with itself)
+            bool bad = false;
+#pragma unroll
+            for (int q = 0; q < 3; ++q) {
+                const double front = lane_shr1(hs[3 + q], hs[6 + q]);
+                bad |= __builtin_bit_cast(long long, front) != __builtin_bit_cast(long long, hs[3 + q]);
+            }
+            const bool redo = __any(bad && lane < NT) != 0;
+            if (lane == 0) {
+                __hip_atomic_fetch_add(ctr, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (redo) __hip_atomic_fetch_add(ctr + 1, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+            accepted = !redo;
+            if (redo) {
+                wave_sync();
+                if (lane < NT) {
+#pragma unroll
+                    for (int k = 0; k < C; ++k) pl[(k << 6) + lane] = keep[k];
+                }
+                wave_sync();
+            }
+        }
+    }
+    if (!accepted) gs_lds3<LOGC, 64, NT, 3, true>(S, P, lane, lane << LOGC, lane == NT - 1, xN, dh, f1, f2, f3);
     const double e1 = sqrt(wave_total(f1)), e2 = sqrt(wave_total(f2)), e3 = sqrt(wave_total(f3));
     wave_sync();
     if (!(e1 < errorMin) && !(e2 < errorMin)) { err = e3; return true; }
@@ -1901,9 +2039,9 @@ __device__ __forceinline__ double cs_iterate(const MgDesc& D, Atom& A, int l, do
     if (D.fuse3w && iterno == 3 && lc >= 2 && lc <= 4) {
         bool done;
         switch (lc) {
-            case 2:  done = half ? cs_visit3<2, 32>(S, P, dh, errorMin, err) : cs_visit3<2>(S, P, dh, errorMin, err); break;
-            case 3:  done = cs_visit3<3>(S, P, dh, errorMin, err); break;
-            default: done = cs_visit3<4>(S, P, dh, errorMin, err); break;
+            case 2:  done = half ? cs_visit3<2, 32>(S, P, dh, errorMin, err, D.predict, D.pred_ctr) : cs_visit3<2>(S, P, dh, errorMin, err, D.predict, D.pred_ctr); break;
+            case 3:  done = cs_visit3<3>(S, P, dh, errorMin, err, D.predict, D.pred_ctr); break;
+            default: done = cs_visit3<4>(S, P, dh, errorMin, err, D.predict, D.pred_ctr); break;
         }
         if (done) { *nsweeps += 3; return err; }
     }

@@ -233,6 +233,7 @@ int plan_poisson(const PlanInputs& in, PoissonPlan* plan)
     D.fold_lds = K.nofold_lds ? 0 : 1;
     D.fuse3 = K.nofuse3 ? 0 : 1;
     D.fuse3w = (D.fuse3 && !K.nofuse3_wave) ? 1 : 0;
+    D.predict = (D.fuse3w && !P.tol && !K.nopredict) ? (K.predict_fuzz ? 2 : 1) : 0;
     D.fuse_min_logc = K.fuse_min_logc;
     D.fuse_coop = K.nofuse_coop ? 0 : 1;
     D.dbg = K.dbg;

@@ -51,6 +51,8 @@ struct MgDesc {
     int fuse_coop;       // ... and on the levels the G workgroups of an atom share (0: $DFTA_DEBUG POISSON_NOFUSE_COOP)
     int fuse3;    // visits of three sweeps on staged levels of one workgroup run as ONE fused pass (gs_lds3); 0: $DFTA_POISSON_NOFUSE3
     int fuse3w;   // ... and those of the one-wave levels with 257 .. 1025 nodes of the coarse section (cs_visit3); 0: POISSON_NOFUSE3 / POISSON_NOFUSE3_WAVE
+    int predict;  // exact mode: the fused visits of the one-wave levels (cs_visit3) start 32 nodes ahead from predicted values and are checked at the hand-over between the lanes; 0: POISSON_NOPREDICT, 2: POISSON_PREDICT_FUZZ (every prediction spoilt: every visit is repeated)
+    unsigned long long* pred_ctr;   // device: [0] visits checked, [1] visits repeated (set by the solver after the plan is made)
     int nofold;   // DFTA_POISSON_NOFOLD: restriction / prolongation as separate passes even where they could be folded into a staged copy-in
     int fold_lds; // the folded restriction reads the finer level from the staging memory where its visit has just left it (POISSON_NOFOLD_LDS: from global)
     int kcoop;       // levels 0 .. kcoop-1 are swept by all G workgroups together (256 G lanes), the others by workgroup 0
@@ -100,6 +102,7 @@ struct PoissonKnobs {
     bool nostage = false, nostage_wave = false, nostage_shared = false;
     bool nocoarse = false, noxw = false, norc = false;
     bool nofuse3 = false, nofuse3_wave = false, nohalf129 = false;
+    bool nopredict = false, predict_fuzz = false;
     bool nofold = false, nofold_lds = false, nofuse_coop = false;
     int fuse_min_logc = kFuseMinLogC;   // POISSON_FUSE_MIN_LOGC, never below kFuseMinLogC
     int dbg = 0;                 // POISSON_DBG

@@ -244,6 +244,12 @@ int  dfta_poisson_solve_dev(dfta_poisson* p, const int* dZ, const double* dDensi
  * workgroup per atom (bit-identical results), and the solver stays `degraded` to that path; `aborts` counts the solves
  * that had to be repeated.  $DFTA_FAULT_POISSON_MEMBER=1 (tests) makes the last member of every group return at once. */
 int  dfta_poisson_group_info(const dfta_poisson* p, int* G, int* degraded, int* aborts);
+/* Exact mode: the fused three-sweep visits of the 129 .. 1025-node levels start 32 nodes in front of a lane's chunk from PREDICTED values
+ * (affine scan of the sweep's recurrence) and every lane's state is compared bit for bit with what the lane in front computed for the
+ * same nodes; a visit with a mismatch is put back and repeated with the 112-node warm-up from old values, so results
+ * never depend on a prediction.  `checked`: visits that ran that way since the solver was created, `repeated`: those that had to be run
+ * again (either may be NULL).  $DFTA_DEBUG POISSON_NOPREDICT: off (both stay 0); POISSON_PREDICT_FUZZ: every visit repeated. */
+int  dfta_poisson_predict_counts(dfta_poisson* p, unsigned long long* checked, unsigned long long* repeated);
 /* unit-parity hooks on level storage of atom 0 (GaussSeidel / Restrict / Prolong / VCycle,
  * PoissonSolver.cpp:40-64, 110-157; PoissonSolver.h:155-159) */
 int  dfta_poisson_level_size(const dfta_poisson* p, int lvl);
