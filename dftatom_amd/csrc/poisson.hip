@@ -354,6 +354,8 @@ static hipError_t allocate(dfta_poisson* p)
     TRY_HIP(hipMemsetAsync(p->d_src, 0, P.n_level_store * sizeof(double), st));
     TRY_HIP(hipMemsetAsync(p->d_cur, 0, P.n_cur * sizeof(int), st));
     TRY_HIP(hipMemsetAsync(p->d_total_vcycles, 0, sizeof(unsigned long long), st));
+    // every atom's barrier counter: a unit launch clears atom 0's alone, and check_groups reads the abort flag of all of them
+    TRY_HIP(hipMemsetAsync(p->d_group_ctr, 0, P.n_group_ctr * sizeof(unsigned), st));
     return hipStreamSynchronize(st);
 }
 #undef TRY_HIP

@@ -3615,6 +3615,8 @@ __global__ __launch_bounds__(kThreads) void k_poisson_solve_res(const MgDesc* __
     const int N = D.lv[0].n;
     const double* rho = density + (size_t)a * N;
     Counters c{0, 0};
+    // level 0 is a member level here (res_kres >= 1, and the planner makes a grid resident from 16385 nodes on): it is never sequential,
+    // so its source needs no LDS block; the coarse workgroup's sequential levels get theirs through src_of (res_init_coarse)
     if (R.role == 0) {
         for (int l = 0; l < R.kres; ++l) { DFTA_RES_LEVEL(R.logC0 - l, (res_init_level<LC>(D, A, R, l, rho, r, psrc, src_all))) }
         __syncthreads();
@@ -3701,7 +3703,10 @@ __global__ __launch_bounds__(kThreads) void k_poisson_solve(const MgDesc* __rest
         const int i = node_of(L0, idx);
         double s = r[i];
         if (src_all || (i > 0 && i < N - 1)) s *= psrc[i] * rho[i];      // PoissonSolver.h:72-74; uniform grid: every node (PoissonSolver.h:39-40)
-        A.src[L0.off + idx] = s;   // level 0 is never sequential: plain global storage
+        A.src[L0.off + idx] = s;   // global storage: what the chunked sweeps, the unit entries and dfta_poisson_get_level read
+        // grids of <= 65 nodes (3 .. 6 levels): level 0 is sequential too, and initialize() and the sweeps read a sequential
+        // level's source from its LDS block (src_of) -- nothing else fills that block in this kernel
+        if (L0.seq) A.src_of(L0)[idx] = s;
     }
     __syncthreads();
     Counters c{0, 0};
