@@ -19,10 +19,12 @@
 
 #include "bessel_plan.h"
 #include "internal.h"
+#include "radial_device.h"
 
 namespace {
 
 using dfta_bessel::kSeriesTerms;
+using namespace dfta_radial;
 
 constexpr int kBtThreads = 256;
 
@@ -36,9 +38,6 @@ __constant__ double kSeries[dfta_bessel::kLmax + 1][kSeriesTerms] = {DFTA_BROW(1
                                                                      DFTA_BROW(1. / 105., 3), DFTA_BROW(1. / 945., 4)};
 #undef DFTA_BROW
 #undef DFTA_BC
-
-// Simpson 3/8 weight of node i without the factor 3/8 (Integral.h:50-73)
-__device__ __forceinline__ double simpson38_weight(int i, int N) { return (i == 0 || i == N - 1) ? 1. : (i % 3 == 0 ? 2. : 3.); }
 
 // j_l(x), x >= 0, as the header states it; l is the same in every lane
 __device__ __forceinline__ double sph_bessel(int l, double x)
@@ -112,19 +111,14 @@ __global__ __launch_bounds__(kBtThreads) void k_bessel_transform(int N, double h
         }
         i = in; fi = fn; ri = rn; ci = cn;
     }
-    // the tree, per q: lanes of a wave by xor shuffles 32 .. 1, then the four waves as (w0 + w1) + (w2 + w3)
+    // the tree of radial_device.h, per q
 #pragma unroll
     for (int m = 0; m < QB; ++m) {
-        double v = acc[m];
-        for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+        const double v = wave_tree_sum(acc[m]);
         if ((tid & 63) == 0) red[tid >> 6][m] = v;
     }
     __syncthreads();
-    if (tid < nv) {
-        const double sum = (red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid]);
-        constexpr double coef = 3. / 8.;
-        out[(size_t)row * nq + q0 + tid] = (sum * coef) * scale;
-    }
+    if (tid < nv) out[(size_t)row * nq + q0 + tid] = simpson38_finish(waves_join(red[0][tid], red[1][tid], red[2][tid], red[3][tid])) * scale;
 }
 
 // the doubles nearest 4 pi and sqrt(2 / pi)
@@ -142,9 +136,9 @@ int dfta_launch_bessel_transform(dfta_ctx* ctx, const dfta_grid* g, int kind, in
     const int qb = dfta_bessel::pick_qblock(nrow, nq, ctx->num_cu, forced);
     DFTA_REQUIRE(ctx, dfta_bessel::num_blocks(nrow, nq, qb) <= 0x7fffffffL, "Bessel transform: too many (row, q) pairs for one launch");
     const dim3 grid((unsigned)dfta_bessel::num_blocks(nrow, nq, qb)), block(kBtThreads);
-    const double hstep = g->uniform ? g->h : 1.0, scale = kind == DFTA_BT_DENSITY ? kFourPi : kSqrtTwoOverPi;
+    const double hstep = dfta_hstep(g), scale = kind == DFTA_BT_DENSITY ? kFourPi : kSqrtTwoOverPi;
     hipStream_t st = ctx->stream;
-    DFTA_HIP(ctx, hipEventRecord(ctx->ev[0], st));
+    DFTA_HIP(ctx, dfta_timer_start(ctx));
     switch (qb) {
     case 8: hipLaunchKernelGGL(k_bessel_transform<8>, grid, block, 0, st, g->N, hstep, g->d_r.p, g->d_cnst.p, kind, scale, dL, dRows, nq, dQ, dOut); break;
     case 4: hipLaunchKernelGGL(k_bessel_transform<4>, grid, block, 0, st, g->N, hstep, g->d_r.p, g->d_cnst.p, kind, scale, dL, dRows, nq, dQ, dOut); break;
@@ -152,8 +146,7 @@ int dfta_launch_bessel_transform(dfta_ctx* ctx, const dfta_grid* g, int kind, in
     default: hipLaunchKernelGGL(k_bessel_transform<1>, grid, block, 0, st, g->N, hstep, g->d_r.p, g->d_cnst.p, kind, scale, dL, dRows, nq, dQ, dOut); break;
     }
     DFTA_CHECK_LAUNCH(ctx);
-    DFTA_HIP(ctx, hipEventRecord(ctx->ev[1], st));
-    ctx->have_kernel_time = true;
+    DFTA_HIP(ctx, dfta_timer_stop(ctx));
     return DFTA_OK;
 }
 
@@ -162,18 +155,10 @@ int dfta_bessel_scratch::run(dfta_ctx* ctx, const dfta_grid* g, int kind, int nr
 {
     if (nrow <= 0 || nq <= 0) return DFTA_OK;
     hipStream_t st = ctx->stream;
-    if (row_cap < nrow) {                            // first use, or more rows than any call before
-        row_cap = 0;
-        DFTA_HIP(ctx, d_l.alloc(nrow));
-        DFTA_HIP(ctx, d_rows.alloc(nrow));
-        row_cap = nrow;
-    }
-    if (q_cap < nq) {
-        q_cap = 0;
-        DFTA_HIP(ctx, d_q.alloc(nq));
-        q_cap = nq;
-    }
-    if (d_out.n < (size_t)nrow * nq) DFTA_HIP(ctx, d_out.alloc((size_t)nrow * nq));
+    DFTA_HIP(ctx, d_l.reserve(nrow));                // first use, or more rows / q's than any call before
+    DFTA_HIP(ctx, d_rows.reserve(nrow));
+    DFTA_HIP(ctx, d_q.reserve(nq));
+    DFTA_HIP(ctx, d_out.reserve((size_t)nrow * nq));
     DFTA_HIP(ctx, hipMemcpyAsync(d_l.p, l, sizeof(int) * nrow, hipMemcpyHostToDevice, st));
     DFTA_HIP(ctx, hipMemcpyAsync(d_rows.p, rows, sizeof(const double*) * nrow, hipMemcpyHostToDevice, st));
     DFTA_HIP(ctx, hipMemcpyAsync(d_q.p, q, sizeof(double) * nq, hipMemcpyHostToDevice, st));
@@ -197,14 +182,13 @@ int dfta_sph_bessel(dfta_ctx* ctx, int l, size_t n, const double* x, double* out
     for (size_t i = 0; i < n; ++i) DFTA_REQUIRE(ctx, x[i] >= 0. && !std::isinf(x[i]), "dfta_sph_bessel: x must be finite and >= 0");
     hipStream_t st = ctx->stream;
     DevBuf<double> dX, dO;
-    DFTA_HIP(ctx, dX.alloc(n)); DFTA_HIP(ctx, dO.alloc(n));
-    DFTA_HIP(ctx, hipMemcpyAsync(dX.p, x, sizeof(double) * n, hipMemcpyHostToDevice, st));
+    DFTA_HIP(ctx, dO.alloc(n));
+    if (const int rc = dfta_upload_rows(ctx, x, n, &dX)) return rc;
     const unsigned blocks = (unsigned)std::min<size_t>((n + 255) / 256, 4096);
-    DFTA_HIP(ctx, hipEventRecord(ctx->ev[0], st));
+    DFTA_HIP(ctx, dfta_timer_start(ctx));
     hipLaunchKernelGGL(k_sph_bessel, dim3(blocks), dim3(256), 0, st, l, n, dX.p, dO.p);
     DFTA_CHECK_LAUNCH(ctx);
-    DFTA_HIP(ctx, hipEventRecord(ctx->ev[1], st));
-    ctx->have_kernel_time = true;
+    DFTA_HIP(ctx, dfta_timer_stop(ctx));
     DFTA_HIP(ctx, hipMemcpyAsync(out, dO.p, sizeof(double) * n, hipMemcpyDeviceToHost, st));
     DFTA_HIP(ctx, hipStreamSynchronize(st));
     return DFTA_OK;
@@ -224,8 +208,7 @@ int dfta_bessel_transform(dfta_ctx* ctx, const dfta_grid* g, int kind, int nrow,
     const size_t N = g->N;
     DevBuf<double> dF;
     dfta_bessel_scratch sc;
-    DFTA_HIP(ctx, dF.alloc((size_t)nrow * N));
-    DFTA_HIP(ctx, hipMemcpyAsync(dF.p, f, sizeof(double) * nrow * N, hipMemcpyHostToDevice, ctx->stream));
+    if (const int rc = dfta_upload_rows(ctx, f, (size_t)nrow * N, &dF)) return rc;
     std::vector<const double*> rows(nrow);
     for (int a = 0; a < nrow; ++a) rows[a] = dF.p + (size_t)a * N;
     return sc.run(ctx, g, kind, nrow, l, rows.data(), nq, q, out);

@@ -156,6 +156,8 @@ struct DevBuf {
         if (count == 0) return hipSuccess;
         return hipMalloc(reinterpret_cast<void**>(&p), count * sizeof(T));
     }
+    // room for at least count elements: a buffer that is large enough stays (with its contents), otherwise a fresh one of count
+    __attribute__((always_inline)) hipError_t reserve(size_t count) { return (p && n >= count) ? hipSuccess : alloc(count); }
 };
 // owners of an event and of a stream (the holder creates them through .e / .s; null: none)
 struct DevEvent {
@@ -203,6 +205,27 @@ struct dfta_grid {
     DevBuf<double> d_rsrc_own;  // uniform grid: FillR's (Rmax i) / (N-1) (PoissonSolver.cpp:200-210)
     const double* d_rsrc = nullptr;   // the r factor of the Poisson source: d_r, or d_rsrc_own on a uniform grid
 };
+// the step that multiplies cnst[i] in dr/di: h on the uniform grid (cnst is all ones there), 1 on the logarithmic one
+static inline double dfta_hstep(const dfta_grid* g) { return g->uniform ? g->h : 1.0; }
+
+// The bracket of dfta_ctx_last_kernel_ms around the launches of a call, on the context's stream:
+//     DFTA_HIP(ctx, dfta_timer_start(ctx)); ... launches ...; DFTA_HIP(ctx, dfta_timer_stop(ctx));
+static inline hipError_t dfta_timer_start(dfta_ctx* ctx) { return hipEventRecord(ctx->ev[0], ctx->stream); }
+static inline hipError_t dfta_timer_stop(dfta_ctx* ctx)
+{
+    const hipError_t e = hipEventRecord(ctx->ev[1], ctx->stream);
+    if (e == hipSuccess) ctx->have_kernel_time = true;
+    return e;
+}
+
+// the caller's rows (host, count values) into a device buffer made for them, on the context's stream
+template <typename T>
+static inline int dfta_upload_rows(dfta_ctx* ctx, const T* host, size_t count, DevBuf<T>* buf)
+{
+    DFTA_HIP(ctx, buf->alloc(count));
+    if (count) DFTA_HIP(ctx, hipMemcpyAsync(buf->p, host, sizeof(T) * count, hipMemcpyHostToDevice, ctx->stream));
+    return DFTA_OK;
+}
 
 // A pointer that reaches a non-inlined device function has no known address space: the compiler emits FLAT loads and stores, which count
 // against the LDS counter as well and return out of order with it -- every wait for one of them is a wait for ALL of them (`s_waitcnt

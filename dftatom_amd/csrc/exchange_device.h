@@ -5,14 +5,12 @@
 #include <hip/hip_runtime.h>
 
 #include "exchange_plan.h"
+#include "radial_device.h"
 
 namespace dfta_exchange_dev {
 
 constexpr int kPwThreads = 256;
 constexpr int kRedThreads = 256;
-
-// Simpson 3/8 weight of node i without the factor 3/8 (Integral.h:50-73)
-__device__ __forceinline__ double simpson38_weight(int i, int N) { return (i == 0 || i == N - 1) ? 1. : (i % 3 == 0 ? 2. : 3.); }
 
 // node i of a channel: X_a of every shell (written), D and vS (returned).  U, X: the channel's rows; Y: the rows of its y jobs
 __device__ __forceinline__ void pointwise_node(int N, int i, int norb, const double* __restrict__ U, const double* __restrict__ occ,
@@ -48,8 +46,8 @@ __device__ __forceinline__ double kli_node(int N, int i, int norb, int homo, con
     return den > 0. ? vS + acc / den : 0.;
 }
 
-// one quadrature by a workgroup of kRedThreads lanes: lane t adds the weighted terms of the nodes t, t + 256, ... to one accumulator, the
-// lanes of a wave by xor shuffles 32 .. 1, then the four waves as (w0 + w1) + (w2 + w3).  The value (sign of HF included) in lane 0.
+// one quadrature by a workgroup of kRedThreads lanes: lane t adds the weighted terms of the nodes t, t + 256, ... to one accumulator, then
+// the tree of radial_device.h.  The value (sign of HF included) in lane 0.
 __device__ __forceinline__ double reduce_block(int N, double hstep, const double* __restrict__ cnst, const double* __restrict__ ua,
                                                const double* __restrict__ ub, const double* __restrict__ xa, const double* __restrict__ D,
                                                const double* __restrict__ v, int kind, double* part /* LDS, kRedThreads / 64 */)
@@ -57,7 +55,7 @@ __device__ __forceinline__ double reduce_block(int N, double hstep, const double
     const int tid = threadIdx.x;
     double acc = 0.;
     for (int i = tid; i < N; i += kRedThreads) {
-        const double sc = cnst[i] * hstep, w = simpson38_weight(i, N), u = ua[i];
+        const double sc = cnst[i] * hstep, w = dfta_radial::simpson38_weight(i, N), u = ua[i];
         double t;
         if (kind == dfta_exchange::kRedHF) t = (u * xa[i]) * sc;
         else if (kind == dfta_exchange::kRedPair) {
@@ -66,14 +64,12 @@ __device__ __forceinline__ double reduce_block(int N, double hstep, const double
         } else t = ((u * u) * v[i]) * sc;
         acc += w * t;
     }
-    for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
+    acc = dfta_radial::wave_tree_sum(acc);
     if ((tid & 63) == 0) part[tid >> 6] = acc;
     __syncthreads();
     double q = 0.;
     if (tid == 0) {
-        const double sum = (part[0] + part[1]) + (part[2] + part[3]);
-        constexpr double coef = 3. / 8.;
-        q = sum * coef;
+        q = dfta_radial::simpson38_finish(dfta_radial::waves_join(part[0], part[1], part[2], part[3]));
         if (kind == dfta_exchange::kRedHF) q = -q;
     }
     return q;

@@ -165,14 +165,13 @@ extern "C" int dfta_xc_pointwise(dfta_ctx* ctx, int functional, size_t sz, const
     }
     for (int k = 0; k < 6; ++k) if (hout[k]) { DFTA_HIP(ctx, out[k].alloc(sz)); dout[k] = out[k].p; }
     const int blocks = (int)std::min<size_t>((sz + 255) / 256, 2048);
-    DFTA_HIP(ctx, hipEventRecord(ctx->ev[0], st));
+    DFTA_HIP(ctx, dfta_timer_start(ctx));
     if (pol && gga) hipLaunchKernelGGL((k_xc_pointwise<true, true>), dim3(blocks), dim3(256), 0, st, sz, din[0], din[1], din[2], din[3], din[4], dout[0], dout[1], dout[2], dout[3], dout[4], dout[5]);
     else if (pol) hipLaunchKernelGGL((k_xc_pointwise<true, false>), dim3(blocks), dim3(256), 0, st, sz, din[0], din[1], din[2], din[3], din[4], dout[0], dout[1], dout[2], dout[3], dout[4], dout[5]);
     else if (gga) hipLaunchKernelGGL((k_xc_pointwise<false, true>), dim3(blocks), dim3(256), 0, st, sz, din[0], din[1], din[2], din[3], din[4], dout[0], dout[1], dout[2], dout[3], dout[4], dout[5]);
     else hipLaunchKernelGGL((k_xc_pointwise<false, false>), dim3(blocks), dim3(256), 0, st, sz, din[0], din[1], din[2], din[3], din[4], dout[0], dout[1], dout[2], dout[3], dout[4], dout[5]);
     DFTA_CHECK_LAUNCH(ctx);
-    DFTA_HIP(ctx, hipEventRecord(ctx->ev[1], st));
-    ctx->have_kernel_time = true;
+    DFTA_HIP(ctx, dfta_timer_stop(ctx));
     for (int k = 0; k < 6; ++k) if (hout[k] && (pol || (k != 2 && k < 4)))
         DFTA_HIP(ctx, hipMemcpyAsync(hout[k], dout[k], sizeof(double) * sz, hipMemcpyDeviceToHost, st));
     DFTA_HIP(ctx, hipStreamSynchronize(st));
@@ -197,14 +196,13 @@ extern "C" int dfta_xc_radial(dfta_ctx* ctx, const dfta_grid* g, int functional,
         DFTA_HIP(ctx, dB.alloc(sz)); DFTA_HIP(ctx, dVa.alloc(sz)); DFTA_HIP(ctx, dVb.alloc(sz));
         DFTA_HIP(ctx, hipMemcpyAsync(dB.p, nb, sizeof(double) * sz, hipMemcpyHostToDevice, st));
     }
-    DFTA_HIP(ctx, hipEventRecord(ctx->ev[0], st));
+    DFTA_HIP(ctx, dfta_timer_start(ctx));
     int rc;
     if (functional == DFTA_XC_PBE) rc = dfta_launch_pbe_radial(ctx, g, natoms, dA.p, dB.p, dR.p, dVa.p, dVb.p, dE.p, nullptr);
     else if (pol) rc = dfta_launch_pw92_lsda(ctx, dA.p, dB.p, sz, dR.p, dVa.p, dVb.p, dE.p);
     else rc = dfta_launch_pw92_lda(ctx, dA.p, sz, dR.p, dE.p);
     if (rc) return rc;
-    DFTA_HIP(ctx, hipEventRecord(ctx->ev[1], st));
-    ctx->have_kernel_time = true;
+    DFTA_HIP(ctx, dfta_timer_stop(ctx));
     if (res) DFTA_HIP(ctx, hipMemcpyAsync(res, dR.p, sizeof(double) * sz, hipMemcpyDeviceToHost, st));
     if (eexc) DFTA_HIP(ctx, hipMemcpyAsync(eexc, dE.p, sizeof(double) * sz, hipMemcpyDeviceToHost, st));
     if (pol && va) DFTA_HIP(ctx, hipMemcpyAsync(va, dVa.p, sizeof(double) * sz, hipMemcpyDeviceToHost, st));

@@ -193,7 +193,6 @@ int dfta_launch_orbital_matrix(dfta_ctx* ctx, const dfta_grid* g, int norb, cons
 // slater_plan.h: check_jobs); records the launch's time for dfta_ctx_last_kernel_ms
 int dfta_launch_slater_rk(dfta_ctx* ctx, const dfta_grid* g, const double* dU, int njobs, const int* dJobs, double* dR);
 struct dfta_slater_scratch {               // job table and results on the device: empty until the first run, grown as needed
-    int cap = 0;                           // jobs the buffers hold
     DevBuf<int> d_jobs;
     DevBuf<double> d_R;
     // uploads the table (host), launches, copies the njobs results to R (host) and synchronises
@@ -204,8 +203,6 @@ struct dfta_slater_scratch {               // job table and results on the devic
 namespace dfta_exchange { struct ChannelPlan; }
 int dfta_launch_screening_yk(dfta_ctx* ctx, const dfta_grid* g, const double* dU, int njobs, const int* dJobs, double* dY);
 struct dfta_exchange_scratch {             // tables, y rows and the channel's rows on the device: empty until the first run, grown as needed
-    int job_cap = 0, orb_cap = 0, tab_cap = 0;
-    size_t node_cap = 0, row_cap = 0;      // nodes the y rows / the channel's rows were made for
     DevBuf<int> d_jobs, d_first, d_tab, d_red;
     DevBuf<double> d_y;                    // njobs x N: 1 MB per job at 131 073 nodes
     DevBuf<double> d_X, d_rows;            // norb x N; D, vS, vKLI
@@ -223,7 +220,6 @@ struct dfta_exchange_scratch {             // tables, y rows and the channel's r
 int dfta_launch_bessel_transform(dfta_ctx* ctx, const dfta_grid* g, int kind, int nrow, const int* dL, const double* const* dRows, int nq,
                                  const double* dQ, double* dOut);
 struct dfta_bessel_scratch {               // the tables of a transform and its results on the device: empty until the first run, grown as needed
-    int row_cap = 0, q_cap = 0;
     DevBuf<int> d_l;
     DevBuf<const double*> d_rows;
     DevBuf<double> d_q, d_out;

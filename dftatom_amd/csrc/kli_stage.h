@@ -48,12 +48,9 @@ struct dfta_kli_stage {
     int run(dfta_ctx* ctx, const dfta_grid* g, const double* dU, const void* Ebase, size_t Estride, const unsigned char* live, bool first,
             double alpha, double oneMinusAlpha, const Dump* dump = nullptr);
     // in place of the functional's launch: Vexc / va / vb / eexc of every atom that has not finished from vx and the mixed densities, E_x
-    // per atom.  Channels atom-major, nspin per atom.
+    // per atom.  Channels atom-major, nspin per atom.  Under `sic`, AFTER the functional's launch on the mixed densities: adds the SIC
+    // potential to Vexc / va / vb and takes it from eexc; E_SIC per atom
     int assemble(dfta_ctx* ctx, const dfta_grid* g, int lsda, const double* density, const double* dA, const double* dB, const int* fin,
                  double* Vexc, double* va, double* vb, double* eexc);
-    // sic, AFTER the functional's launch on the mixed densities: adds the SIC potential of every atom that has not finished to Vexc / va /
-    // vb and takes it from eexc; E_SIC per atom
-    int assemble_sic(dfta_ctx* ctx, const dfta_grid* g, int lsda, const double* density, const double* dA, const double* dB, const int* fin,
-                     double* Vexc, double* va, double* vb, double* eexc);
     void reset();
 };

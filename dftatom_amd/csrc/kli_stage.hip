@@ -10,14 +10,14 @@
 //                       an element's operations do not depend on that --, back substitution by lane 0; then E_x of the channel, the last
 //                       node with D > 0 and v_raw r there.
 //   k_kli_update        grid (node tile, channel): the KLI pass, the Coulomb tail beyond the last node with D > 0, the mix into vx.
-//   k_kli_assemble      grid (node tile, atom), once per step: Vexc / va / vb / eexc from vx and the mixed densities; E_x of the atom.
+//   k_kli_assemble<false>  grid (node tile, atom), once per step: Vexc / va / vb / eexc from vx and the mixed densities; E_x of the atom.
 // Under DFTA_EXCHANGE_SIC_KLI (dfta_kli_stage::sic) the builder of X_a differs and the rest is shared:
 //   y launch            the diagonal jobs (a, a, 0) alone: one row per shell.
 //   k_sic_pointwise     grid (node tile, channel): rho_a, v_a and eps_a (vwn_device.h: k_vwn_lsda's own arithmetic at (rho_a, 0)),
 //                       X_a = (y0_a + v_a) u_a, D, vS.
-//   k_sic_reduce        k_kli_reduce plus the two quadratures EH_a and EXC_a, the same lane chains and trees.
+//   k_kli_reduce<true, SicRows>  k_kli_reduce<false> plus the two quadratures EH_a and EXC_a, the same lane chains and trees.
 //   k_kli_solve, then k_sic_energy (one thread per channel: E_SIC of the channel in place of E_x, the per-shell table), k_kli_update.
-//   k_sic_assemble      once per step AFTER the functional's launch: adds vx to Vexc / va / vb, takes it from eexc; E_SIC of the atom.
+//   k_kli_assemble<true>  once per step AFTER the functional's launch: adds vx to Vexc / va / vb, takes it from eexc; E_SIC of the atom.
 // Every shape is a function of N alone; no floating-point atomics; no workgroup waits for another: a channel's bits do not depend on the
 // batch, its position in it, the chunking or the run.  Built, as everything here, without FMA contraction: the solve repeats the host
 // solve of exchange_plan.cpp operation by operation.
@@ -58,22 +58,6 @@ __global__ __launch_bounds__(kPwThreads) void k_kli_pointwise(int N, int c0, int
                                       X + (size_t)(ch.u0 - u0) * N, &den, &v);
     D[(size_t)blockIdx.y * N + i] = den;
     vS[(size_t)blockIdx.y * N + i] = v;
-}
-
-// quadrature q0 + blockIdx.x of the batch's table
-__global__ __launch_bounds__(kRedThreads) void k_kli_reduce(int N, double hstep, int q0, int c0, int u0, const Channel* __restrict__ chs,
-                                                            const int* __restrict__ red, const double* __restrict__ cnst,
-                                                            const double* __restrict__ U, const double* __restrict__ X,
-                                                            const double* __restrict__ D, const double* __restrict__ vS, double* __restrict__ out)
-{
-    __shared__ double part[kRedThreads / 64];
-    const int* row = red + (size_t)dfta_kli::kRedInts * (q0 + blockIdx.x);
-    const int kind = row[0], a = row[1], b = row[2], c = row[3];
-    const Channel ch = chs[c];
-    const double* Uc = U + (size_t)ch.u0 * N;
-    const double q = dfta_exchange_dev::reduce_block(N, hstep, cnst, Uc + (size_t)a * N, Uc + (size_t)b * N, X + (size_t)(ch.u0 - u0 + a) * N,
-                                                     D + (size_t)(c - c0) * N, vS + (size_t)(c - c0) * N, kind, part);
-    if (threadIdx.x == 0) out[q0 + blockIdx.x] = q;
 }
 
 // the constants c of channel c0 + blockIdx.x, its HOMO, E_x, last node with D > 0 and v_raw r there
@@ -192,31 +176,6 @@ __global__ __launch_bounds__(kPwThreads) void k_kli_update(int N, int c0, const 
     vx[oc] = first ? v : alpha * vx[oc] + oneMinusAlpha * v;
 }
 
-__global__ __launch_bounds__(kPwThreads) void k_kli_assemble(int N, int lsda, const int* __restrict__ fin, const double* __restrict__ vx,
-                                                             const double* __restrict__ ExCh, const double* __restrict__ density,
-                                                             const double* __restrict__ dA, const double* __restrict__ dB,
-                                                             double* __restrict__ Vexc, double* __restrict__ va, double* __restrict__ vb,
-                                                             double* __restrict__ eexc, double* __restrict__ ExAtom)
-{
-    const int a = blockIdx.y;
-    if (fin[a]) return;                      // a finished atom keeps its potential and its E_x
-    const int i = blockIdx.x * kPwThreads + threadIdx.x;
-    if (i == 0) ExAtom[a] = lsda ? ExCh[2 * a] + ExCh[2 * a + 1] : 2. * ExCh[a];
-    if (i >= N) return;
-    const size_t o = (size_t)a * N + i;
-    double v;
-    if (!lsda) v = vx[o];
-    else {
-        const double x = vx[((size_t)2 * a) * N + i], y = vx[((size_t)2 * a + 1) * N + i];
-        const double rho = density[o];
-        va[o] = x;
-        vb[o] = y;
-        v = rho > 0. ? (dA[o] * x + dB[o] * y) / rho : 0.;
-    }
-    Vexc[o] = v;
-    eexc[o] = -v;
-}
-
 // ---- the self-interaction correction: the builder of X_a, the two energy quadratures, E_SIC and the additive assembly --------------------
 // rho_a, v_a, eps_a, X_a, D, vS of the chunk's channels [c0, c0 + gridDim.y); chunk rows: Y from job j0; vorb, eps, X from orbital row u0
 __global__ __launch_bounds__(kPwThreads) void k_sic_pointwise(int N, int c0, int j0, int u0, const Channel* __restrict__ chs,
@@ -251,13 +210,18 @@ __global__ __launch_bounds__(kPwThreads) void k_sic_pointwise(int N, int c0, int
     vS[(size_t)blockIdx.y * N + i] = den > 0. ? -(num / den) : 0.;
 }
 
-// quadrature q0 + blockIdx.x of the batch's table: the kinds of k_kli_reduce, and EH_a / EXC_a as the kRedS chain on y0_a / eps_a
-__global__ __launch_bounds__(kRedThreads) void k_sic_reduce(int N, double hstep, int q0, int c0, int j0, int u0, const Channel* __restrict__ chs,
+// what the SIC quadratures read beyond the KLI ones: the chunk's y rows from job j0 and eps rows (from orbital row u0)
+struct SicRows { int j0; const double* Y; const double* eps; };
+
+// quadrature q0 + blockIdx.x of the batch's table: vbarHF_a, vbarS_a, S_ab; kSic: also EH_a / EXC_a as the kRedS chain on y0_a / eps_a.
+// Rows is one SicRows under kSic and nothing otherwise: the KLI instance has the thirteen arguments it uses and compiles to the code it
+// had (three unused arguments measured 0.5 us on the stage of a Ne step)
+template <bool kSic, typename... Rows>
+__global__ __launch_bounds__(kRedThreads) void k_kli_reduce(int N, double hstep, int q0, int c0, int u0, const Channel* __restrict__ chs,
                                                             const int* __restrict__ red, const double* __restrict__ cnst,
                                                             const double* __restrict__ U, const double* __restrict__ X,
                                                             const double* __restrict__ D, const double* __restrict__ vS,
-                                                            const double* __restrict__ Y, const double* __restrict__ eps,
-                                                            double* __restrict__ out)
+                                                            double* __restrict__ out, Rows... rows)
 {
     __shared__ double part[kRedThreads / 64];
     const int* row = red + (size_t)dfta_kli::kRedInts * (q0 + blockIdx.x);
@@ -266,11 +230,14 @@ __global__ __launch_bounds__(kRedThreads) void k_sic_reduce(int N, double hstep,
     const double* Uc = U + (size_t)ch.u0 * N;
     const double* v = vS + (size_t)(c - c0) * N;
     int shape = kind;
-    if (kind == dfta_kli::kRedSicH) { v = Y + (size_t)(ch.job0 - j0 + a) * N; shape = dfta_exchange::kRedS; }
-    else if (kind == dfta_kli::kRedSicXC) { v = eps + (size_t)(ch.u0 - u0 + a) * N; shape = dfta_exchange::kRedS; }
+    if constexpr (kSic) {
+        const SicRows sic = (rows, ...);
+        if (kind == dfta_kli::kRedSicH) { v = sic.Y + (size_t)(ch.job0 - sic.j0 + a) * N; shape = dfta_exchange::kRedS; }
+        else if (kind == dfta_kli::kRedSicXC) { v = sic.eps + (size_t)(ch.u0 - u0 + a) * N; shape = dfta_exchange::kRedS; }
+    }
     double q = dfta_exchange_dev::reduce_block(N, hstep, cnst, Uc + (size_t)a * N, Uc + (size_t)b * N, X + (size_t)(ch.u0 - u0 + a) * N,
                                                D + (size_t)(c - c0) * N, v, shape, part);
-    if (kind == dfta_kli::kRedSicH) q = 0.5 * q;
+    if (kSic && kind == dfta_kli::kRedSicH) q = 0.5 * q;
     if (threadIdx.x == 0) out[q0 + blockIdx.x] = q;
 }
 
@@ -294,14 +261,18 @@ __global__ void k_sic_energy(int c0, int nc, const Channel* __restrict__ chs, co
     ExCh[c0 + k] = -acc;
 }
 
-__global__ __launch_bounds__(kPwThreads) void k_sic_assemble(int N, int lsda, const int* __restrict__ fin, const double* __restrict__ vx,
+// once per step, grid (node tile, atom): vx and E_x of the atom into the SCF's arrays.  kAdd false (KLI, in place of the functional's
+// launch): Vexc / va / vb = the potential, eexc = -Vexc.  kAdd true (SIC, after the functional's launch): added to Vexc / va / vb, taken
+// from eexc
+template <bool kAdd>
+__global__ __launch_bounds__(kPwThreads) void k_kli_assemble(int N, int lsda, const int* __restrict__ fin, const double* __restrict__ vx,
                                                              const double* __restrict__ ExCh, const double* __restrict__ density,
                                                              const double* __restrict__ dA, const double* __restrict__ dB,
                                                              double* __restrict__ Vexc, double* __restrict__ va, double* __restrict__ vb,
                                                              double* __restrict__ eexc, double* __restrict__ ExAtom)
 {
     const int a = blockIdx.y;
-    if (fin[a]) return;                      // a finished atom keeps its potential and its E_SIC
+    if (fin[a]) return;                      // a finished atom keeps its potential and its E_x / E_SIC
     const int i = blockIdx.x * kPwThreads + threadIdx.x;
     if (i == 0) ExAtom[a] = lsda ? ExCh[2 * a] + ExCh[2 * a + 1] : 2. * ExCh[a];
     if (i >= N) return;
@@ -311,12 +282,12 @@ __global__ __launch_bounds__(kPwThreads) void k_sic_assemble(int N, int lsda, co
     else {
         const double x = vx[((size_t)2 * a) * N + i], y = vx[((size_t)2 * a + 1) * N + i];
         const double rho = density[o];
-        va[o] = va[o] + x;
-        vb[o] = vb[o] + y;
+        va[o] = kAdd ? va[o] + x : x;
+        vb[o] = kAdd ? vb[o] + y : y;
         t = rho > 0. ? (dA[o] * x + dB[o] * y) / rho : 0.;
     }
-    Vexc[o] = Vexc[o] + t;
-    eexc[o] = eexc[o] - t;
+    Vexc[o] = kAdd ? Vexc[o] + t : t;
+    eexc[o] = kAdd ? eexc[o] - t : -t;
 }
 
 }  // namespace
@@ -384,7 +355,7 @@ int dfta_kli_stage::run(dfta_ctx* ctx, const dfta_grid* g, const double* dU, con
                         bool first, double alpha, double oneMinusAlpha, const Dump* dump)
 {
     hipStream_t st = ctx->stream;
-    const double hstep = g->uniform ? g->h : 1.0;
+    const double hstep = dfta_hstep(g);
     const int nblk = (N + kPwThreads - 1) / kPwThreads;
     double* dD = d_DvS.p;
     double* dvS = d_DvS.p + (size_t)caps.chans * N;
@@ -402,17 +373,18 @@ int dfta_kli_stage::run(dfta_ctx* ctx, const dfta_grid* g, const double* dU, con
             hipLaunchKernelGGL(k_kli_pointwise, dim3(nblk, nc), dim3(kPwThreads), 0, st, N, c0, a.job0, a.u0, d_ch.p, dU, d_occ.p, d_first.p, d_tab.p,
                                d_coef.p, d_y.p, d_X.p, dD, dvS);
             DFTA_CHECK_LAUNCH(ctx);
-            hipLaunchKernelGGL(k_kli_reduce, dim3(nred), dim3(kRedThreads), 0, st, N, hstep, a.red0, c0, a.u0, d_ch.p, d_red.p, g->d_cnst.p, dU, d_X.p,
-                               dD, dvS, d_redout.p);
-            DFTA_CHECK_LAUNCH(ctx);
         } else {
             hipLaunchKernelGGL(k_sic_pointwise, dim3(nblk, nc), dim3(kPwThreads), 0, st, N, c0, a.job0, a.u0, d_ch.p, dU, d_occ.p, g->d_r.p, d_y.p,
                                dfta_vwn_cx(), dfta_vwn_cbrt2(), d_vorb.p, d_eps.p, d_X.p, dD, dvS);
             DFTA_CHECK_LAUNCH(ctx);
-            hipLaunchKernelGGL(k_sic_reduce, dim3(nred), dim3(kRedThreads), 0, st, N, hstep, a.red0, c0, a.job0, a.u0, d_ch.p, d_red.p, g->d_cnst.p,
-                               dU, d_X.p, dD, dvS, d_y.p, d_eps.p, d_redout.p);
-            DFTA_CHECK_LAUNCH(ctx);
         }
+        if (!sic)
+            hipLaunchKernelGGL(k_kli_reduce<false>, dim3(nred), dim3(kRedThreads), 0, st, N, hstep, a.red0, c0, a.u0, d_ch.p, d_red.p, g->d_cnst.p, dU,
+                               d_X.p, dD, dvS, d_redout.p);
+        else
+            hipLaunchKernelGGL((k_kli_reduce<true, SicRows>), dim3(nred), dim3(kRedThreads), 0, st, N, hstep, a.red0, c0, a.u0, d_ch.p, d_red.p, g->d_cnst.p, dU,
+                               d_X.p, dD, dvS, d_redout.p, SicRows{a.job0, d_y.p, d_eps.p});
+        DFTA_CHECK_LAUNCH(ctx);
         hipLaunchKernelGGL(k_kli_solve, dim3(nc), dim3(kSolveThreads), 0, st, N, c0, d_ch.p, d_occ.p, static_cast<const char*>(Ebase), Estride,
                            d_redout.p, g->d_r.p, dU, dD, dvS, d_c.p, d_vbarHF.p, d_homo.p, d_ExCh.p, d_ilast.p, d_tail.p, d_status.p);
         DFTA_CHECK_LAUNCH(ctx);
@@ -444,17 +416,8 @@ int dfta_kli_stage::run(dfta_ctx* ctx, const dfta_grid* g, const double* dU, con
 int dfta_kli_stage::assemble(dfta_ctx* ctx, const dfta_grid* g, int lsda, const double* density, const double* dA, const double* dB,
                              const int* fin, double* Vexc, double* va, double* vb, double* eexc)
 {
-    hipLaunchKernelGGL(k_kli_assemble, dim3((N + kPwThreads - 1) / kPwThreads, natoms), dim3(kPwThreads), 0, ctx->stream, N, lsda, fin, d_vx.p,
-                       d_ExCh.p, density, dA, dB, Vexc, va, vb, eexc, d_ExAtom.p);
-    DFTA_CHECK_LAUNCH(ctx);
-    return DFTA_OK;
-}
-
-int dfta_kli_stage::assemble_sic(dfta_ctx* ctx, const dfta_grid* g, int lsda, const double* density, const double* dA, const double* dB,
-                                 const int* fin, double* Vexc, double* va, double* vb, double* eexc)
-{
-    hipLaunchKernelGGL(k_sic_assemble, dim3((N + kPwThreads - 1) / kPwThreads, natoms), dim3(kPwThreads), 0, ctx->stream, N, lsda, fin, d_vx.p,
-                       d_ExCh.p, density, dA, dB, Vexc, va, vb, eexc, d_ExAtom.p);
+    hipLaunchKernelGGL(sic ? k_kli_assemble<true> : k_kli_assemble<false>, dim3((N + kPwThreads - 1) / kPwThreads, natoms), dim3(kPwThreads), 0,
+                       ctx->stream, N, lsda, fin, d_vx.p, d_ExCh.p, density, dA, dB, Vexc, va, vb, eexc, d_ExAtom.p);
     DFTA_CHECK_LAUNCH(ctx);
     return DFTA_OK;
 }
@@ -466,75 +429,40 @@ double dfta_kli_budget_mb()
 }
 
 // ---- the stage on caller-supplied channels (host pointers) ---------------------------------------------------------------------------
-extern "C" {
+namespace {
 
-int dfta_kli_channels(dfta_ctx* ctx, const dfta_grid* g, int nch, const int* norb, const int* l, const double* occ, const double* E,
-                      const double* u, int first_step, double alpha, double* vx_inout, double* v_raw, double* vbarHF, double* c, int* homo,
-                      double* Ex)
+// what dfta_sic_channels returns beyond dfta_kli_channels (any may be null): y0, vorb, eps, X of every shell (rows of N), D and vS of every
+// channel, EH and EXC per shell, vbarS per shell and M per channel from the quadratures
+struct SicOutputs { double *y0, *vorb, *eps, *X, *D, *vS, *EH, *EXC, *vbarS, *M; };
+
+// both entries: the checks, one stage made for the call, the uploads, the run between the events of dfta_ctx_last_kernel_ms (the whole
+// stage), the downloads.  sic: null for dfta_kli_channels
+int run_channels(dfta_ctx* ctx, const dfta_grid* g, int nch, const int* norb, const int* l, const double* occ, const double* E, const double* u,
+                 int first_step, double alpha, double* vx_inout, double* v_raw, double* vbarHF, double* c, int* homo, double* Ex,
+                 const SicOutputs* sic)
 {
     if (!ctx || !g) return DFTA_ERR_INVALID;
     DFTA_ENTER(ctx);
-    DFTA_REQUIRE(ctx, nch >= 0, "dfta_kli_channels: nch");
+    DFTA_REQUIRE(ctx, nch >= 0, sic ? "dfta_sic_channels: nch" : "dfta_kli_channels: nch");
     if (nch == 0) return DFTA_OK;
-    DFTA_REQUIRE(ctx, norb, "dfta_kli_channels: norb");
-    DFTA_REQUIRE(ctx, alpha >= 0 && alpha <= 1, "dfta_kli_channels: alpha");
+    DFTA_REQUIRE(ctx, norb, sic ? "dfta_sic_channels: norb" : "dfta_kli_channels: norb");
+    DFTA_REQUIRE(ctx, alpha >= 0 && alpha <= 1, sic ? "dfta_sic_channels: alpha" : "dfta_kli_channels: alpha");
     long total = 0;
     for (int k = 0; k < nch; ++k) total += norb[k] > 0 ? norb[k] : 0;
-    DFTA_REQUIRE(ctx, total == 0 || (l && occ && E && u), "dfta_kli_channels: l / occ / E / u");
-    DFTA_REQUIRE(ctx, first_step || vx_inout, "dfta_kli_channels: a later step mixes into vx_inout");
+    DFTA_REQUIRE(ctx, total == 0 || (l && occ && E && u), sic ? "dfta_sic_channels: l / occ / E / u" : "dfta_kli_channels: l / occ / E / u");
+    DFTA_REQUIRE(ctx, first_step || vx_inout,
+                 sic ? "dfta_sic_channels: a later step mixes into vx_inout" : "dfta_kli_channels: a later step mixes into vx_inout");
     dfta_kli_stage stage;
-    int rc = stage.create(ctx, g, nch, norb, l, occ, nullptr, 0, dfta_kli_budget_mb());
-    if (rc) return rc;
-    hipStream_t st = ctx->stream;
-    const size_t N = g->N, no = stage.plan.norb_total;
-    DevBuf<double> dU, dE;
-    DFTA_HIP(ctx, dU.alloc(std::max<size_t>(no * N, 1)));
-    DFTA_HIP(ctx, dE.alloc(std::max<size_t>(no, 1)));
-    if (no) {
-        DFTA_HIP(ctx, hipMemcpyAsync(dU.p, u, sizeof(double) * no * N, hipMemcpyHostToDevice, st));
-        DFTA_HIP(ctx, hipMemcpyAsync(dE.p, E, sizeof(double) * no, hipMemcpyHostToDevice, st));
-    }
-    if (!first_step) DFTA_HIP(ctx, hipMemcpyAsync(stage.d_vx.p, vx_inout, sizeof(double) * nch * N, hipMemcpyHostToDevice, st));
-    DFTA_HIP(ctx, hipEventRecord(ctx->ev[0], st));     // dfta_ctx_last_kernel_ms: the whole stage
-    rc = stage.run(ctx, g, dU.p, dE.p, sizeof(double), nullptr, first_step != 0, alpha, 1. - alpha);
-    if (rc) return rc;
-    DFTA_HIP(ctx, hipEventRecord(ctx->ev[1], st));
-    ctx->have_kernel_time = true;
-    if (vx_inout) DFTA_HIP(ctx, hipMemcpyAsync(vx_inout, stage.d_vx.p, sizeof(double) * nch * N, hipMemcpyDeviceToHost, st));
-    if (v_raw) DFTA_HIP(ctx, hipMemcpyAsync(v_raw, stage.d_vraw.p, sizeof(double) * nch * N, hipMemcpyDeviceToHost, st));
-    if (vbarHF && no) DFTA_HIP(ctx, hipMemcpyAsync(vbarHF, stage.d_vbarHF.p, sizeof(double) * no, hipMemcpyDeviceToHost, st));
-    if (c && no) DFTA_HIP(ctx, hipMemcpyAsync(c, stage.d_c.p, sizeof(double) * no, hipMemcpyDeviceToHost, st));
-    if (homo) DFTA_HIP(ctx, hipMemcpyAsync(homo, stage.d_homo.p, sizeof(int) * nch, hipMemcpyDeviceToHost, st));
-    if (Ex) DFTA_HIP(ctx, hipMemcpyAsync(Ex, stage.d_ExCh.p, sizeof(double) * nch, hipMemcpyDeviceToHost, st));
-    DFTA_HIP(ctx, hipStreamSynchronize(st));
-    return DFTA_OK;
-}
-
-int dfta_sic_channels(dfta_ctx* ctx, const dfta_grid* g, int nch, const int* norb, const int* l, const double* occ, const double* E,
-                      const double* u, int first_step, double alpha, double* vx_inout, double* y0, double* vorb, double* eps, double* X,
-                      double* D, double* vS, double* v_raw, double* vbar, double* c, double* EH, double* EXC, int* homo, double* Esic,
-                      double* vbarS, double* M)
-{
-    if (!ctx || !g) return DFTA_ERR_INVALID;
-    DFTA_ENTER(ctx);
-    DFTA_REQUIRE(ctx, nch >= 0, "dfta_sic_channels: nch");
-    if (nch == 0) return DFTA_OK;
-    DFTA_REQUIRE(ctx, norb, "dfta_sic_channels: norb");
-    DFTA_REQUIRE(ctx, alpha >= 0 && alpha <= 1, "dfta_sic_channels: alpha");
-    long total = 0;
-    for (int k = 0; k < nch; ++k) total += norb[k] > 0 ? norb[k] : 0;
-    DFTA_REQUIRE(ctx, total == 0 || (l && occ && E && u), "dfta_sic_channels: l / occ / E / u");
-    DFTA_REQUIRE(ctx, first_step || vx_inout, "dfta_sic_channels: a later step mixes into vx_inout");
-    dfta_kli_stage stage;
-    int rc = stage.create(ctx, g, nch, norb, l, occ, nullptr, 0, dfta_kli_budget_mb(), true);
+    int rc = stage.create(ctx, g, nch, norb, l, occ, nullptr, 0, dfta_kli_budget_mb(), sic != nullptr);
     if (rc) return rc;
     hipStream_t st = ctx->stream;
     const size_t N = g->N, no = stage.plan.norb_total;
     DevBuf<double> dU, dE, dRows[4], dChan[2];       // rows: y0, vorb, eps, X of every shell; D, vS of every channel
     DFTA_HIP(ctx, dU.alloc(std::max<size_t>(no * N, 1)));
     DFTA_HIP(ctx, dE.alloc(std::max<size_t>(no, 1)));
-    double* hostRows[4] = {y0, vorb, eps, X};
-    double* hostChan[2] = {D, vS};
+    double* hostRows[4] = {nullptr, nullptr, nullptr, nullptr};
+    double* hostChan[2] = {nullptr, nullptr};
+    if (sic) { hostRows[0] = sic->y0; hostRows[1] = sic->vorb; hostRows[2] = sic->eps; hostRows[3] = sic->X; hostChan[0] = sic->D; hostChan[1] = sic->vS; }
     for (int k = 0; k < 4; ++k)
         if (hostRows[k] && no) DFTA_HIP(ctx, dRows[k].alloc(no * N));
     for (int k = 0; k < 2; ++k)
@@ -547,28 +475,33 @@ int dfta_sic_channels(dfta_ctx* ctx, const dfta_grid* g, int nch, const int* nor
         DFTA_HIP(ctx, hipMemcpyAsync(dE.p, E, sizeof(double) * no, hipMemcpyHostToDevice, st));
     }
     if (!first_step) DFTA_HIP(ctx, hipMemcpyAsync(stage.d_vx.p, vx_inout, sizeof(double) * nch * N, hipMemcpyHostToDevice, st));
-    dfta_kli_stage::Dump dump = {dRows[0].p, dRows[1].p, dRows[2].p, dRows[3].p, dChan[0].p, dChan[1].p};
-    DFTA_HIP(ctx, hipEventRecord(ctx->ev[0], st));     // dfta_ctx_last_kernel_ms: the whole stage
-    rc = stage.run(ctx, g, dU.p, dE.p, sizeof(double), nullptr, first_step != 0, alpha, 1. - alpha, &dump);
+    const dfta_kli_stage::Dump dump = {dRows[0].p, dRows[1].p, dRows[2].p, dRows[3].p, dChan[0].p, dChan[1].p};
+    DFTA_HIP(ctx, dfta_timer_start(ctx));
+    rc = stage.run(ctx, g, dU.p, dE.p, sizeof(double), nullptr, first_step != 0, alpha, 1. - alpha, sic ? &dump : nullptr);
     if (rc) return rc;
-    DFTA_HIP(ctx, hipEventRecord(ctx->ev[1], st));
-    ctx->have_kernel_time = true;
-    for (int k = 0; k < 4; ++k)
-        if (dRows[k].p) DFTA_HIP(ctx, hipMemcpyAsync(hostRows[k], dRows[k].p, sizeof(double) * no * N, hipMemcpyDeviceToHost, st));
-    for (int k = 0; k < 2; ++k)
-        if (dChan[k].p) DFTA_HIP(ctx, hipMemcpyAsync(hostChan[k], dChan[k].p, sizeof(double) * nch * N, hipMemcpyDeviceToHost, st));
-    if (vx_inout) DFTA_HIP(ctx, hipMemcpyAsync(vx_inout, stage.d_vx.p, sizeof(double) * nch * N, hipMemcpyDeviceToHost, st));
-    if (v_raw) DFTA_HIP(ctx, hipMemcpyAsync(v_raw, stage.d_vraw.p, sizeof(double) * nch * N, hipMemcpyDeviceToHost, st));
-    if (vbar && no) DFTA_HIP(ctx, hipMemcpyAsync(vbar, stage.d_vbarHF.p, sizeof(double) * no, hipMemcpyDeviceToHost, st));
-    if (c && no) DFTA_HIP(ctx, hipMemcpyAsync(c, stage.d_c.p, sizeof(double) * no, hipMemcpyDeviceToHost, st));
-    if (EH && no) DFTA_HIP(ctx, hipMemcpyAsync(EH, stage.d_EH.p, sizeof(double) * no, hipMemcpyDeviceToHost, st));
-    if (EXC && no) DFTA_HIP(ctx, hipMemcpyAsync(EXC, stage.d_EXC.p, sizeof(double) * no, hipMemcpyDeviceToHost, st));
-    if (homo) DFTA_HIP(ctx, hipMemcpyAsync(homo, stage.d_homo.p, sizeof(int) * nch, hipMemcpyDeviceToHost, st));
-    if (Esic) DFTA_HIP(ctx, hipMemcpyAsync(Esic, stage.d_ExCh.p, sizeof(double) * nch, hipMemcpyDeviceToHost, st));
-    std::vector<double> red((vbarS || M) ? stage.plan.nred() : 0);
-    if (!red.empty()) DFTA_HIP(ctx, hipMemcpyAsync(red.data(), stage.d_redout.p, sizeof(double) * red.size(), hipMemcpyDeviceToHost, st));
+    DFTA_HIP(ctx, dfta_timer_stop(ctx));
+    auto down = [&](auto* host, const auto* dev, size_t count) {
+        return host && count ? hipMemcpyAsync(host, dev, sizeof(*host) * count, hipMemcpyDeviceToHost, st) : hipSuccess;
+    };
+    for (int k = 0; k < 4; ++k) DFTA_HIP(ctx, down(dRows[k].p ? hostRows[k] : nullptr, dRows[k].p, no * N));
+    for (int k = 0; k < 2; ++k) DFTA_HIP(ctx, down(hostChan[k], dChan[k].p, (size_t)nch * N));
+    DFTA_HIP(ctx, down(vx_inout, stage.d_vx.p, (size_t)nch * N));
+    DFTA_HIP(ctx, down(v_raw, stage.d_vraw.p, (size_t)nch * N));
+    DFTA_HIP(ctx, down(vbarHF, stage.d_vbarHF.p, no));
+    DFTA_HIP(ctx, down(c, stage.d_c.p, no));
+    DFTA_HIP(ctx, down(homo, stage.d_homo.p, (size_t)nch));
+    DFTA_HIP(ctx, down(Ex, stage.d_ExCh.p, (size_t)nch));
+    std::vector<double> red;
+    if (sic) {
+        DFTA_HIP(ctx, down(sic->EH, stage.d_EH.p, no));
+        DFTA_HIP(ctx, down(sic->EXC, stage.d_EXC.p, no));
+        red.assign((sic->vbarS || sic->M) ? stage.plan.nred() : 0, 0.);
+        DFTA_HIP(ctx, down(red.data(), stage.d_redout.p, red.size()));
+    }
     DFTA_HIP(ctx, hipStreamSynchronize(st));
     if (!red.empty()) {
+        double* vbarS = sic->vbarS;
+        double* M = sic->M;
         size_t m0 = 0;
         for (const dfta_kli::Channel& ch : stage.plan.ch) {
             const int n = ch.norb;
@@ -584,6 +517,26 @@ int dfta_sic_channels(dfta_ctx* ctx, const dfta_grid* g, int nch, const int* nor
         }
     }
     return DFTA_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int dfta_kli_channels(dfta_ctx* ctx, const dfta_grid* g, int nch, const int* norb, const int* l, const double* occ, const double* E,
+                      const double* u, int first_step, double alpha, double* vx_inout, double* v_raw, double* vbarHF, double* c, int* homo,
+                      double* Ex)
+{
+    return run_channels(ctx, g, nch, norb, l, occ, E, u, first_step, alpha, vx_inout, v_raw, vbarHF, c, homo, Ex, nullptr);
+}
+
+int dfta_sic_channels(dfta_ctx* ctx, const dfta_grid* g, int nch, const int* norb, const int* l, const double* occ, const double* E,
+                      const double* u, int first_step, double alpha, double* vx_inout, double* y0, double* vorb, double* eps, double* X,
+                      double* D, double* vS, double* v_raw, double* vbar, double* c, double* EH, double* EXC, int* homo, double* Esic,
+                      double* vbarS, double* M)
+{
+    const SicOutputs sic = {y0, vorb, eps, X, D, vS, EH, EXC, vbarS, M};
+    return run_channels(ctx, g, nch, norb, l, occ, E, u, first_step, alpha, vx_inout, v_raw, vbar, c, homo, Esic, &sic);
 }
 
 }  // extern "C"

@@ -1379,7 +1379,7 @@ int LevelSolver::finish_wavefunctions(RunPlan& p)
         if (!p.nfrozen) keep = nullptr;
     }
     if (normalise) {
-        hipLaunchKernelGGL(k_normalize, dim3(njobs), dim3(kNormThreads), 0, st, d_Psi.p, d_Q.p, N, g->d_eh, g->d_cnst, keep, g->uniform ? g->h : 1.0, integ_rule);
+        hipLaunchKernelGGL(k_normalize, dim3(njobs), dim3(kNormThreads), 0, st, d_Psi.p, d_Q.p, N, g->d_eh, g->d_cnst, keep, dfta_hstep(g), integ_rule);
         DFTA_CHECK_LAUNCH(ctx);
     }
     if (p.dNewDensity) {

@@ -18,6 +18,7 @@
 #include <cmath>
 
 #include "internal.h"
+#include "radial_device.h"
 
 namespace {
 
@@ -71,15 +72,14 @@ __device__ __forceinline__ void gram_chunk(int lsda, int N, int a, int chunk, in
     if (H == 0) return;
 #pragma unroll
     for (int d = 0; d < nd; ++d) {
-        double s = acc[d];
-        for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
+        const double s = dfta_radial::wave_tree_sum(acc[d]);         // the tree of radial_device.h, per dot product
         if ((threadIdx.x & 63) == 0) lds[(threadIdx.x >> 6) * kAndersonDots + d] = s;
     }
     __syncthreads();
     if ((int)threadIdx.x < nd) {
         const int d = threadIdx.x;
         slab[((size_t)a * nchunks + chunk) * kAndersonDots + d] =
-            (lds[d] + lds[kAndersonDots + d]) + (lds[2 * kAndersonDots + d] + lds[3 * kAndersonDots + d]);
+            dfta_radial::waves_join(lds[d], lds[kAndersonDots + d], lds[2 * kAndersonDots + d], lds[3 * kAndersonDots + d]);
     }
 }
 
@@ -241,7 +241,7 @@ int dfta_launch_anderson_mix(dfta_ctx* ctx, const dfta_grid* g, dfta_anderson* a
 {
     const int N = g->N, nchunks = dfta_anderson_chunks(N);
     hipStream_t st = ctx->stream;
-    hipLaunchKernelGGL(k_anderson_gram, dim3(nchunks, natoms), dim3(kGramThreads), 0, st, lsda, N, an->m, an->warmup, g->uniform ? g->h : 1.0,
+    hipLaunchKernelGGL(k_anderson_gram, dim3(nchunks, natoms), dim3(kGramThreads), 0, st, lsda, N, an->m, an->warmup, dfta_hstep(g),
                        g->d_fpr2, g->d_cnst, newDensity, density, dA, dB, an->ring.p, an->slab.p, an->state.p, fin);
     DFTA_CHECK_LAUNCH(ctx);
     hipLaunchKernelGGL(k_anderson_solve, dim3(natoms), dim3(64), 0, st, nchunks, an->m, an->warmup, an->slab.p, an->gamma.p, an->state.p, fin);

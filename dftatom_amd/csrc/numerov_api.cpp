@@ -179,11 +179,10 @@ extern "C" int dfta_numerov_sweeps(dfta_ctx* ctx, const dfta_grid* g, int kind, 
     SweepTrials tr{};
     tr.E = dE; tr.limit = dLim; tr.start = bv.start; tr.us = bv.us; tr.us1 = bv.us1;
     tr.count = dCount; tr.u0 = dU0; tr.trip = dTrip;
-    DFTA_HIP(ctx, hipEventRecord(ctx->ev[0], st));
+    DFTA_HIP(ctx, dfta_timer_start(ctx));
     rc = dfta_launch_sweep(ctx, g, kind, tb.tables(), tb.blocks(), tr, nullptr, nullptr, 0);
     if (rc) return rc;
-    DFTA_HIP(ctx, hipEventRecord(ctx->ev[1], st));
-    ctx->have_kernel_time = true;
+    DFTA_HIP(ctx, dfta_timer_stop(ctx));
     std::vector<int> hCount(ntrials), hTrip(ntrials), hStart(ntrials);
     std::vector<double> hU0(ntrials);
     DFTA_HIP(ctx, hipMemcpyAsync(hCount.data(), dCount.p, ntrials * sizeof(int), hipMemcpyDeviceToHost, st));
@@ -360,7 +359,6 @@ int potential_scan_sweeps(dfta_potential* p, const StageLayout& L, int kind, int
 {
     dfta_ctx* ctx = p->ctx;
     const dfta_grid* g = p->g;
-    hipStream_t st = ctx->stream;
     if (!p->scan_built) {
         int rc = dfta_scan_tables_create(ctx, g, 4, &p->scan);
         if (rc) return rc;
@@ -376,13 +374,12 @@ int potential_scan_sweeps(dfta_potential* p, const StageLayout& L, int kind, int
     int rc = potential_stage_in(p, L);
     if (rc) return rc;
     void *di = p->dIn.p, *dn = p->dOut.p;
-    DFTA_HIP(ctx, hipEventRecord(ctx->ev[0], st));
+    DFTA_HIP(ctx, dfta_timer_start(ctx));
     rc = dfta_launch_scan_sweeps(ctx, g, kind, ntrials, p->scan, stage_ptr<int>(di, L.blk_slot), stage_ptr<double>(di, L.E), stage_ptr<int>(di, L.limit),
                                  stage_ptr<int>(dn, L.count), stage_ptr<double>(dn, L.u0), stage_ptr<int>(dn, L.start_out), stage_ptr<int>(dn, L.trip),
                                  stage_ptr<int>(dn, L.bad));
     if (rc) return rc;
-    DFTA_HIP(ctx, hipEventRecord(ctx->ev[1], st));
-    ctx->have_kernel_time = true;
+    DFTA_HIP(ctx, dfta_timer_stop(ctx));
     return potential_stage_out(p, L, nullptr, ntrials, kind, nullptr, count_out, u0_out, start_out, trip_out, anybad);
 }
 }  // namespace
@@ -436,7 +433,6 @@ extern "C" int dfta_potential_sweeps(dfta_potential* p, int kind, int sweep_mode
     DFTA_REQUIRE(ctx, kind != DFTA_SWEEP_ZERO || u0_out, "ZERO needs u0_out");
     DFTA_REQUIRE(ctx, sweep_mode == DFTA_SWEEPS_EXACT || (sweep_mode == DFTA_SWEEPS_TOLERANCE && dfta_scan_supported(g)), "sweep mode / grid");
     if (ntrials == 0) return DFTA_OK;
-    hipStream_t st = ctx->stream;
     int rc = potential_scratch(p, ntrials);
     if (rc) return rc;
     StageLayout L;
@@ -466,11 +462,10 @@ extern "C" int dfta_potential_sweeps(dfta_potential* p, int kind, int sweep_mode
     tr.E = stage_ptr<double>(di, L.E); tr.us = stage_ptr<double>(di, L.us); tr.us1 = stage_ptr<double>(di, L.us1);
     tr.limit = stage_ptr<int>(di, L.limit); tr.start = stage_ptr<int>(di, L.start);
     tr.count = stage_ptr<int>(dn, L.count); tr.u0 = stage_ptr<double>(dn, L.u0); tr.trip = stage_ptr<int>(dn, L.trip);
-    DFTA_HIP(ctx, hipEventRecord(ctx->ev[0], st));
+    DFTA_HIP(ctx, dfta_timer_start(ctx));
     rc = dfta_launch_sweep(ctx, g, kind, p->tables(), blocks, tr, nullptr, nullptr, 0);
     if (rc) return rc;
-    DFTA_HIP(ctx, hipEventRecord(ctx->ev[1], st));
-    ctx->have_kernel_time = true;
+    DFTA_HIP(ctx, dfta_timer_stop(ctx));
     return potential_stage_out(p, L, G.order.data(), ntrials, kind, h.start, count_out, u0_out, start_out, trip_out, nullptr);
 }
 

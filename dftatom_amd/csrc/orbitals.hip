@@ -19,6 +19,7 @@
 #include <cmath>
 
 #include "internal.h"
+#include "radial_device.h"
 
 namespace {
 
@@ -31,8 +32,7 @@ constexpr int kMatThreads = 256;
 constexpr int kMatTile = 128;                        // nodes of every orbital in LDS at a time: 32 orbitals x 128 nodes = 32 KB
 constexpr int kMatChunk = 512;                       // nodes per workgroup: the chunking is a function of N alone
 
-// Simpson 3/8 weight of node i without the factor 3/8 (Integral.h:50-73)
-__device__ __forceinline__ double simpson38_weight(int i, int N) { return (i == 0 || i == N - 1) ? 1. : (i % 3 == 0 ? 2. : 3.); }
+using namespace dfta_radial;
 
 __global__ __launch_bounds__(kPropThreads) void k_orbital_properties(int N, double hstep, const double* __restrict__ r,
                                                                      const double* __restrict__ cnst, const int* __restrict__ l,
@@ -93,11 +93,10 @@ __global__ __launch_bounds__(kPropThreads) void k_orbital_properties(int N, doub
             __syncthreads();
         }
     }
-    // the tree: lanes of a wave by xor shuffles 32 .. 1, then the four waves as (w0 + w1) + (w2 + w3)
+    // the tree of radial_device.h, per quantity
 #pragma unroll
     for (int c = 0; c < 7; ++c) {
-        double v = acc[c];
-        for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+        const double v = wave_tree_sum(acc[c]);
         if ((tid & 63) == 0) red[tid >> 6][c] = v;
     }
     for (int off = 32; off > 0; off >>= 1) {
@@ -109,9 +108,7 @@ __global__ __launch_bounds__(kPropThreads) void k_orbital_properties(int N, doub
     __syncthreads();
     double* __restrict__ out = props + (size_t)orb * kProps;
     if (tid < 7) {
-        const double sum = (red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid]);
-        constexpr double coef = 3. / 8.;
-        const double q = sum * coef;
+        const double q = simpson38_finish(waves_join(red[0][tid], red[1][tid], red[2][tid], red[3][tid]));
         out[tid == 5 ? DFTA_ORB_T : (tid == 6 ? DFTA_ORB_RM3 : tid)] = tid == 5 ? 0.5 * q : q;
     } else if (tid == 7) {
         double b = red[0][7];
@@ -188,8 +185,7 @@ __global__ __launch_bounds__(kMatThreads) void k_orbital_matrix(int N, int norb,
         if (p >= npair) continue;
         double sum = 0.;
         for (int c = 0; c < nchunks; ++c) sum += vs[(size_t)c * npair + p];
-        constexpr double coef = 3. / 8.;
-        const double m = sum * coef;
+        const double m = simpson38_finish(sum);
         M[(size_t)pa[q] * norb + pb[q]] = m;
         M[(size_t)pb[q] * norb + pa[q]] = m;
     }
@@ -201,13 +197,11 @@ __global__ __launch_bounds__(kMatThreads) void k_orbital_matrix(int N, int norb,
 int dfta_launch_orbital_properties(dfta_ctx* ctx, const dfta_grid* g, int norb, const int* dL, const double* dU, double* dProps)
 {
     if (norb <= 0) return DFTA_OK;
-    hipStream_t st = ctx->stream;
-    DFTA_HIP(ctx, hipEventRecord(ctx->ev[0], st));
-    hipLaunchKernelGGL(k_orbital_properties, dim3(norb), dim3(kPropThreads), 0, st, g->N, g->uniform ? g->h : 1.0, g->d_r.p, g->d_cnst.p, dL, dU,
+    DFTA_HIP(ctx, dfta_timer_start(ctx));
+    hipLaunchKernelGGL(k_orbital_properties, dim3(norb), dim3(kPropThreads), 0, ctx->stream, g->N, dfta_hstep(g), g->d_r.p, g->d_cnst.p, dL, dU,
                        dProps);
     DFTA_CHECK_LAUNCH(ctx);
-    DFTA_HIP(ctx, hipEventRecord(ctx->ev[1], st));
-    ctx->have_kernel_time = true;
+    DFTA_HIP(ctx, dfta_timer_stop(ctx));
     return DFTA_OK;
 }
 
@@ -218,7 +212,7 @@ int dfta_launch_orbital_matrix(dfta_ctx* ctx, const dfta_grid* g, int norb, cons
     if (norb <= 0) return DFTA_OK;
     const int N = g->N, nchunks = dfta_orbital_matrix_chunks(N);
     const size_t lds = sizeof(double) * ((size_t)kMatTile * norb + kMatTile);
-    const double hstep = g->uniform ? g->h : 1.0;
+    const double hstep = dfta_hstep(g);
     hipStream_t st = ctx->stream;
     if (k == 0) hipLaunchKernelGGL(k_orbital_matrix<0>, dim3(nchunks), dim3(kMatThreads), lds, st, N, norb, hstep, g->d_r.p, g->d_cnst.p, dU, dSlab, dTicket, dM);
     else if (k == 1) hipLaunchKernelGGL(k_orbital_matrix<1>, dim3(nchunks), dim3(kMatThreads), lds, st, N, norb, hstep, g->d_r.p, g->d_cnst.p, dU, dSlab, dTicket, dM);
@@ -256,13 +250,12 @@ int dfta_orbital_properties(dfta_ctx* ctx, const dfta_grid* g, int norb, const i
     DFTA_REQUIRE(ctx, l && u && props && g->N >= 5, "dfta_orbital_properties arguments");
     for (int k = 0; k < norb; ++k) DFTA_REQUIRE(ctx, l[k] >= 0, "dfta_orbital_properties: l < 0");
     hipStream_t st = ctx->stream;
-    const size_t sz = (size_t)norb * g->N;
     DevBuf<double> dU, dP;
     DevBuf<int> dL;
-    DFTA_HIP(ctx, dU.alloc(sz)); DFTA_HIP(ctx, dP.alloc((size_t)norb * kProps)); DFTA_HIP(ctx, dL.alloc(norb));
-    DFTA_HIP(ctx, hipMemcpyAsync(dU.p, u, sizeof(double) * sz, hipMemcpyHostToDevice, st));
-    DFTA_HIP(ctx, hipMemcpyAsync(dL.p, l, sizeof(int) * norb, hipMemcpyHostToDevice, st));
-    const int rc = dfta_launch_orbital_properties(ctx, g, norb, dL.p, dU.p, dP.p);
+    DFTA_HIP(ctx, dP.alloc((size_t)norb * kProps));
+    int rc = dfta_upload_rows(ctx, u, (size_t)norb * g->N, &dU);
+    if (!rc) rc = dfta_upload_rows(ctx, l, (size_t)norb, &dL);
+    if (!rc) rc = dfta_launch_orbital_properties(ctx, g, norb, dL.p, dU.p, dP.p);
     if (rc) return rc;
     DFTA_HIP(ctx, hipMemcpyAsync(props, dP.p, sizeof(double) * norb * kProps, hipMemcpyDeviceToHost, st));
     DFTA_HIP(ctx, hipStreamSynchronize(st));
@@ -278,14 +271,11 @@ int dfta_orbital_matrix(dfta_ctx* ctx, const dfta_grid* g, int norb, const doubl
     if (norb == 0) return DFTA_OK;
     DFTA_REQUIRE(ctx, u && M, "dfta_orbital_matrix arguments");
     hipStream_t st = ctx->stream;
-    const size_t sz = (size_t)norb * g->N;
     DevBuf<double> dU;
     dfta_orbital_scratch sc;
-    DFTA_HIP(ctx, dU.alloc(sz));
     int rc = dfta_orbital_scratch_create(ctx, g, norb, &sc);
-    if (rc) return rc;
-    DFTA_HIP(ctx, hipMemcpyAsync(dU.p, u, sizeof(double) * sz, hipMemcpyHostToDevice, st));
-    rc = dfta_launch_orbital_matrix(ctx, g, norb, dU.p, k, sc.slab.p, sc.ticket.p, sc.M.p);
+    if (!rc) rc = dfta_upload_rows(ctx, u, (size_t)norb * g->N, &dU);
+    if (!rc) rc = dfta_launch_orbital_matrix(ctx, g, norb, dU.p, k, sc.slab.p, sc.ticket.p, sc.M.p);
     if (rc) return rc;
     DFTA_HIP(ctx, hipMemcpyAsync(M, sc.M.p, sizeof(double) * norb * norb, hipMemcpyDeviceToHost, st));
     DFTA_HIP(ctx, hipStreamSynchronize(st));

@@ -457,11 +457,10 @@ int dfta_poisson_solve(dfta_poisson* p, const int* Z, const double* density, dou
     DFTA_HIP(ctx, dRho.alloc((size_t)B * N)); DFTA_HIP(ctx, dU.alloc((size_t)B * N));
     DFTA_HIP(ctx, hipMemcpyAsync(dZ.p, ne.data(), sizeof(double) * B, hipMemcpyHostToDevice, st));
     DFTA_HIP(ctx, hipMemcpyAsync(dRho.p, density, sizeof(double) * (size_t)B * N, hipMemcpyHostToDevice, st));
-    DFTA_HIP(ctx, hipEventRecord(ctx->ev[0], st));
+    DFTA_HIP(ctx, dfta_timer_start(ctx));
     int rc = dfta_poisson_solve_launch(p, dZ.p, dRho.p, dU.p, dVc.p, dErr.p, nullptr);
     if (rc) return rc;
-    DFTA_HIP(ctx, hipEventRecord(ctx->ev[1], st));
-    ctx->have_kernel_time = true;
+    DFTA_HIP(ctx, dfta_timer_stop(ctx));
     rc = dfta_poisson_finish(p, dZ.p, dRho.p, dU.p, dVc.p, dErr.p, nullptr);
     if (rc) return rc;
     DFTA_HIP(ctx, hipMemcpyAsync(U, dU.p, sizeof(double) * (size_t)B * N, hipMemcpyDeviceToHost, st));

@@ -5,6 +5,7 @@
 
 #include "internal.h"
 #include "ordered_sum.h"
+#include "radial_device.h"
 
 namespace {
 
@@ -32,11 +33,12 @@ __global__ __launch_bounds__(256) void k_integrate_simpson38_par(const double* _
         const double x = v[i];
         if (i % 3 == 0) s2 += x; else s1 += x;
     }
-    for (int off = 32; off > 0; off >>= 1) { s1 += __shfl_xor(s1, off); s2 += __shfl_xor(s2, off); }
+    s1 = dfta_radial::wave_tree_sum(s1);            // the tree of radial_device.h, per sum
+    s2 = dfta_radial::wave_tree_sum(s2);
     if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6] = s1; red[4 + (threadIdx.x >> 6)] = s2; }
     __syncthreads();
     if (threadIdx.x == 0) {
-        const double sum1 = (red[0] + red[1]) + (red[2] + red[3]), sum2 = (red[4] + red[5]) + (red[6] + red[7]);
+        const double sum1 = dfta_radial::waves_join(red[0], red[1], red[2], red[3]), sum2 = dfta_radial::waves_join(red[4], red[5], red[6], red[7]);
         double sum = v[0] + v[n - 1];
         sum += 3. * sum1 + 2. * sum2;
         constexpr double coef = 3. / 8.;

@@ -217,8 +217,9 @@ __global__ void k_scatter_rows(const double* __restrict__ src, const int* __rest
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < N; i += gridDim.x * blockDim.x) d[i] = s[i];
 }
 
-// DFTA_EXCHANGE_KLI, in place of scf_xc: the exchange stage on the step's orbitals for every live channel, then Vexc / va / vb / eexc
-static int scf_kli(dfta_scf* s)
+// The exchange stage on the step's orbitals for every live channel, then its potential into Vexc / va / vb / eexc: under
+// DFTA_EXCHANGE_KLI in place of scf_xc, under DFTA_EXCHANGE_SIC_KLI after scf_xc and on top of the functional's (the stage knows which)
+static int scf_exchange_stage(dfta_scf* s)
 {
     const int nspin = s->nspin;
     s->h_live_ch.resize((size_t)s->nV);
@@ -229,22 +230,6 @@ static int scf_kli(dfta_scf* s)
                         1. - s->alpha);
     if (rc) return rc;
     return s->kli.assemble(s->ctx, s->g, s->lsda, s->d_density.p, s->d_dA.p, s->d_dB.p, s->d_fin.p, s->d_Vexc.p, s->d_va.p, s->d_vb.p, s->d_eexc.p);
-}
-
-// DFTA_EXCHANGE_SIC_KLI, after scf_xc: the SIC stage on the step's orbitals for every live channel, then its potential on top of the
-// functional's Vexc / va / vb / eexc
-static int scf_sic(dfta_scf* s)
-{
-    const int nspin = s->nspin;
-    s->h_live_ch.resize((size_t)s->nV);
-    for (int a = 0; a < s->natoms; ++a)
-        for (int sp = 0; sp < nspin; ++sp) s->h_live_ch[(size_t)a * nspin + sp] = s->h_atoms[a].finished ? 0 : 1;
-    const dfta::Job* jobs = s->solver.d_jobs.p;
-    int rc = s->kli.run(s->ctx, s->g, s->solver.d_Psi.p, &jobs->E, sizeof(dfta::Job), s->h_live_ch.data(), s->steps_done == 1, s->alpha,
-                        1. - s->alpha);
-    if (rc) return rc;
-    return s->kli.assemble_sic(s->ctx, s->g, s->lsda, s->d_density.p, s->d_dA.p, s->d_dB.p, s->d_fin.p, s->d_Vexc.p, s->d_va.p, s->d_vb.p,
-                               s->d_eexc.p);
 }
 
 static int scf_xc(dfta_scf* s)
@@ -564,10 +549,10 @@ int dfta_scf_step(dfta_scf* s, dfta_step_stats* stats)
     dfta_range r_tail("dfta: XC + integrands + ordered integrals + energies");
     const bool kli = s->exchange_mode == DFTA_EXCHANGE_KLI;
     const bool sic = s->exchange_mode == DFTA_EXCHANGE_SIC_KLI;
-    rc = kli ? scf_kli(s) : scf_xc(s);
+    rc = kli ? scf_exchange_stage(s) : scf_xc(s);
     if (rc) return rc;
     if (sic) {
-        rc = scf_sic(s);
+        rc = scf_exchange_stage(s);
         if (rc) return rc;
     }
     hipLaunchKernelGGL(k_tail, grid, block, 0, st, s->d_atoms.p, s->lsda, N, g->d_r, g->d_cnst, s->d_density.p, s->d_dA.p, s->d_dB.p, s->d_U.p,
@@ -577,9 +562,9 @@ int dfta_scf_step(dfta_scf* s, dfta_step_stats* stats)
     // (tolerance mode of the sweeps: the two sums of Simpson 3/8 in parallel, as the normalisation integral of scan_match takes them --
     // 0.44 ms of ordered additions per step otherwise; the energies move by a few 1e-16 relative)
     if (s->solver.sweep_mode == DFTA_SWEEPS_TOLERANCE && s->solver.integ_rule == DFTA_INT_SIMPSON38 && !dfta_knob("SCF_ORDERED_SUMS"))
-        rc = dfta_launch_integrate_simpson38_parallel(ctx, g->uniform ? g->h : 1.0, s->d_integrands, N, natoms * 5, (size_t)N, s->d_integrals);
+        rc = dfta_launch_integrate_simpson38_parallel(ctx, dfta_hstep(g), s->d_integrands, N, natoms * 5, (size_t)N, s->d_integrals);
     else
-        rc = dfta_launch_integrate_ordered(ctx, s->solver.integ_rule, g->uniform ? g->h : 1.0, s->d_integrands, N, natoms * 5, (size_t)N, s->d_integrals);
+        rc = dfta_launch_integrate_ordered(ctx, s->solver.integ_rule, dfta_hstep(g), s->d_integrands, N, natoms * 5, (size_t)N, s->d_integrals);
     if (rc) return rc;
     hipLaunchKernelGGL(k_energies, dim3((natoms + 63) / 64), dim3(64), 0, st, s->d_atoms.p, natoms, s->solver.d_jobs.p, s->solver.d_occ.p, s->d_integrals.p,
                        s->d_records.p, s->d_fin.p, kli || sic ? s->kli.d_ExAtom.p : nullptr);

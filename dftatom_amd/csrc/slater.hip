@@ -17,6 +17,7 @@
 #include <algorithm>
 
 #include "internal.h"
+#include "radial_device.h"
 #include "slater_plan.h"
 
 namespace {
@@ -28,28 +29,7 @@ constexpr int kSlBefore = 3;                         // nodes kept in front of a
 constexpr int kSlSlots = kSlTile + kSlBefore + 1;    // slot q of the running tile [t0, t0 + kSlTile) holds node t0 - kSlBefore + q
 constexpr int kSlArrays = 6;
 enum { kGX, kGY, kPX, kPY, kInv, kSc };
-
-// Simpson 3/8 weight of node i without the factor 3/8 (Integral.h:50-73)
-__device__ __forceinline__ double simpson38_weight(int i, int N) { return (i == 0 || i == N - 1) ? 1. : (i % 3 == 0 ? 2. : 3.); }
-
-// the increment d_i of Z at node i, 1 <= i <= N-1, from the slots around q (the header states these orders)
-__device__ __forceinline__ double increment(const double* g, int q, int i, int N)
-{
-    if (i == 1) return (((9. * g[q - 1] + 19. * g[q]) - 5. * g[q + 1]) + g[q + 2]) / 24.;
-    if (i == N - 1) return (((g[q - 3] - 5. * g[q - 2]) + 19. * g[q - 1]) + 9. * g[q]) / 24.;
-    return (13. * (g[q - 1] + g[q]) - (g[q - 2] + g[q + 1])) / 24.;
-}
-
-// inclusive scan of v over the 64 lanes of a wave: six levels, lane t takes lane t - off
-__device__ __forceinline__ double wave_scan(double v, int lane)
-{
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const double o = __shfl_up(v, off);
-        if (lane >= off) v += o;
-    }
-    return v;
-}
+using namespace dfta_radial;
 
 __global__ __launch_bounds__(kSlThreads) void k_slater_rk(int N, double hstep, const double* __restrict__ r, const double* __restrict__ cnst,
                                                           const double* __restrict__ U, const int* __restrict__ jobs,
@@ -86,15 +66,13 @@ __global__ __launch_bounds__(kSlThreads) void k_slater_rk(int N, double hstep, c
             const double b1 = y1 == y0 ? b0 : (y1 == x0 ? a0 : (y1 == x1 ? a1 : uy1[i]));
             py = b0 * b1;
         }
-        const double ri = r[i], sc = cnst[i] * hstep;
-        double p = 1.;
-        for (int m = 0; m < k; ++m) p = p * ri;      // r^k: k multiplications from 1
-        v[kGX] = (p * px) * sc;
-        v[kGY] = (p * py) * sc;
+        const NodeFactors f = node_factors(k, r[i], cnst[i], hstep, i);
+        v[kGX] = (f.p * px) * f.sc;
+        v[kGY] = (f.p * py) * f.sc;
         v[kPX] = px;
         v[kPY] = py;
-        v[kInv] = i > 0 ? 1. / (p * ri) : 0.;        // r_0 = 0: the outer term is 0 there
-        v[kSc] = sc;
+        v[kInv] = f.inv;
+        v[kSc] = f.sc;
     };
 
     if (tid < kSlBefore)
@@ -110,32 +88,14 @@ __global__ __launch_bounds__(kSlThreads) void k_slater_rk(int N, double hstep, c
     double carryX = 0., carryY = 0., acc = 0.;
     for (int t0 = 0; t0 < N; t0 += kSlTile) {
         const int q0 = kSlBefore + kSlPer * tid, i0 = t0 + kSlPer * tid;
-        // the lane's chain of increments, both streams
+        // the scan of the tile (radial_device.h), both streams through one barrier
         double lx[kSlPer], ly[kSlPer];
-        double tx = 0., ty = 0.;
-#pragma unroll
-        for (int j = 0; j < kSlPer; ++j) {
-            const int i = i0 + j;
-            const bool in = i >= 1 && i < N;
-            const double dx = in ? increment(s[kGX], q0 + j, i, N) : 0.;
-            const double dy = (in && !same) ? increment(s[kGY], q0 + j, i, N) : 0.;
-            tx = j == 0 ? dx : tx + dx;
-            ty = j == 0 ? dy : ty + dy;
-            lx[j] = tx;
-            ly[j] = ty;
-        }
-        // the lanes' totals across the wave, the waves' totals through LDS
-        const double ix = wave_scan(tx, lane), iy = wave_scan(ty, lane);
-        double ex = __shfl_up(ix, 1), ey = __shfl_up(iy, 1);
-        if (lane == 0) ex = ey = 0.;
-        if (lane == 63) { wtot[0][wave] = ix; wtot[1][wave] = iy; }      // read before the next tile's: two barriers lie between
+        const double tx = chain_up(s[kGX], q0, i0, N, true, lx), ty = chain_up(s[kGY], q0, i0, N, !same, ly);
+        const LanePrefix px = wave_prefix_up(tx, lane), py = wave_prefix_up(ty, lane);
+        if (lane == 63) { wtot[0][wave] = px.inc; wtot[1][wave] = py.inc; }      // read before the next tile's: two barriers lie between
         __syncthreads();
-        const double* wx = wtot[0];
-        const double* wy = wtot[1];
-        const double offx = wave == 0 ? 0. : (wave == 1 ? wx[0] : (wave == 2 ? wx[0] + wx[1] : (wx[0] + wx[1]) + wx[2]));
-        const double offy = wave == 0 ? 0. : (wave == 1 ? wy[0] : (wave == 2 ? wy[0] + wy[1] : (wy[0] + wy[1]) + wy[2]));
-        const double totx = ((wx[0] + wx[1]) + wx[2]) + wx[3], toty = ((wy[0] + wy[1]) + wy[2]) + wy[3];
-        const double bx = offx + ex, by = offy + ey;
+        const TileSums wx = waves_chain_up(wtot[0], wave), wy = waves_chain_up(wtot[1], wave);
+        const double bx = wx.off + px.ex, by = wy.off + py.ex;
 #pragma unroll
         for (int j = 0; j < kSlPer; ++j) {
             const int i = i0 + j, q = q0 + j;
@@ -145,8 +105,8 @@ __global__ __launch_bounds__(kSlThreads) void k_slater_rk(int N, double hstep, c
             const double S = s[kPX][q] * zy + s[kPY][q] * zx;
             acc += simpson38_weight(i, N) * ((S * s[kInv][q]) * s[kSc][q]);
         }
-        carryX = carryX + totx;
-        carryY = carryY + toty;
+        carryX = carryX + wx.tot;
+        carryY = carryY + wy.tot;
         const int t1 = t0 + kSlTile;
         if (t1 < N) {
             double keep[kSlArrays];
@@ -165,15 +125,10 @@ __global__ __launch_bounds__(kSlThreads) void k_slater_rk(int N, double hstep, c
             __syncthreads();
         }
     }
-    // the tree: lanes of a wave by xor shuffles 32 .. 1, then the four waves as (w0 + w1) + (w2 + w3)
-    for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
+    acc = wave_tree_sum(acc);                        // the tree of radial_device.h
     if (lane == 0) red[wave] = acc;
     __syncthreads();
-    if (tid == 0) {
-        const double sum = (red[0] + red[1]) + (red[2] + red[3]);
-        constexpr double coef = 3. / 8.;
-        R[blockIdx.x] = sum * coef;
-    }
+    if (tid == 0) R[blockIdx.x] = simpson38_finish(waves_join(red[0], red[1], red[2], red[3]));
 }
 
 }  // namespace
@@ -181,12 +136,10 @@ __global__ __launch_bounds__(kSlThreads) void k_slater_rk(int N, double hstep, c
 int dfta_launch_slater_rk(dfta_ctx* ctx, const dfta_grid* g, const double* dU, int njobs, const int* dJobs, double* dR)
 {
     if (njobs <= 0) return DFTA_OK;
-    hipStream_t st = ctx->stream;
-    DFTA_HIP(ctx, hipEventRecord(ctx->ev[0], st));
-    hipLaunchKernelGGL(k_slater_rk, dim3(njobs), dim3(kSlThreads), 0, st, g->N, g->uniform ? g->h : 1.0, g->d_r.p, g->d_cnst.p, dU, dJobs, dR);
+    DFTA_HIP(ctx, dfta_timer_start(ctx));
+    hipLaunchKernelGGL(k_slater_rk, dim3(njobs), dim3(kSlThreads), 0, ctx->stream, g->N, dfta_hstep(g), g->d_r.p, g->d_cnst.p, dU, dJobs, dR);
     DFTA_CHECK_LAUNCH(ctx);
-    DFTA_HIP(ctx, hipEventRecord(ctx->ev[1], st));
-    ctx->have_kernel_time = true;
+    DFTA_HIP(ctx, dfta_timer_stop(ctx));
     return DFTA_OK;
 }
 
@@ -194,12 +147,8 @@ int dfta_slater_scratch::run(dfta_ctx* ctx, const dfta_grid* g, const double* dU
 {
     if (njobs <= 0) return DFTA_OK;
     hipStream_t st = ctx->stream;
-    if (cap < njobs) {                               // first use, or a longer table than any before
-        cap = 0;
-        DFTA_HIP(ctx, d_jobs.alloc((size_t)njobs * dfta_slater::kJobInts));
-        DFTA_HIP(ctx, d_R.alloc(njobs));
-        cap = njobs;
-    }
+    DFTA_HIP(ctx, d_jobs.reserve((size_t)njobs * dfta_slater::kJobInts));     // first use, or a longer table than any before
+    DFTA_HIP(ctx, d_R.reserve(njobs));
     DFTA_HIP(ctx, hipMemcpyAsync(d_jobs.p, jobs, sizeof(int) * dfta_slater::kJobInts * njobs, hipMemcpyHostToDevice, st));
     const int rc = dfta_launch_slater_rk(ctx, g, dU, njobs, d_jobs.p, d_R.p);
     if (rc) return rc;
@@ -220,11 +169,9 @@ int dfta_slater_rk(dfta_ctx* ctx, const dfta_grid* g, int norb, const double* u,
     DFTA_REQUIRE(ctx, u && jobs && R, "dfta_slater_rk arguments");
     DFTA_REQUIRE(ctx, g->N >= 5, "dfta_slater_rk: the grid needs 5 nodes");
     if (const char* msg = dfta_slater::check_jobs(norb, njobs, jobs)) DFTA_REQUIRE(ctx, false, msg);
-    const size_t sz = (size_t)norb * g->N;
     DevBuf<double> dU;
     dfta_slater_scratch sc;
-    DFTA_HIP(ctx, dU.alloc(sz));
-    DFTA_HIP(ctx, hipMemcpyAsync(dU.p, u, sizeof(double) * sz, hipMemcpyHostToDevice, ctx->stream));
+    if (const int rc = dfta_upload_rows(ctx, u, (size_t)norb * g->N, &dU)) return rc;
     return sc.run(ctx, g, dU.p, njobs, jobs, R);
 }
 

@@ -167,11 +167,10 @@ extern "C" int dfta_vwn_lda(dfta_ctx* ctx, const double* n, size_t sz, double* v
     DevBuf<double> dN, dV, dE;
     DFTA_HIP(ctx, dN.alloc(sz)); DFTA_HIP(ctx, dV.alloc(sz)); DFTA_HIP(ctx, dE.alloc(sz));
     DFTA_HIP(ctx, hipMemcpyAsync(dN.p, n, sizeof(double) * sz, hipMemcpyHostToDevice, st));
-    DFTA_HIP(ctx, hipEventRecord(ctx->ev[0], st));
+    DFTA_HIP(ctx, dfta_timer_start(ctx));
     int rc = dfta_launch_vwn_lda(ctx, dN.p, sz, dV.p, dE.p);
     if (rc) return rc;
-    DFTA_HIP(ctx, hipEventRecord(ctx->ev[1], st));
-    ctx->have_kernel_time = true;
+    DFTA_HIP(ctx, dfta_timer_stop(ctx));
     if (vexc) DFTA_HIP(ctx, hipMemcpyAsync(vexc, dV.p, sizeof(double) * sz, hipMemcpyDeviceToHost, st));
     if (eexcdif) DFTA_HIP(ctx, hipMemcpyAsync(eexcdif, dE.p, sizeof(double) * sz, hipMemcpyDeviceToHost, st));
     DFTA_HIP(ctx, hipStreamSynchronize(st));
@@ -191,11 +190,10 @@ extern "C" int dfta_vwn_lsda(dfta_ctx* ctx, const double* na, const double* nb, 
     DFTA_HIP(ctx, dVa.alloc(sz)); DFTA_HIP(ctx, dVb.alloc(sz)); DFTA_HIP(ctx, dE.alloc(sz));
     DFTA_HIP(ctx, hipMemcpyAsync(dA.p, na, sizeof(double) * sz, hipMemcpyHostToDevice, st));
     DFTA_HIP(ctx, hipMemcpyAsync(dB.p, nb, sizeof(double) * sz, hipMemcpyHostToDevice, st));
-    DFTA_HIP(ctx, hipEventRecord(ctx->ev[0], st));
+    DFTA_HIP(ctx, dfta_timer_start(ctx));
     int rc = dfta_launch_vwn_lsda(ctx, dA.p, dB.p, sz, dR.p, dVa.p, dVb.p, dE.p);
     if (rc) return rc;
-    DFTA_HIP(ctx, hipEventRecord(ctx->ev[1], st));
-    ctx->have_kernel_time = true;
+    DFTA_HIP(ctx, dfta_timer_stop(ctx));
     if (vexc) DFTA_HIP(ctx, hipMemcpyAsync(vexc, dR.p, sizeof(double) * sz, hipMemcpyDeviceToHost, st));
     if (va) DFTA_HIP(ctx, hipMemcpyAsync(va, dVa.p, sizeof(double) * sz, hipMemcpyDeviceToHost, st));
     if (vb) DFTA_HIP(ctx, hipMemcpyAsync(vb, dVb.p, sizeof(double) * sz, hipMemcpyDeviceToHost, st));
