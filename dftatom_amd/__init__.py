@@ -41,6 +41,9 @@ EXCHANGE_FUNCTIONAL, EXCHANGE_KLI = 0, 1   # dfta_scf_set_exchange: v_xc of the 
 EXCHANGE_SIC_KLI = 2                       # ... / VWN plus the Perdew-Zunger self-interaction correction as one KLI potential per channel
 BT_DENSITY, BT_ORBITAL = 0, 1         # DFTA_BT_*: kinds of bessel_transform
 BESSEL_LMAX = 4                        # DFTA_BESSEL_LMAX: largest order of sph_bessel / bessel_transform
+CONT_FREE, CONT_WKB = 0, 1             # DFTA_CONT_*: normalisation of continuum(): Riccati matching (short range) / WKB amplitude (any tail)
+CONT_MAX_PARTNERS = 16                 # DFTA_CONT_MAX_PARTNERS: partners of one list
+CONT_NONFINITE, CONT_STEP, CONT_WKB_TAIL = 1, 2, 4      # status bits of a continuum trial
 
 c_dp = C.POINTER(C.c_double)
 c_ip = C.POINTER(C.c_int)
@@ -187,6 +190,11 @@ SIGNATURES = {
     "dfta_bessel_transform": (C.c_int, [vp, vp, C.c_int, C.c_int, c_ip, c_dp, C.c_int, c_dp, c_dp]),
     "dfta_scf_form_factors": (C.c_int, [vp, C.c_int, c_dp, c_dp]),
     "dfta_scf_momentum_orbitals": (C.c_int, [vp, C.c_int, c_dp, c_dp]),
+    "dfta_continuum": (C.c_int, [vp, vp, C.c_int, C.c_int, c_dp, C.c_int, c_ip, c_ip, c_dp, c_ip, C.c_int, c_dp, C.c_int, C.c_int, c_ip, c_ip,
+                                 c_ip, c_dp, c_ip, c_dp, c_dp, c_ip, c_dp, c_dp]),
+    "dfta_scf_continuum": (C.c_int, [vp, C.c_int, C.c_int, c_ip, c_ip, c_ip, c_dp, c_ip, C.c_int, c_dp, c_ip, c_dp, c_dp, c_ip, c_dp, c_ip,
+                                     c_dp]),
+    "dfta_scf_photoionization": (C.c_int, [vp, C.c_int, C.c_int, c_dp, C.c_int, c_dp, c_dp]),
 }
 
 _lib = None
@@ -769,6 +777,49 @@ def bessel_transform(ctx, grid, kind, l, f, q):
     return out
 
 
+def _cont_outputs(nt, N, want_sums, want_rows):
+    out = {"logderiv": np.zeros(nt), "nodes": np.zeros(nt, np.int32), "delta": np.zeros(nt), "scale": np.zeros(nt),
+           "status": np.zeros(nt, np.int32)}
+    if want_sums:
+        out["sums"] = np.zeros((nt, CONT_MAX_PARTNERS))
+    if want_rows:
+        out["rows"] = np.zeros((nt, N))
+    return out
+
+
+def continuum(ctx, grid, V, l, E, m=None, vidx=None, norm=CONT_FREE, partners=None, power=0, lists=None, trial_list=None, want_rows=False):
+    """dfta_continuum: outward sweeps at any finite energy.  V: (nV, N) potentials; per trial l (0 .. 4), E, end node m (None: N-2) and
+    vidx (None: 0).  partners: (nrows, N) bound orbitals u; lists: a list of lists of partner rows (at most 16 each), trial_list: the
+    list of every trial (-1: none; None with lists given: list 0 for every trial); power: r^power in the sums.  Returns "logderiv"
+    (u'/u at r_m), "nodes", "delta" (CONT_FREE: the phase shift; CONT_WKB: the WKB phase at r_m), "scale" (the normalisation factor; 0
+    for E <= 0), "status" (CONT_* bits), "sums" (ntrials, 16) with partners, "rows" (ntrials, N) on request -- energy-normalised for E > 0."""
+    V = _f64(V).reshape(-1, grid.N)
+    l = _i32(np.atleast_1d(l))
+    E = _f64(np.atleast_1d(E))
+    nt = len(E)
+    if len(l) != nt:
+        raise ValueError("%d orders for %d energies" % (len(l), nt))
+    m = np.full(nt, grid.N - 2, np.int32) if m is None else _i32(np.broadcast_to(m, (nt,)))
+    vidx = None if vidx is None else _i32(np.broadcast_to(vidx, (nt,)))
+    P = None if partners is None else _f64(partners).reshape(-1, grid.N)
+    nrows = 0 if P is None else P.shape[0]
+    if lists is None and P is not None:
+        lists = [list(range(nrows))]
+    lists = lists or []
+    off = _i32(np.concatenate([[0], np.cumsum([len(x) for x in lists])])) if lists else None
+    flat = _i32([r for x in lists for r in x]) if lists else None
+    if lists and trial_list is None:
+        trial_list = np.zeros(nt, np.int32)
+    tl = None if trial_list is None else _i32(np.broadcast_to(trial_list, (nt,)))
+    out = _cont_outputs(nt, grid.N, bool(lists), want_rows)
+    ptr = lambda a, f: None if a is None else f(a)       # noqa: E731
+    ctx.check(ctx.lib.dfta_continuum(ctx.h, grid.h, int(norm), V.shape[0], _dp(V), nt, ptr(vidx, _ip), _ip(l), _dp(E), _ip(m), nrows,
+                                     ptr(P, _dp), int(power), len(lists), ptr(off, _ip), ptr(flat, _ip), ptr(tl, _ip), _dp(out["logderiv"]),
+                                     _ip(out["nodes"]), _dp(out["delta"]), _dp(out["scale"]), _ip(out["status"]), ptr(out.get("sums"), _dp),
+                                     ptr(out.get("rows"), _dp)))
+    return out
+
+
 class Mixer:
     """The SCF's density-mixing stage on its own (dfta_mixer): the launches dfta_scf_step issues for `mixing`, on the caller's arrays."""
 
@@ -856,6 +907,7 @@ class Scf:
             ctx.check(ctx.lib.dfta_scf_create_ex(ctx.h, grid.h, int(self.lsda), self.natoms, _ip(self.Z), alpha, levels_mode,
                                                  tree_depth, C.cast(C.byref(opt), vp), C.byref(h)))
         self.h = h
+        self._exchange = EXCHANGE_FUNCTIONAL
         d, nj, tr = C.c_int(), C.c_int(), C.c_long()
         ctx.check(ctx.lib.dfta_scf_info(h, C.byref(d), C.byref(nj), C.byref(tr)))
         self.tree_depth, self.njobs, self.trials_per_round = d.value, nj.value, tr.value
@@ -993,6 +1045,44 @@ class Scf:
         self.ctx.check(self.ctx.lib.dfta_scf_momentum_orbitals(self.h, len(q), _dp(q), _dp(out)))
         return out, self.orbital_jobs()
 
+    def _cont_norm(self, norm):
+        """"auto": CONT_WKB when an atom of the batch is charged or the exchange switch is KLI / SIC-KLI (a -1/r tail), else CONT_FREE"""
+        if norm != "auto":
+            return int(norm)
+        charged = self.configs is not None and any(config_electrons(c) != int(z) for c, z in zip(self.configs, self.Z))
+        return CONT_WKB if charged or self._exchange != EXCHANGE_FUNCTIONAL else CONT_FREE
+
+    def continuum(self, l, E, m=None, atom=0, spin=0, norm="auto", power=-1, want_rows=False):
+        """dfta_scf_continuum: continuum() on the batch's resident potentials (array(3 / 4) as it is now), read in place; atom, spin per
+        trial or one for all.  power >= 0: sums with the orbitals of the trial's channel -- l_b = l +- 1 for power 1 (dipole), l_b = l
+        otherwise (power 0: overlaps) --, "partner_index" (ntrials, 16) naming the level of each column (-1: none).  The orbitals belong
+        to the last step's input potential, the resident potential is the next step's."""
+        l = _i32(np.atleast_1d(l))
+        E = _f64(np.atleast_1d(E))
+        nt = len(E)
+        if len(l) != nt:
+            raise ValueError("%d orders for %d energies" % (len(l), nt))
+        m = np.full(nt, self.grid.N - 2, np.int32) if m is None else _i32(np.broadcast_to(m, (nt,)))
+        atom, spin = _i32(np.broadcast_to(atom, (nt,))), _i32(np.broadcast_to(spin, (nt,)))
+        out = _cont_outputs(nt, self.grid.N, power >= 0, want_rows)
+        if power >= 0:
+            out["partner_index"] = np.full((nt, CONT_MAX_PARTNERS), -1, np.int32)
+        ptr = lambda a, f: None if a is None else f(a)       # noqa: E731
+        self.ctx.check(self.ctx.lib.dfta_scf_continuum(self.h, self._cont_norm(norm), nt, _ip(atom), _ip(spin), _ip(l), _dp(E), _ip(m),
+                                                       int(power), _dp(out["logderiv"]), _ip(out["nodes"]), _dp(out["delta"]),
+                                                       _dp(out["scale"]), _ip(out["status"]), ptr(out.get("sums"), _dp),
+                                                       ptr(out.get("partner_index"), _ip), ptr(out.get("rows"), _dp)))
+        return out
+
+    def photoionization(self, eps, atom=0, norm="auto"):
+        """dfta_scf_photoionization: {"omega", "sigma"} (subshells of the atom, neps) -- photon energies eps - E_nl (Ha) and cross
+        sections (a_0^2) of every subshell at the photoelectron energies eps > 0 -- and "jobs", the subshells [(spin, n, l), ...]"""
+        eps = _f64(np.atleast_1d(eps))
+        jobs = [(sp, int(n), int(l)) for sp in range(2 if self.lsda else 1) for n, l in zip(*[self.levels(atom, sp)[k] for k in ("n", "l")])]
+        om, sg = np.zeros((len(jobs), len(eps))), np.zeros((len(jobs), len(eps)))
+        self.ctx.check(self.ctx.lib.dfta_scf_photoionization(self.h, int(atom), len(eps), _dp(eps), self._cont_norm(norm), _dp(om), _dp(sg)))
+        return {"omega": om, "sigma": sg, "jobs": jobs}
+
     def set_integrator(self, rule):
         """INT_TRAPEZOID .. INT_ROMBERG: quadrature of the energy integrals and of the orbitals' normalisation."""
         self.ctx.check(self.ctx.lib.dfta_scf_set_integrator(self.h, int(rule)))
@@ -1000,6 +1090,7 @@ class Scf:
     def set_exchange(self, exchange):
         """EXCHANGE_FUNCTIONAL, EXCHANGE_KLI or EXCHANGE_SIC_KLI, before the first step (dfta_scf_set_exchange)."""
         self.ctx.check(self.ctx.lib.dfta_scf_set_exchange(self.h, int(exchange)))
+        self._exchange = int(exchange)
 
     def exchange(self, atom=0, spin=0):
         """under EXCHANGE_KLI or EXCHANGE_SIC_KLI, after a step: {"vx", "v_raw"} (N each) of channel (atom, spin) and "Ex", the atom's

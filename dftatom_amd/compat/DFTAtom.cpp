@@ -28,6 +28,12 @@ bool DFTAtom::sicTable = false;            // --sic-table
 bool DFTAtom::formFactorTable = false;     // --form-factor-table[=smax:ns]
 double DFTAtom::formFactorSmax = 2.0;
 int DFTAtom::formFactorPoints = 41;
+bool DFTAtom::phaseShiftTable = false;     // --phase-shift-table[=emax:ne]
+double DFTAtom::phaseShiftEmax = 2.0;
+int DFTAtom::phaseShiftPoints = 8;
+bool DFTAtom::photoTable = false;          // --photo-table[=emax:ne]
+double DFTAtom::photoEmax = 4.0;
+int DFTAtom::photoPoints = 8;
 
 namespace {
 struct LevelLine { int n, l; double occ, E; int status, n_count, n_zero; };
@@ -214,6 +220,54 @@ void print_form_factor_table(dfta_scf* scf, bool lsda)
     std::cout << std::endl;
 }
 
+// the normalisation of the continuum tables: the Riccati matching needs a short-range potential
+int continuum_norm() { return DFTAtom::charge != 0 || !DFTAtom::config.empty() || DFTAtom::exchange != DFTA_EXCHANGE_FUNCTIONAL ? DFTA_CONT_WKB : DFTA_CONT_FREE; }
+
+// --phase-shift-table: every (spin, l = 0 .. 4, E_k = Emax (k + 1) / ne) in one launch, end node N - 2
+void print_phase_shift_table(dfta_scf* scf, const dfta_grid* grid, bool lsda)
+{
+    const int ne = DFTAtom::phaseShiftPoints, nspin = lsda ? 2 : 1, nt = nspin * 5 * ne, norm = continuum_norm();
+    std::vector<int> atom(nt, 0), spin(nt), l(nt), m(nt, dfta_grid_num_nodes(grid) - 2), nodes(nt), status(nt);
+    std::vector<double> E(nt), ld(nt), delta(nt), scale(nt);
+    for (int t = 0; t < nt; ++t) {
+        spin[t] = t / (5 * ne); l[t] = (t / ne) % 5;
+        E[t] = DFTAtom::phaseShiftEmax * (t % ne + 1) / ne;
+    }
+    if (dfta_scf_continuum(scf, norm, nt, atom.data(), spin.data(), l.data(), E.data(), m.data(), -1, ld.data(), nodes.data(), delta.data(),
+                           scale.data(), status.data(), nullptr, nullptr, nullptr) != DFTA_OK)
+        throw std::runtime_error("dfta_scf_continuum");
+    for (int t = 0; t < nt; ++t) {
+        std::cout << "PhaseShift ";
+        if (lsda) std::cout << (spin[t] == 0 ? "alpha " : "beta ");
+        std::cout << "l = " << l[t] << " E = " << std::fixed << std::setprecision(6) << E[t] << (norm == DFTA_CONT_FREE ? " delta = " : " phase = ") << delta[t]
+                  << " dlog = " << ld[t] << " nodes = " << nodes[t] << " status = " << status[t] << std::endl;
+    }
+    std::cout << std::endl;
+}
+
+// --photo-table: sigma_nl(omega) of every subshell at eps_k = Emax (k + 1) / ne, one launch; 1 a_0^2 = 28.002852 Mb
+void print_photo_table(dfta_scf* scf, bool lsda)
+{
+    const int ne = DFTAtom::photoPoints;
+    std::vector<double> eps(ne);
+    for (int k = 0; k < ne; ++k) eps[k] = DFTAtom::photoEmax * (k + 1) / ne;
+    std::vector<LevelLine> levels = fetch_levels(scf, 0);
+    const size_t nalpha = levels.size();
+    if (lsda)
+        for (const auto& lv : fetch_levels(scf, 1)) levels.push_back(lv);
+    std::vector<double> omega(levels.size() * ne), sigma(levels.size() * ne);
+    if (dfta_scf_photoionization(scf, 0, ne, eps.data(), continuum_norm(), omega.data(), sigma.data()) != DFTA_OK)
+        throw std::runtime_error("dfta_scf_photoionization");
+    for (size_t a = 0; a < levels.size(); ++a)
+        for (int k = 0; k < ne; ++k) {
+            std::cout << "Photo ";
+            if (lsda) std::cout << (a < nalpha ? "alpha " : "beta ");
+            std::cout << levels[a].n + 1 << DFTAtom::orb[levels[a].l] << " eps = " << std::fixed << std::setprecision(6) << eps[k] << " omega = " << omega[a * ne + k]
+                      << " sigma = " << sigma[a * ne + k] << " Mb = " << sigma[a * ne + k] * 28.002852 << std::endl;
+        }
+    std::cout << std::endl;
+}
+
 void print_configuration(std::vector<LevelLine> levels)
 {
     // levels sorted by energy for the final configuration line (DFTAtom.cpp:487-490)
@@ -277,6 +331,8 @@ void DFTAtom::Run(bool lsda, bool uniform, int Z, int MultigridLevels, double al
             if (exchangeTable) print_exchange_table(scf, grid, lsda);
             if (sicTable && exchange == DFTA_EXCHANGE_SIC_KLI) print_sic_table(scf, lsda);
             if (formFactorTable) print_form_factor_table(scf, lsda);
+            if (phaseShiftTable) print_phase_shift_table(scf, grid, lsda);
+            if (photoTable) print_photo_table(scf, lsda);
             break;
         }
         std::cout << "********************************************************************************" << std::endl;

@@ -61,6 +61,13 @@ public:
     static bool formFactorTable;
     static double formFactorSmax;
     static int formFactorPoints;
+    // after "Finished!" (and the other tables): the phase-shift table -- for every spin channel, l = 0 .. 4 and E_k = Emax (k + 1) / ne the
+    // scattering phase shift, u'/u at the last node but one and the node count of the outward solution (dfta_scf_continuum, one launch) --
+    // and the photoionization table: omega and sigma_nl of every subshell at the photoelectron energies eps_k = Emax (k + 1) / ne
+    // (dfta_scf_photoionization).  A charged atom or a KLI / SIC-KLI run is normalised by DFTA_CONT_WKB: the column then holds the WKB phase
+    static bool phaseShiftTable, photoTable;
+    static double phaseShiftEmax, photoEmax;
+    static int phaseShiftPoints, photoPoints;
 
 private:
     static constexpr double fourM_PI = 4. * M_PI;

@@ -25,6 +25,13 @@
 //                ns - 1 (1 / Angstrom; default 0 .. 2 in 41 points): s, q = 4 pi s 0.529177210903 (atomic units) and the X-ray form factor
 //                f(q) of the converged density; LSDA adds the magnetic form factor f_a - f_b (include/dftatom_hip.h:
 //                dfta_scf_form_factors, one launch for the table).  Without it the output is unchanged.
+// --phase-shift-table[=emax:ne]: after "Finished!" (and the other tables), one line per spin channel, l = 0 .. 4 and E = emax k / ne, k = 1 .. ne
+//                (Ha; default 2:8): the scattering phase shift delta_l(E) of the converged potential, u'/u at the last node but one and the
+//                node count of the outward solution (include/dftatom_hip.h: dfta_scf_continuum, one launch for the table).  With
+//                --charge, --config or --exchange=kli|sic the potential has a Coulomb tail: the column is the WKB phase instead.
+// --photo-table[=emax:ne]: then one line per subshell and photoelectron energy eps = emax k / ne (default 4:8): the photon energy
+//                omega = eps - E_nl and the photoionization cross section sigma_nl(omega) in a_0^2 and megabarn (dfta_scf_photoionization).
+//                Without them the output is unchanged.
 // --sweeps=exact|tolerance, --poisson=exact|tolerance|adaptive: the opt-in tolerance modes of the device path (include/dftatom_hip.h).
 // --mixing=linear (default, the reference's density mixing) | anderson (Anderson acceleration: about half the SCF steps, same protocol).
 // --exchange=functional (default) | kli: self-consistent exchange-only KLI -- every step's exchange potential from its own orbitals, no
@@ -125,6 +132,23 @@ int main(int argc, char** argv)
             DFT::DFTAtom::formFactorTable = true;
             DFT::DFTAtom::formFactorSmax = smax;
             DFT::DFTAtom::formFactorPoints = ns;
+        } else if (a == "--phase-shift-table") {
+            DFT::DFTAtom::phaseShiftTable = true;
+        } else if (a == "--photo-table") {
+            DFT::DFTAtom::photoTable = true;
+        } else if (a.rfind("--phase-shift-table=", 0) == 0 || a.rfind("--photo-table=", 0) == 0) {
+            const bool photo = a.rfind("--photo-table=", 0) == 0;
+            const std::string v = a.substr(a.find('=') + 1);
+            double emax = 0;
+            int ne = 0;
+            char tail = 0;
+            if (std::sscanf(v.c_str(), "%lf:%d%c", &emax, &ne, &tail) != 2 || !(emax > 0 && emax <= 1e4) || ne < 1 || ne > 100000) {
+                std::cerr << "bad continuum table " << v << " (emax:ne, emax in Ha, ne energies)" << std::endl;
+                return 2;
+            }
+            (photo ? DFT::DFTAtom::photoTable : DFT::DFTAtom::phaseShiftTable) = true;
+            (photo ? DFT::DFTAtom::photoEmax : DFT::DFTAtom::phaseShiftEmax) = emax;
+            (photo ? DFT::DFTAtom::photoPoints : DFT::DFTAtom::phaseShiftPoints) = ne;
         } else if (a == "--sweeps=tolerance" || a == "--sweeps=exact") {
             DFT::DFTAtom::sweepMode = a == "--sweeps=tolerance" ? DFTA_SWEEPS_TOLERANCE : DFTA_SWEEPS_EXACT;
         } else if (a == "--poisson=tolerance" || a == "--poisson=adaptive" || a == "--poisson=exact") {
@@ -190,6 +214,8 @@ int main(int argc, char** argv)
                   << "       --slater-table: after Finished!, the Slater integrals F^k, G^k of the levels, then E_H and the exact-exchange energy\n"
                   << "       --exchange-table: after Finished!, per shell its eigenvalue, the orbital averages of the Fock, Slater and KLI exchange potentials and the KLI constant, then E_x and r vKLI at the density's outermost node\n"
                   << "       --form-factor-table[=smax:ns]: after Finished!, the X-ray form factor f(q) at ns values of s = sin(theta)/lambda in 0 .. smax 1/Angstrom (default 2:41)\n"
+                  << "       --phase-shift-table[=emax:ne]: after Finished!, the scattering phase shifts delta_l(E), l = 0 .. 4, at ne energies in (0, emax] Ha (default 2:8), with u'/u and the node count\n"
+                  << "       --photo-table[=emax:ne]: after Finished!, the photoionization cross section of every subshell at ne photoelectron energies in (0, emax] Ha (default 4:8)\n"
                   << "       --charge=q: the cation (q > 0); --config: an electron configuration, fractional occupations allowed\n";
         return 2;
     }

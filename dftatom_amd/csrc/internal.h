@@ -226,6 +226,16 @@ struct dfta_bessel_scratch {               // the tables of a transform and its 
     // uploads l, the rows' device addresses and q (host arrays), launches, copies the nrow x nq results to out (host) and synchronises
     int run(dfta_ctx* ctx, const dfta_grid* g, int kind, int nrow, const int* l, const double* const* rows, int nq, const double* q, double* out);
 };
+// continuum.hip: the outward sweeps of a validated call (continuum_plan.h: check) on potentials dV (nV x N) and partner rows dP
+// (npartner_rows x N) that are on the device; the call's arrays and every output are host pointers (any output may be null).  Plans,
+// launches, copies the results back in the order of the call and synchronises; records the launches' time for dfta_ctx_last_kernel_ms
+namespace dfta_continuum_plan { struct Call; }
+struct dfta_continuum_out {
+    double* logderiv; int* nodes; double *delta_or_phase, *scale; int* status;
+    double *sums, *rows;           // ntrials x 16; ntrials x N
+};
+int dfta_continuum_run(dfta_ctx* ctx, const dfta_grid* g, const dfta_continuum_plan::Call& c, const double* dV, const double* dP,
+                       const dfta_continuum_out& out);
 // kli_stage.hip: the budget of a chunk's y rows in MiB: DFTA_DEBUG KLI_Y_MB, or the default
 double dfta_kli_budget_mb();
 // scf.hip: the k_mix launch (DFTA_MIX_LINEAR), same arguments

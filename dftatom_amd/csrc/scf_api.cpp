@@ -1,5 +1,5 @@
 // scf_api.cpp -- the read-only C ABI of the SCF layer (include/dftatom_hip.h): the accessors of a batch's state (scf_state.h) and the
-// post-SCF analysis entries on its orbitals and densities (orbitals.hip, slater.hip, exchange.hip, bessel.hip).  Host code only: what runs on the device is launched through the
+// post-SCF analysis entries on its orbitals and densities (orbitals.hip, slater.hip, exchange.hip, bessel.hip, continuum.hip).  Host code only: what runs on the device is launched through the
 // dfta_launch_* helpers (internal.h).  What an entry accepts and rejects is its own and stays in the entry.
 #include <hip/hip_runtime.h>
 
@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "bessel_plan.h"
+#include "continuum_plan.h"
 #include "exchange_plan.h"
 #include "scf_state.h"
 #include "slater_plan.h"
@@ -459,6 +460,125 @@ int dfta_scf_momentum_orbitals(dfta_scf* s, int nq, const double* q, double* out
     }
     if (const char* msg = dfta_bessel::check_transform(DFTA_BT_ORBITAL, njobs, l.data(), nq, q)) DFTA_REQUIRE(ctx, false, msg);
     return s->bessel.run(ctx, s->g, DFTA_BT_ORBITAL, njobs, l.data(), rows.data(), nq, q, out);
+}
+
+// ---- continuum orbitals in the batch's resident potentials (continuum.hip; potentials and orbitals are read in place) ----------------------
+namespace {
+
+// the partner lists of dfta_scf_continuum: one per (channel, l) in use, the channel's levels with l_b = l +- 1 (power 1) or l_b = l
+struct ContLists {
+    std::vector<int> off{0}, rows, trial_list;
+    std::vector<int> key;                // per list: channel * 5 + l
+};
+const char* scf_cont_lists(const dfta_scf* s, int ntrials, const int* atom, const int* spin, const int* l, int power, ContLists* out)
+{
+    out->trial_list.assign(ntrials, -1);
+    for (int t = 0; t < ntrials; ++t) {
+        const int key = (atom[t] * s->nspin + spin[t]) * (dfta_continuum_plan::kLmax + 1) + l[t];
+        int list = (int)(std::find(out->key.begin(), out->key.end(), key) - out->key.begin());
+        if (list == (int)out->key.size()) {
+            const auto [k0, cnt] = s->channel(atom[t], spin[t]);
+            for (int k = 0; k < cnt; ++k) {
+                const int lb = s->h_jobs[k0 + k].l;
+                if (power == 1 ? (lb == l[t] - 1 || lb == l[t] + 1) : lb == l[t]) out->rows.push_back(k0 + k);
+            }
+            if ((int)out->rows.size() - out->off.back() > dfta_continuum_plan::kMaxPartners) return "continuum: more than 16 partners in a list";
+            out->off.push_back((int)out->rows.size());
+            out->key.push_back(key);
+        }
+        out->trial_list[t] = list;
+    }
+    return nullptr;
+}
+
+}  // namespace
+
+int dfta_scf_continuum(dfta_scf* s, int norm_mode, int ntrials, const int* atom, const int* spin, const int* l, const double* E,
+                       const int* m, int power, double* logderiv, int* nodes, double* delta_or_phase, double* scale, int* status,
+                       double* sums, int* partner_index, double* rows)
+{
+    if (!s) return DFTA_ERR_INVALID;
+    dfta_ctx* ctx = s->ctx;
+    DFTA_ENTER(ctx);
+    DFTA_REQUIRE(ctx, ntrials >= 0, "dfta_scf_continuum: ntrials");
+    if (ntrials == 0) return DFTA_OK;
+    DFTA_REQUIRE(ctx, atom && spin && l && E && m, "dfta_scf_continuum arguments");
+    DFTA_REQUIRE(ctx, power < 0 || s->steps_done > 0, "no SCF step has run yet: there are no orbitals");
+    std::vector<int> vidx(ntrials);
+    for (int t = 0; t < ntrials; ++t) {
+        DFTA_REQUIRE(ctx, atom[t] >= 0 && atom[t] < s->natoms && spin[t] >= 0 && spin[t] < s->nspin, "dfta_scf_continuum: atom/spin");
+        DFTA_REQUIRE(ctx, l[t] >= 0 && l[t] <= dfta_continuum_plan::kLmax, "continuum: l outside 0 .. 4");
+        vidx[t] = atom[t] * s->nspin + spin[t];
+    }
+    ContLists lists;
+    if (power >= 0)
+        if (const char* msg = scf_cont_lists(s, ntrials, atom, spin, l, power, &lists)) DFTA_REQUIRE(ctx, false, msg);
+    dfta_continuum_plan::Call c;
+    c.norm_mode = norm_mode; c.N = s->g->N; c.nV = s->natoms * s->nspin; c.ntrials = ntrials;
+    c.vidx = vidx.data(); c.l = l; c.E = E; c.m = m;
+    c.npartner_rows = power >= 0 ? s->solver.njobs : 0; c.power = power >= 0 ? power : 0;
+    c.nlists = power >= 0 ? (int)lists.key.size() : 0;
+    c.list_off = lists.off.data(); c.list_rows = lists.rows.data(); c.trial_list = power >= 0 ? lists.trial_list.data() : nullptr;
+    if (const char* msg = dfta_continuum_plan::check(c)) DFTA_REQUIRE(ctx, false, msg);
+    dfta_continuum_out out;
+    out.logderiv = logderiv; out.nodes = nodes; out.delta_or_phase = delta_or_phase; out.scale = scale; out.status = status;
+    out.sums = power >= 0 ? sums : nullptr; out.rows = rows;
+    if (const int rc = dfta_continuum_run(ctx, s->g, c, s->d_V, power >= 0 ? s->solver.d_Psi.p : nullptr, out)) return rc;
+    if (partner_index && power >= 0)
+        for (int t = 0; t < ntrials; ++t) {
+            const int list = lists.trial_list[t], k0 = s->channel(atom[t], spin[t]).k0;
+            for (int q = 0; q < dfta_continuum_plan::kMaxPartners; ++q) {
+                const int j = lists.off[list] + q;
+                partner_index[(size_t)t * dfta_continuum_plan::kMaxPartners + q] = j < lists.off[list + 1] ? lists.rows[j] - k0 : -1;
+            }
+        }
+    return DFTA_OK;
+}
+
+int dfta_scf_photoionization(dfta_scf* s, int atom, int neps, const double* eps, int norm_mode, double* omega_out, double* sigma_out)
+{
+    if (!s) return DFTA_ERR_INVALID;
+    dfta_ctx* ctx = s->ctx;
+    DFTA_ENTER(ctx);
+    DFTA_REQUIRE(ctx, s->steps_done > 0, "no SCF step has run yet: there are no orbitals");
+    DFTA_REQUIRE(ctx, atom >= 0 && atom < s->natoms && neps >= 0, "dfta_scf_photoionization: atom / neps");
+    if (neps == 0) return DFTA_OK;
+    DFTA_REQUIRE(ctx, eps && omega_out && sigma_out, "dfta_scf_photoionization arguments");
+    for (int e = 0; e < neps; ++e) DFTA_REQUIRE(ctx, eps[e] > 0. && std::isfinite(eps[e]), "dfta_scf_photoionization: eps must be finite and > 0");
+    constexpr int nl = dfta_continuum_plan::kLmax + 1, np = dfta_continuum_plan::kMaxPartners;
+    // trials (spin, l', eps), eps fastest
+    const int ntrials = s->nspin * nl * neps;
+    std::vector<int> at(ntrials, atom), sp(ntrials), lt(ntrials), mt(ntrials, s->g->N - 2), status(ntrials), pidx((size_t)ntrials * np);
+    std::vector<double> Et(ntrials), sums((size_t)ntrials * np);
+    for (int t = 0; t < ntrials; ++t) { sp[t] = t / (nl * neps); lt[t] = (t / neps) % nl; Et[t] = eps[t % neps]; }
+    if (const int rc = dfta_scf_continuum(s, norm_mode, ntrials, at.data(), sp.data(), lt.data(), Et.data(), mt.data(), 1, nullptr, nullptr,
+                                          nullptr, nullptr, status.data(), sums.data(), pidx.data(), nullptr))
+        return rc;
+    const double K = (4. * (M_PI * M_PI)) * (1. / 137.035999084);
+    for (int spin = 0; spin < s->nspin; ++spin) {
+        const auto [k0, cnt] = s->channel(atom, spin);
+        for (int k = 0; k < cnt; ++k) {
+            const dfta::Job& j = s->h_jobs[k0 + k];
+            const size_t row = (size_t)(k0 + k - s->h_atoms[atom].job_off) * neps;
+            const double occ = s->solver.h_occ[k0 + k];
+            for (int e = 0; e < neps; ++e) {
+                double S[2] = {0., 0.};                                      // S_{l-1}, S_{l+1}
+                for (int side = 0; side < 2; ++side) {
+                    const int lp = j.l + (side ? 1 : -1);
+                    if (lp < 0 || lp > dfta_continuum_plan::kLmax) continue;
+                    const size_t t = ((size_t)spin * nl + lp) * neps + e;
+                    S[side] = std::nan("");
+                    if (!status[t])
+                        for (int q = 0; q < np; ++q)
+                            if (pidx[t * np + q] == k) S[side] = sums[t * np + q];
+                }
+                const double omega = eps[e] - j.E;
+                omega_out[row + e] = omega;
+                sigma_out[row + e] = (((K * omega) / 3.) * (occ / (2. * j.l + 1.))) * ((j.l * (S[0] * S[0])) + ((j.l + 1.) * (S[1] * S[1])));
+            }
+        }
+    }
+    return DFTA_OK;
 }
 
 int dfta_scf_get_records_dev(dfta_scf* s, double* dRecords)

@@ -68,6 +68,9 @@ def main():
     ap.add_argument("--form-factors", action="store_true",
                     help="after the table, every atom's X-ray form factor f(q) at s = sin(theta)/lambda = 0 .. 2 1/Angstrom in 41 points "
                          "(q = 4 pi s 0.529177210903 a.u.; LSDA adds f_a - f_b), one launch per shard: Scf.form_factors()")
+    ap.add_argument("--photo", action="store_true",
+                    help="after the table, the photoionization cross section (megabarn) of every atom's outermost subshell at the photoelectron "
+                         "energies 0.25, 0.5 .. 2 Ha, one launch per atom: Scf.photoionization()")
     ap.add_argument("--lsda", action="store_true", help="spin-polarised (LSDA) instead of LDA")
     ap.add_argument("--ionization", action="store_true",
                     help="first ionization energies: the neutral atom and the +1 cation of every Z of a rank's shard advance in one batch; "
@@ -210,6 +213,18 @@ def main():
             parts = [None] * world
             dist.all_gather_object(parts, ff)
             ff = {z: v for p in parts for z, v in p.items()}
+    photo = {}
+    photo_eps = [0.25 * k for k in range(1, 9)]
+    if args.photo:                              # per atom one launch: the trials (spin, l' = 0 .. 4, eps) with the dipole sums of its subshells
+        for a, z in enumerate(mine):
+            ph = scf.photoionization(photo_eps, atom=a)
+            nalpha = sum(1 for j in ph["jobs"] if j[0] == 0)
+            sp, n, l = ph["jobs"][nalpha - 1]   # the last alpha level: the outermost subshell
+            photo[int(z)] = {"n": n + 1, "l": l, "omega": ph["omega"][nalpha - 1].tolist(), "sigma_Mb": (ph["sigma"][nalpha - 1] * 28.002852).tolist()}
+        if world > 1:
+            parts = [None] * world
+            dist.all_gather_object(parts, photo)
+            photo = {z: v for p in parts for z, v in p.items()}
     block = torch.zeros((cap, D.RECORD_DOUBLES), dtype=torch.float64, device="cuda")
     scf.records_into(block.data_ptr())          # rows beyond len(mine) stay zero (Z = 0: no atom)
     ctx.synchronize()
@@ -233,6 +248,11 @@ def main():
                 for k, s in enumerate(ff_s):
                     print("Z %3d  FormFactor s = %.6f q = %.6f f = %.6f%s" % (r["Z"], s, ((4.0 * math.pi) * s) * 0.529177210903, t["f"][k],
                           " fa-fb = %.6f" % t["fa_minus_fb"][k] if "fa_minus_fb" in t else ""))
+        for r in rows:                          # sigma_nl(omega) of the outermost subshell, per atom
+            t = photo.get(r["Z"])
+            if t:
+                for om, sg in zip(t["omega"], t["sigma_Mb"]):
+                    print("Z %3d  Photo %d%s omega = %.6f sigma = %.6f Mb" % (r["Z"], t["n"], "spdf"[t["l"]], om, sg))
         print("%d atoms, %d GPU(s), %d SCF steps of the longest-running atom of rank 0, %d atom-steps in all, %d finished, %.1f s"
               % (len(rows), world, steps, sum(r["steps"] for r in rows), sum(r["finished"] for r in rows), elapsed))
         if args.out:
@@ -242,7 +262,8 @@ def main():
                                           **({"outermost": outer[r["Z"]]} if r["Z"] in outer else {}),
                                           **({"exx": exx[r["Z"]]} if r["Z"] in exx else {}),
                                           **({"kli": kli[r["Z"]]} if r["Z"] in kli else {}),
-                                          **({"form_factor": ff[r["Z"]]} if r["Z"] in ff else {})) for r in rows]},
+                                          **({"form_factor": ff[r["Z"]]} if r["Z"] in ff else {}),
+                                          **({"photoionization": photo[r["Z"]]} if r["Z"] in photo else {})) for r in rows]},
                           f, indent=1)
     scf.close()
     grid.close()

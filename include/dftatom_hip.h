@@ -11,7 +11,7 @@
  *   - plain C types only; every function returns an int status (DFTA_OK == 0) and never throws;
  *   - all floating point is IEEE fp64; kernels are built with -ffp-contract=off and use only + - * / sqrt on
  *     values, with exp() tables built on the host exactly as the reference evaluates them (the Bessel transforms, which the
- *     reference does not have, also call the device's sin and cos);
+ *     reference does not have, also call the device's sin and cos; the continuum block's normalisation also atan2 and hypot);
  *   - `_dev` functions take DEVICE pointers and are asynchronous on the context's stream;
  *     functions without the suffix take HOST pointers, copy, run the same kernels and synchronise;
  *   - one in-flight call per context (the reference is single threaded: DFTAtomFrame.cpp:176-198);
@@ -716,6 +716,93 @@ int  dfta_scf_form_factors(dfta_scf* s, int nq, const double* q, double* out);
 /* R~_nl(q) of every orbital of the batch, read in place, one launch: out njobs x nq (host), rows as dfta_scf_orbital_properties lists
  * them, each with its own l.  Before the first dfta_scf_step: DFTA_ERR_INVALID. */
 int  dfta_scf_momentum_orbitals(dfta_scf* s, int nq, const double* q, double* out);
+
+/* ---- continuum orbitals: outward sweeps, phase shifts, photoionization (beyond the reference's live code) -------------------------------
+ * The outward integration of the radial equation from the nucleus to a caller-given end node, at ANY finite energy: logarithmic
+ * derivatives u'/u, node counts, scattering phase shifts, energy-normalised continuum orbitals and their overlap / dipole sums with
+ * bound orbitals.  The reference's own outward sweep, Numerov::SolveSchrodingerCountNodesFromNucleus (Numerov.h:204-270), is dormant
+ * there; this block keeps its transformation (Numerov.h:96-101) and replaces its start (u_1 = r^(l+1), w_0 = 0) by a power series.
+ * One trial = (potential, l, E, end node m), 0 <= l <= 4, 3 <= m <= N-2; one lane per trial, the 64 lanes of a wave marching the node
+ * index together.
+ *
+ * Tables: r_i and s_i = dr/di of the orbital block (logarithmic grid: (Rp delta) exp(i delta), uniform grid: h); c = delta^2 / 4 and
+ * lam = delta on the logarithmic grid, c = lam = 0 on the uniform one.  Per node i >= 1 of a (potential, l), the same in every trial:
+ *   s2_i = s_i s_i;  q_i = sqrt(s_i);  vl_i = V_i + ((L / (r_i r_i)) 0.5) with L = l (l + 1.) (l = 0: vl_i = V_i + 0.0).
+ * Per trial, with y_i = u(r_i) / q_i:
+ *   f_i = (2 (vl_i - E)) s2_i + c        (the equation is y'' = f y in the index)
+ *   d_i = 1 - f_i / 12
+ * Start, nodes 1 and 2, from the fit V_i = -Zc / r_i + v0 at those two nodes:
+ *   Zc = ((V_2 - V_1) (r_1 r_2)) / (r_2 - r_1);  v0 = V_1 + Zc / r_1;
+ *   a_0 = 1;  a_1 = -Zc / (l + 1);  a_k = (((-2 Zc) a_{k-1}) + ((2 (v0 - E)) a_{k-2})) / (k (k + 2l + 1)), k = 2, 3, 4 (the divisor exact);
+ *   u_i = p_i ((((a_4 r_i + a_3) r_i + a_2) r_i + a_1) r_i + a_0),  p_i = r_i^(l+1) by l products from r_i;
+ *   y_i = u_i / q_i;  w_i = d_i y_i.          (V = 0 gives Zc = v0 = 0; the Coulomb cusp of l = 0 is right.)
+ * Recurrence, i = 3 .. m+1:
+ *   w_i = ((2 w_{i-1}) - w_{i-2}) + f_{i-1} y_{i-1};  y_i = w_i / d_i.
+ * End node m:
+ *   y'_m = (((1 - f_{m+1} / 6) y_{m+1}) - ((1 - f_{m-1} / 6) y_{m-1})) 0.5          (Numerov's O(h^4) derivative)
+ *   u_m = q_m y_m;  u'_m = (y'_m + (lam 0.5) y_m) / q_m;  logderiv = u'_m / u_m;
+ *   nodes = the number of i in 2 .. m with (y_i < 0) != (y_{i-1} < 0).
+ * status (0: fine): DFTA_CONT_NONFINITE -- a y_i, 1 <= i <= m+1, was not finite; DFTA_CONT_STEP -- d_i > 0 failed for an i in 3 .. m+1
+ * (a NaN node of the potential does that).  With either bit every floating-point output of the trial is NaN and nodes is -1.
+ *
+ * Normalisation, E > 0 only: k = sqrt(2 E), x = k r_m, U = u'_m / k.  E <= 0: factor = 1 and delta_or_phase = scale = 0.0; logderiv,
+ * nodes, sums and rows stay valid (unnormalised).  scale = factor.
+ *   DFTA_CONT_FREE (short-range potentials: neutral atoms under an LDA or GGA): matching to the Riccati functions jh_l = x j_l(x), with
+ *     j_l the device's (the Bessel block), and yh_l: yh_0 = -cos x, yh_1 = yh_0 / x - sin x, yh_{n+1} = ((2n+1) / x) yh_n - yh_{n-1};
+ *     jh'_l = x j_{l-1}(x) - (l / x) jh_l, yh'_l = yh_{l-1} - (l / x) yh_l; l = 0: jh' = cos x, yh' = sin x.
+ *     a = u_m yh' - U yh;  b = U jh - u_m jh';  delta_l = atan2(-b, a) in (-pi, pi];  factor = sqrt(2 / (pi k)) / hypot(a, b).
+ *   DFTA_CONT_WKB (any tail: ions, KLI, SIC-KLI): kap2_i = (2 (E - V_i)) - L / (r_i r_i) at i = m-1, m, m+1; all three must be > 0,
+ *     otherwise status has DFTA_CONT_WKB_TAIL, logderiv and nodes stay and the normalised outputs are NaN.  kap_i = sqrt(kap2_i);
+ *     kp = (kap_{m+1} - kap_{m-1}) / (r_{m+1} - r_{m-1});  al = 1 / sqrt(kap_m);  alp = -kp / ((2 kap_m) kap_m^(1/2));
+ *     A = u_m / al;  B = al u'_m - alp u_m;  factor = sqrt(2 / pi) / hypot(A, B);  phase = atan2(A, B): the phase of the WKB form
+ *     u = C al sin(phase) at r_m -- no phase shift (that needs Coulomb functions), but the amplitude is the energy-normalised one.
+ * Normalised, u_E(r) -> sqrt(2 / (pi k)) sin(k r - l pi / 2 + delta_l): Int u_E u_E' dr = delta(E - E').
+ *
+ * Partner sums (overlap and dipole integrals with bound orbitals), fused into the sweep.  Partner rows P_b (N doubles each), a power
+ * 0 <= p <= 8: g_b,i = w_i ((P_b,i rp_i) s_i) with w_i the weight of node i without 3/8 (the Bessel block's) and rp_i = r_i^p by p
+ * products from 1;  S_t,b = ((Sum_{1 <= i <= m} g_b,i (q_i y_i)) (3/8)) factor_t.  The sum is taken sequentially inside blocks of 256
+ * nodes (256 k .. 256 k + 255), and the blocks' sums are added in order: the shape depends on m alone.  Every trial names one partner
+ * list (or none); a list holds at most DFTA_CONT_MAX_PARTNERS rows.  Rows: u_t,i = (q_i y_i) factor_t for 1 <= i <= m+1, 0.0 at node 0
+ * and beyond m+1.
+ * The first steps of the recurrence at high l on the logarithmic grid (f_i ~ l (l+1) / i^2) admix the irregular solution, which dies
+ * as (r_1 / r)^(2l+1): the SCALE of the unnormalised solution carries that error (1e-4 for l = 4 at 4097 nodes), so compare only
+ * scale-free (logderiv, nodes, delta) and normalised quantities.
+ * A trial's bits depend on its potential, l, E, m, its partners and the grid -- not on the other trials of the call, their number or
+ * order, the instance of the kernel (0, 4, 8 or 16 partner accumulators), whether rows were asked for, or the run.  No atomics.
+ * DFTA_ERR_INVALID: a NULL pointer, a mode outside {0, 1}, an l outside 0 .. 4, an m outside 3 .. N-2, a non-finite E, more than 16
+ * partners in a list, an index out of range, N < 5.  ntrials == 0: DFTA_OK, nothing is written.  Every entry records the sweep's
+ * time for dfta_ctx_last_kernel_ms. */
+#define DFTA_CONT_FREE 0
+#define DFTA_CONT_WKB  1
+#define DFTA_CONT_MAX_PARTNERS 16
+#define DFTA_CONT_NONFINITE 1
+#define DFTA_CONT_STEP      2
+#define DFTA_CONT_WKB_TAIL  4
+/* on caller-supplied potentials and partner rows; host pointers.  V: nV x N; vidx (NULL: 0), l, E, m: ntrials; P: npartner_rows x N
+ * (NULL with 0 rows); list k holds the rows list_rows[list_off[k] .. list_off[k+1] - 1], trial_list[t] (NULL: none) is the list of trial
+ * t or -1.  Outputs per trial, any of which may be NULL: logderiv, nodes, delta_or_phase, scale, status; sums ntrials x 16 (entries
+ * beyond the trial's list: 0.0); rows ntrials x N. */
+int  dfta_continuum(dfta_ctx* ctx, const dfta_grid* g, int norm_mode, int nV, const double* V, int ntrials, const int* vidx, const int* l,
+                    const double* E, const int* m, int npartner_rows, const double* P, int power, int nlists, const int* list_off,
+                    const int* list_rows, const int* trial_list, double* logderiv, int* nodes, double* delta_or_phase, double* scale,
+                    int* status, double* sums, double* rows);
+/* ... on the batch's resident potentials, read in place: trial t runs in the potential of (atom[t], spin[t]), the array
+ * dfta_scf_get_array(.., 3 / 4) returns at the time of the call.  power < 0: no partners.  Otherwise the partners of a trial are the
+ * orbitals of its channel, in the order of dfta_scf_get_levels, with l_b = l - 1 or l + 1 for power == 1 and l_b = l for any other
+ * power; partner_index (may be NULL): ntrials x 16, the level index of each column of sums within the channel, -1 beyond the list.
+ * Mind the orbital block: the orbitals belong to the last step's INPUT potential, the resident potential is the NEXT step's input; at
+ * convergence the two agree to the SCF's tolerance.  Before the first dfta_scf_step a call with power >= 0 returns DFTA_ERR_INVALID. */
+int  dfta_scf_continuum(dfta_scf* s, int norm_mode, int ntrials, const int* atom, const int* spin, const int* l, const double* E,
+                        const int* m, int power, double* logderiv, int* nodes, double* delta_or_phase, double* scale, int* status,
+                        double* sums, int* partner_index, double* rows);
+/* Photoionization cross sections of every subshell of an atom on a common grid of photoelectron energies eps (neps values > 0), in
+ * a_0^2, from ONE launch: the trials (spin, l' = 0 .. 4, eps) with end node N-2 and the dipole sums (power 1) of dfta_scf_continuum.
+ * For the subshell of job j of the atom (alpha levels, then beta levels: the order of dfta_scf_orbital_properties) with eigenvalue E_j,
+ * angular momentum l and occupation occ (dfta_scf_get_occupations), omega = eps - E_j and, host arithmetic in double in this order,
+ *   sigma = (((K omega) / 3) (occ / (2l + 1))) ((l (S_{l-1} S_{l-1})) + ((l + 1) (S_{l+1} S_{l+1}))),  K = (4 (pi pi)) alpha,
+ * alpha = 1 / 137.035999084, S_{l'} the subshell's sum in the trial (its spin, l', eps); the S_{l-1} term is absent for l = 0, the
+ * S_{l+1} term for l = 4.  omega_out, sigma_out: njobs_of_the_atom x neps.  A trial with a status bit makes its sigma NaN. */
+int  dfta_scf_photoionization(dfta_scf* s, int atom, int neps, const double* eps, int norm_mode, double* omega_out, double* sigma_out);
 
 /* ---- Aufbau -------------------------------------------------------------------------------------------------
  * AufbauPrinciple::GetSubshells + sort (AufbauPrinciple.h:36-75, DFTAtom.cpp:367); integer-only host code. */
