@@ -44,6 +44,8 @@ BESSEL_LMAX = 4                        # DFTA_BESSEL_LMAX: largest order of sph_
 CONT_FREE, CONT_WKB = 0, 1             # DFTA_CONT_*: normalisation of continuum(): Riccati matching (short range) / WKB amplitude (any tail)
 CONT_MAX_PARTNERS = 16                 # DFTA_CONT_MAX_PARTNERS: partners of one list
 CONT_NONFINITE, CONT_STEP, CONT_WKB_TAIL = 1, 2, 4      # status bits of a continuum trial
+PS_COEF, PS_MATCH = 7, 8               # DFTA_PS_*: a0, a2 .. a12 of a pseudized channel; P0 .. P4, I_AE, I_ps, g
+PS_NOBRACKET, PS_CAP, PS_NODES, PS_NONFINITE, PS_NOTPOSITIVE = 1, 2, 4, 8, 16      # status bits of a pseudized channel
 
 c_dp = C.POINTER(C.c_double)
 c_ip = C.POINTER(C.c_int)
@@ -195,6 +197,12 @@ SIGNATURES = {
     "dfta_scf_continuum": (C.c_int, [vp, C.c_int, C.c_int, c_ip, c_ip, c_ip, c_dp, c_ip, C.c_int, c_dp, c_ip, c_dp, c_dp, c_ip, c_dp, c_ip,
                                      c_dp]),
     "dfta_scf_photoionization": (C.c_int, [vp, C.c_int, C.c_int, c_dp, C.c_int, c_dp, c_dp]),
+    "dfta_pseudize": (C.c_int, [vp, vp, C.c_int, c_dp, c_dp, c_ip, c_dp, c_ip, c_dp, c_dp, c_dp, c_dp, c_dp, c_ip, c_ip]),
+    "dfta_pseudo_ionic": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, c_ip, c_ip, c_dp, c_dp, c_dp, c_dp, c_ip] + [c_dp] * 6),
+    "dfta_scf_pseudopotentials": (C.c_int, [vp, C.c_int, c_ip, c_ip, c_ip, C.c_double, c_ip, c_ip, c_dp, c_dp, c_dp, c_dp, c_dp, c_ip, c_ip]
+                                  + [c_dp] * 6),
+    "dfta_pseudo_default_valence": (C.c_int, [C.c_int, c_ip, c_ip, c_ip, C.c_int, c_ip, c_ip]),
+    "dfta_pseudo_default_ic": (C.c_int, [vp, C.c_int, c_dp, C.c_double, c_ip]),
 }
 
 _lib = None
@@ -820,6 +828,64 @@ def continuum(ctx, grid, V, l, E, m=None, vidx=None, norm=CONT_FREE, partners=No
     return out
 
 
+def pseudize(ctx, grid, V, u, l, eps, ic):
+    """dfta_pseudize: Troullier-Martins pseudization of the channels (V[k], u[k], l[k], eps[k], ic[k]); V, u: (nch, N).  Returns
+    "u_ps", "V_ps" (nch, N), "coef" (nch, 7: a0, a2 .. a12 in x = r / r_c), "rc", "match" (nch, 8: P0 .. P4, I_AE, I_ps, g), "iters",
+    "status" (PS_* bits; with any bit the channel's floating-point outputs are NaN)."""
+    V = _f64(V).reshape(-1, grid.N)
+    u = _f64(u).reshape(-1, grid.N)
+    l, eps, ic = _i32(np.atleast_1d(l)), _f64(np.atleast_1d(eps)), _i32(np.atleast_1d(ic))
+    nch = len(l)
+    if not (V.shape[0] == u.shape[0] == len(eps) == len(ic) == nch):
+        raise ValueError("pseudize: %d potentials, %d orbitals, %d l, %d eps, %d ic" % (V.shape[0], u.shape[0], nch, len(eps), len(ic)))
+    out = {"u_ps": np.zeros((nch, grid.N)), "V_ps": np.zeros((nch, grid.N)), "coef": np.zeros((nch, PS_COEF)), "rc": np.zeros(nch),
+           "match": np.zeros((nch, PS_MATCH)), "iters": np.zeros(nch, np.int32), "status": np.zeros(nch, np.int32)}
+    ctx.check(ctx.lib.dfta_pseudize(ctx.h, grid.h, nch, _dp(V), _dp(u), _ip(l), _dp(eps), _ip(ic), _dp(out["u_ps"]), _dp(out["V_ps"]),
+                                    _dp(out["coef"]), _dp(out["rc"]), _dp(out["match"]), _ip(out["iters"]), _ip(out["status"])))
+    return out
+
+
+def pseudo_ionic(ctx, grid, ps, l, occ, atom=None, functional=XC_VWN, l_loc=None):
+    """dfta_pseudo_ionic: unscreening and Kleinman-Bylander quantities of the channels of a pseudize() result `ps`; l, occ per channel,
+    atom: the atom of each channel (None: one atom), l_loc: the local l per atom (None: the highest l of the atom).  Returns "rho_v",
+    "vH", "vxc" (natoms, N), "V_ion", "beta" (nch, N), "kb" (nch, 3: <u|dV|u>, <u|dV^2|u>, E_KB; the local channel 0, 0, NaN)."""
+    u, V = _f64(ps["u_ps"]).reshape(-1, grid.N), _f64(ps["V_ps"]).reshape(-1, grid.N)
+    nch = u.shape[0]
+    l, occ = _i32(np.atleast_1d(l)), _f64(np.atleast_1d(occ))
+    atom = np.zeros(nch, np.int32) if atom is None else _i32(np.atleast_1d(atom))
+    if not (len(l) == len(occ) == len(atom) == nch == V.shape[0]):
+        raise ValueError("pseudo_ionic: the channel arrays disagree in length")
+    natoms = int(atom.max()) + 1 if nch else 0
+    a0 = _f64(np.asarray(ps["coef"]).reshape(-1, PS_COEF)[:, 0])
+    ll = None if l_loc is None else _i32(np.broadcast_to(l_loc, (natoms,)))
+    out = {"rho_v": np.zeros((natoms, grid.N)), "vH": np.zeros((natoms, grid.N)), "vxc": np.zeros((natoms, grid.N)),
+           "V_ion": np.zeros((nch, grid.N)), "beta": np.zeros((nch, grid.N)), "kb": np.zeros((nch, 3))}
+    ctx.check(ctx.lib.dfta_pseudo_ionic(ctx.h, grid.h, int(functional), natoms, nch, _ip(atom), _ip(l), _dp(occ), _dp(a0), _dp(u), _dp(V),
+                                        None if ll is None else _ip(ll), _dp(out["rho_v"]), _dp(out["vH"]), _dp(out["vxc"]),
+                                        _dp(out["V_ion"]), _dp(out["beta"]), _dp(out["kb"])))
+    return out
+
+
+def default_valence(n, l, occ):
+    """dfta_pseudo_default_valence: the indices of the levels (n, l, occ > 0) that a pseudopotential keeps as valence -- per l the
+    occupied level of largest n, if n >= n_max - max(0, l - 1).  Host integers only."""
+    n, l, occ = _i32(n), _i32(l), _i32(np.ceil(np.asarray(occ, dtype=np.float64)))
+    pick, cnt = np.zeros(max(len(n), 1), np.int32), C.c_int()
+    if load().dfta_pseudo_default_valence(len(n), _ip(n), _ip(l), _ip(occ), len(pick), _ip(pick), C.byref(cnt)):
+        raise DftaError("default_valence: invalid configuration")
+    return pick[:cnt.value].copy()
+
+
+def default_ic(grid, u, factor=1.5):
+    """dfta_pseudo_default_ic: the core node of each orbital of u (nch, N): nearest to factor x the radius of the orbital's largest |u|,
+    ORB_RPEAK, moved beyond the last node of u.  Host only."""
+    u = _f64(u).reshape(-1, grid.N)
+    ic = np.zeros(u.shape[0], np.int32)
+    if load().dfta_pseudo_default_ic(grid.h, u.shape[0], _dp(u), float(factor), _ip(ic)):
+        raise DftaError("default_ic: invalid arguments")
+    return ic
+
+
 class Mixer:
     """The SCF's density-mixing stage on its own (dfta_mixer): the launches dfta_scf_step issues for `mixing`, on the caller's arrays."""
 
@@ -1072,6 +1138,38 @@ class Scf:
                                                        int(power), _dp(out["logderiv"]), _ip(out["nodes"]), _dp(out["delta"]),
                                                        _dp(out["scale"]), _ip(out["status"]), ptr(out.get("sums"), _dp),
                                                        ptr(out.get("partner_index"), _ip), ptr(out.get("rows"), _dp)))
+        return out
+
+    def pseudopotentials(self, atoms=None, levels=None, ic=None, factor=1.5, l_loc=None):
+        """dfta_scf_pseudopotentials: Troullier-Martins pseudopotentials of valence levels, the resident orbitals and potentials read in
+        place.  atoms: the atoms wanted (None: all); levels: per atom in `atoms` the level indices (None: default_valence of its levels);
+        ic: a core node per channel (None: default_ic(factor)); l_loc: the local l per atom in `atoms` (None: the highest).  The
+        potential is array(3) AS IT IS NOW (after a step: the next step's input; the orbitals belong to the last step's input).
+        Returns "atom", "level", "l", "occ", "eps", "ic" per channel and the outputs of pseudize() and pseudo_ionic()."""
+        atoms = list(range(self.natoms)) if atoms is None else [int(a) for a in np.atleast_1d(atoms)]
+        at, lev, l, occ, eps = [], [], [], [], []
+        for k, a in enumerate(atoms):
+            if not 0 <= a < self.natoms:
+                raise DftaError("pseudopotentials: atom %d outside 0 .. %d" % (a, self.natoms - 1))
+            lv = self.levels(a, 0)
+            keep = default_valence(lv["n"], lv["l"], lv["occupation"]) if levels is None else np.atleast_1d(levels[k])
+            for j in keep:
+                if not 0 <= j < len(lv["l"]):
+                    raise DftaError("pseudopotentials: level %d of atom %d outside 0 .. %d" % (j, a, len(lv["l"]) - 1))
+                at.append(a); lev.append(int(j)); l.append(int(lv["l"][j])); occ.append(float(lv["occupation"][j])); eps.append(float(lv["E"][j]))
+        nch, N, na = len(at), self.grid.N, len(atoms)
+        at, lev = _i32(at), _i32(lev)
+        icv = None if ic is None else _i32(np.broadcast_to(ic, (nch,)))
+        ll = None if l_loc is None else _i32(np.broadcast_to(l_loc, (na,)))
+        out = {"atom": at, "level": lev, "l": _i32(l), "occ": _f64(occ), "eps": _f64(eps), "ic": np.zeros(nch, np.int32),
+               "u_ps": np.zeros((nch, N)), "V_ps": np.zeros((nch, N)), "coef": np.zeros((nch, PS_COEF)), "rc": np.zeros(nch),
+               "match": np.zeros((nch, PS_MATCH)), "iters": np.zeros(nch, np.int32), "status": np.zeros(nch, np.int32),
+               "rho_v": np.zeros((na, N)), "vH": np.zeros((na, N)), "vxc": np.zeros((na, N)), "V_ion": np.zeros((nch, N)),
+               "beta": np.zeros((nch, N)), "kb": np.zeros((nch, 3))}
+        self.ctx.check(self.ctx.lib.dfta_scf_pseudopotentials(
+            self.h, nch, _ip(at), _ip(lev), None if icv is None else _ip(icv), float(factor), None if ll is None else _ip(ll), _ip(out["ic"]),
+            _dp(out["u_ps"]), _dp(out["V_ps"]), _dp(out["coef"]), _dp(out["rc"]), _dp(out["match"]), _ip(out["iters"]), _ip(out["status"]),
+            _dp(out["rho_v"]), _dp(out["vH"]), _dp(out["vxc"]), _dp(out["V_ion"]), _dp(out["beta"]), _dp(out["kb"])))
         return out
 
     def photoionization(self, eps, atom=0, norm="auto"):

@@ -31,6 +31,8 @@ int DFTAtom::formFactorPoints = 41;
 bool DFTAtom::phaseShiftTable = false;     // --phase-shift-table[=emax:ne]
 double DFTAtom::phaseShiftEmax = 2.0;
 int DFTAtom::phaseShiftPoints = 8;
+bool DFTAtom::pseudoTable = false;         // --pseudo-table[=factor]
+double DFTAtom::pseudoFactor = 1.5;
 bool DFTAtom::photoTable = false;          // --photo-table[=emax:ne]
 double DFTAtom::photoEmax = 4.0;
 int DFTAtom::photoPoints = 8;
@@ -268,6 +270,51 @@ void print_photo_table(dfta_scf* scf, bool lsda)
     std::cout << std::endl;
 }
 
+// --pseudo-table: the Troullier-Martins pseudopotentials of the default valence levels (dfta_scf_pseudopotentials on the resident
+// potential), with two checks: the eigenvalue of the nodeless level of V_ps by dfta_solve_levels, and the norm residual g
+void print_pseudo_table(dfta_scf* scf, dfta_ctx* ctx, const dfta_grid* grid, bool lsda, int N)
+{
+    if (lsda) {
+        std::cout << "Pseudo: spin-polarised atoms are out of scope" << std::endl << std::endl;
+        return;
+    }
+    const std::vector<LevelLine> levels = fetch_levels(scf, 0);
+    const int nlev = (int)levels.size();
+    std::vector<int> n(nlev), l(nlev), occ(nlev), pick(nlev), atom;
+    for (int k = 0; k < nlev; ++k) { n[k] = levels[k].n; l[k] = levels[k].l; occ[k] = levels[k].occ > 0. ? 1 : 0; }
+    int nch = 0;
+    if (dfta_pseudo_default_valence(nlev, n.data(), l.data(), occ.data(), nlev, pick.data(), &nch) != DFTA_OK)
+        throw std::runtime_error("dfta_pseudo_default_valence");
+    atom.assign(nch, 0);
+    std::vector<int> ic(nch), iters(nch), status(nch);
+    std::vector<double> Vps((size_t)nch * N), coef((size_t)nch * DFTA_PS_COEF), rc(nch), match((size_t)nch * DFTA_PS_MATCH), kb((size_t)nch * 3);
+    if (dfta_scf_pseudopotentials(scf, nch, atom.data(), pick.data(), nullptr, DFTAtom::pseudoFactor, nullptr, ic.data(), nullptr, Vps.data(),
+                                  coef.data(), rc.data(), match.data(), iters.data(), status.data(), nullptr, nullptr, nullptr, nullptr, nullptr,
+                                  kb.data()) != DFTA_OK)
+        throw std::runtime_error(std::string("dfta_scf_pseudopotentials: ") + dfta_last_error(ctx));
+    for (int k = 0; k < nch; ++k) {
+        const LevelLine& lv = levels[pick[k]];
+        std::cout << "Pseudo " << lv.n + 1 << DFTAtom::orb[lv.l] << " status = " << status[k] << " ic = " << ic[k] << " rc = " << std::fixed
+                  << std::setprecision(6) << rc[k] << " evaluations = " << iters[k] << " coef =";
+        for (int q = 0; q < DFTA_PS_COEF; ++q) std::cout << " " << std::setprecision(9) << coef[(size_t)k * DFTA_PS_COEF + q];
+        std::cout << " EKB = " << std::setprecision(6) << kb[(size_t)k * 3 + 2];
+        double dE = std::nan("");
+        if (!status[k]) {
+            const double* V = Vps.data() + (size_t)k * N;
+            const double bottom = *std::min_element(V + 1, V + N) - 1.0;
+            const int vidx = 0, nn = lv.l, one = 1;
+            dfta_level_result res = {};
+            if (dfta_solve_levels(ctx, grid, DFTA_LEVELS_BATCHED, 0, 1, V, &bottom, nullptr, 1, &vidx, &nn, &lv.l, &one, &res, nullptr, nullptr, nullptr,
+                                  nullptr) != DFTA_OK)
+                throw std::runtime_error("dfta_solve_levels");
+            dE = res.E - lv.E;
+        }
+        std::cout << " eigenvalue check = " << std::scientific << std::setprecision(2) << dE << " norm check = " << match[(size_t)k * DFTA_PS_MATCH + 7]
+                  << std::fixed << std::endl;
+    }
+    std::cout << std::endl;
+}
+
 void print_configuration(std::vector<LevelLine> levels)
 {
     // levels sorted by energy for the final configuration line (DFTAtom.cpp:487-490)
@@ -333,6 +380,7 @@ void DFTAtom::Run(bool lsda, bool uniform, int Z, int MultigridLevels, double al
             if (formFactorTable) print_form_factor_table(scf, lsda);
             if (phaseShiftTable) print_phase_shift_table(scf, grid, lsda);
             if (photoTable) print_photo_table(scf, lsda);
+            if (pseudoTable) print_pseudo_table(scf, rt.ctx(), grid, lsda, dfta_num_nodes(MultigridLevels));
             break;
         }
         std::cout << "********************************************************************************" << std::endl;

@@ -66,6 +66,10 @@ public:
     // and the photoionization table: omega and sigma_nl of every subshell at the photoelectron energies eps_k = Emax (k + 1) / ne
     // (dfta_scf_photoionization).  A charged atom or a KLI / SIC-KLI run is normalised by DFTA_CONT_WKB: the column then holds the WKB phase
     static bool phaseShiftTable, photoTable;
+    // --pseudo-table[=factor]: after Finished!, the Troullier-Martins pseudopotentials of the default valence levels, core radii at
+    // factor x the radius of the orbital's largest |u| (dfta_scf_pseudopotentials): r_c, the coefficients, E_KB and two checks
+    static bool pseudoTable;
+    static double pseudoFactor;
     static double phaseShiftEmax, photoEmax;
     static int phaseShiftPoints, photoPoints;
 

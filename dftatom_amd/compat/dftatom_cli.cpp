@@ -136,6 +136,17 @@ int main(int argc, char** argv)
             DFT::DFTAtom::phaseShiftTable = true;
         } else if (a == "--photo-table") {
             DFT::DFTAtom::photoTable = true;
+        } else if (a == "--pseudo-table") {
+            DFT::DFTAtom::pseudoTable = true;
+        } else if (a.rfind("--pseudo-table=", 0) == 0) {
+            double f = 0;
+            char tail = 0;
+            if (std::sscanf(a.c_str() + 15, "%lf%c", &f, &tail) != 1 || !(f > 0 && f <= 100)) {
+                std::cerr << "bad pseudo table " << a.substr(15) << " (factor: r_c over the radius of the orbital's largest |u|)" << std::endl;
+                return 2;
+            }
+            DFT::DFTAtom::pseudoTable = true;
+            DFT::DFTAtom::pseudoFactor = f;
         } else if (a.rfind("--phase-shift-table=", 0) == 0 || a.rfind("--photo-table=", 0) == 0) {
             const bool photo = a.rfind("--photo-table=", 0) == 0;
             const std::string v = a.substr(a.find('=') + 1);
@@ -215,6 +226,7 @@ int main(int argc, char** argv)
                   << "       --exchange-table: after Finished!, per shell its eigenvalue, the orbital averages of the Fock, Slater and KLI exchange potentials and the KLI constant, then E_x and r vKLI at the density's outermost node\n"
                   << "       --form-factor-table[=smax:ns]: after Finished!, the X-ray form factor f(q) at ns values of s = sin(theta)/lambda in 0 .. smax 1/Angstrom (default 2:41)\n"
                   << "       --phase-shift-table[=emax:ne]: after Finished!, the scattering phase shifts delta_l(E), l = 0 .. 4, at ne energies in (0, emax] Ha (default 2:8), with u'/u and the node count\n"
+                  << "       --pseudo-table[=factor]: after Finished!, the Troullier-Martins pseudopotentials of the default valence levels (LDA / GGA), r_c at factor x the radius of the orbital's largest |u| (default 1.5): r_c, coefficients, E_KB, eigenvalue and norm checks\n"
                   << "       --photo-table[=emax:ne]: after Finished!, the photoionization cross section of every subshell at ne photoelectron energies in (0, emax] Ha (default 4:8)\n"
                   << "       --charge=q: the cation (q > 0); --config: an electron configuration, fractional occupations allowed\n";
         return 2;

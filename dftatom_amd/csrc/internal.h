@@ -236,6 +236,17 @@ struct dfta_continuum_out {
 };
 int dfta_continuum_run(dfta_ctx* ctx, const dfta_grid* g, const dfta_continuum_plan::Call& c, const double* dV, const double* dP,
                        const dfta_continuum_out& out);
+// pseudo.hip: the pseudization of nch validated channels (pseudo_plan.h: check) whose rows dV, dU and tables dL, dEps,
+// dIc are on the device; every output is a host pointer and may be null.  One launch; copies the results back and synchronises;
+// records the launch's time for dfta_ctx_last_kernel_ms
+struct dfta_pseudize_out {
+    double *u_ps, *V_ps;           // nch x N
+    double *coef, *rc, *match;     // nch x DFTA_PS_COEF, nch, nch x DFTA_PS_MATCH
+    int *iters, *status;
+};
+// dVrow, dUrow (device, may be null): per channel the row of dV and of dU that it reads -- resident rows are read in place
+int dfta_pseudize_run(dfta_ctx* ctx, const dfta_grid* g, int nch, const double* dV, const int* dVrow, const double* dU, const int* dUrow,
+                      const int* dL, const double* dEps, const int* dIc, const dfta_pseudize_out& out);
 // kli_stage.hip: the budget of a chunk's y rows in MiB: DFTA_DEBUG KLI_Y_MB, or the default
 double dfta_kli_budget_mb();
 // scf.hip: the k_mix launch (DFTA_MIX_LINEAR), same arguments

@@ -10,6 +10,7 @@
 #include "bessel_plan.h"
 #include "continuum_plan.h"
 #include "exchange_plan.h"
+#include "pseudo_plan.h"
 #include "scf_state.h"
 #include "slater_plan.h"
 #include "xc.h"             // dfta_poisson_group_state
@@ -533,6 +534,77 @@ int dfta_scf_continuum(dfta_scf* s, int norm_mode, int ntrials, const int* atom,
             }
         }
     return DFTA_OK;
+}
+
+// ---- pseudopotentials of the batch's valence levels (pseudo.hip; the resident orbitals and potentials are read in place) -----------------
+int dfta_scf_pseudopotentials(dfta_scf* s, int nch, const int* atom, const int* level, const int* ic, double factor, const int* l_loc,
+                              int* ic_used, double* u_ps, double* V_ps, double* coef, double* rc, double* match, int* iters, int* status,
+                              double* rho_v, double* vH, double* vxc, double* V_ion, double* beta, double* kb)
+{
+    if (!s) return DFTA_ERR_INVALID;
+    dfta_ctx* ctx = s->ctx;
+    DFTA_ENTER(ctx);
+    DFTA_REQUIRE(ctx, nch >= 0, "dfta_scf_pseudopotentials: nch");
+    DFTA_REQUIRE(ctx, !s->lsda, "dfta_scf_pseudopotentials: spin-polarised batches are out of scope");
+    DFTA_REQUIRE(ctx, s->exchange_mode == DFTA_EXCHANGE_FUNCTIONAL, "dfta_scf_pseudopotentials: exchange mode must be DFTA_EXCHANGE_FUNCTIONAL");
+    DFTA_REQUIRE(ctx, s->steps_done > 0, "no SCF step has run yet: there are no orbitals");
+    DFTA_REQUIRE(ctx, s->functional == DFTA_XC_VWN || s->functional == DFTA_XC_PW92 || s->functional == DFTA_XC_PBE,
+                 "dfta_scf_pseudopotentials: functional (VWN, PW92 or PBE)");
+    if (nch == 0) return DFTA_OK;
+    DFTA_REQUIRE(ctx, atom && level, "dfta_scf_pseudopotentials arguments");
+    const size_t N = s->g->N;
+    hipStream_t st = ctx->stream;
+    // the channels' rows, and the atoms in use numbered in the order of their first channel
+    std::vector<int> vrow(nch), urow(nch), l(nch), local(nch), order;
+    std::vector<double> eps(nch), occ(nch);
+    for (int k = 0; k < nch; ++k) {
+        DFTA_REQUIRE(ctx, atom[k] >= 0 && atom[k] < s->natoms, "dfta_scf_pseudopotentials: atom");
+        const auto [k0, cnt] = s->channel(atom[k], 0);
+        DFTA_REQUIRE(ctx, level[k] >= 0 && level[k] < cnt, "dfta_scf_pseudopotentials: level");
+        const dfta::Job& j = s->h_jobs[k0 + level[k]];
+        DFTA_REQUIRE(ctx, j.l <= dfta_pseudo_plan::kLmax, "pseudize: l outside 0 .. 4");
+        DFTA_REQUIRE(ctx, s->solver.h_occ[k0 + level[k]] > 0., "dfta_scf_pseudopotentials: an unoccupied level");
+        vrow[k] = atom[k]; urow[k] = k0 + level[k]; l[k] = j.l; eps[k] = j.E; occ[k] = s->solver.h_occ[k0 + level[k]];
+        const int at = (int)(std::find(order.begin(), order.end(), atom[k]) - order.begin());
+        if (at == (int)order.size()) order.push_back(atom[k]);
+        local[k] = at;
+    }
+    std::vector<int> icv(nch);
+    if (ic) icv.assign(ic, ic + nch);
+    else {                                           // the default core nodes: the rule reads the orbitals on the host
+        std::vector<double> u(N);
+        for (int k = 0; k < nch; ++k) {
+            DFTA_HIP(ctx, hipMemcpyAsync(u.data(), s->solver.d_Psi + (size_t)urow[k] * N, sizeof(double) * N, hipMemcpyDeviceToHost, st));
+            DFTA_HIP(ctx, hipStreamSynchronize(st));
+            icv[k] = dfta_pseudo_plan::default_ic(s->g->N, s->g->h_r.data(), u.data(), factor);
+            DFTA_REQUIRE(ctx, icv[k] >= 0, "dfta_scf_pseudopotentials: factor");
+        }
+    }
+    dfta_pseudo_plan::Call c;
+    c.N = s->g->N; c.nch = nch; c.l = l.data(); c.ic = icv.data();
+    if (const char* msg = dfta_pseudo_plan::check(c)) DFTA_REQUIRE(ctx, false, msg);
+    if (ic_used) std::copy(icv.begin(), icv.end(), ic_used);
+    DevBuf<int> dVrow, dUrow, dL, dIc;
+    DevBuf<double> dEps;
+    int e = dfta_upload_rows(ctx, vrow.data(), (size_t)nch, &dVrow);
+    if (!e) e = dfta_upload_rows(ctx, urow.data(), (size_t)nch, &dUrow);
+    if (!e) e = dfta_upload_rows(ctx, l.data(), (size_t)nch, &dL);
+    if (!e) e = dfta_upload_rows(ctx, icv.data(), (size_t)nch, &dIc);
+    if (!e) e = dfta_upload_rows(ctx, eps.data(), (size_t)nch, &dEps);
+    if (e) return e;
+    const bool ionic = rho_v || vH || vxc || V_ion || beta || kb;
+    std::vector<double> hu, hv, hc;                  // the unscreening reads these three: the caller's arrays, or these
+    if (ionic && !u_ps) { hu.resize(nch * N); u_ps = hu.data(); }
+    if (ionic && !V_ps) { hv.resize(nch * N); V_ps = hv.data(); }
+    if (ionic && !coef) { hc.resize((size_t)nch * DFTA_PS_COEF); coef = hc.data(); }
+    dfta_pseudize_out out;
+    out.u_ps = u_ps; out.V_ps = V_ps; out.coef = coef; out.rc = rc; out.match = match; out.iters = iters; out.status = status;
+    if ((e = dfta_pseudize_run(ctx, s->g, nch, s->d_V, dVrow.p, s->solver.d_Psi, dUrow.p, dL.p, dEps.p, dIc.p, out))) return e;
+    if (!ionic) return DFTA_OK;
+    std::vector<double> a0(nch);
+    for (int k = 0; k < nch; ++k) a0[k] = coef[(size_t)k * DFTA_PS_COEF];
+    return dfta_pseudo_ionic(ctx, s->g, s->functional, (int)order.size(), nch, local.data(), l.data(), occ.data(), a0.data(), u_ps, V_ps, l_loc,
+                             rho_v, vH, vxc, V_ion, beta, kb);
 }
 
 int dfta_scf_photoionization(dfta_scf* s, int atom, int neps, const double* eps, int norm_mode, double* omega_out, double* sigma_out)

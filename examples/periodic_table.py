@@ -71,6 +71,9 @@ def main():
     ap.add_argument("--photo", action="store_true",
                     help="after the table, the photoionization cross section (megabarn) of every atom's outermost subshell at the photoelectron "
                          "energies 0.25, 0.5 .. 2 Ha, one launch per atom: Scf.photoionization()")
+    ap.add_argument("--pseudo", action="store_true",
+                    help="after the table, the Troullier-Martins pseudopotentials of every atom's default valence levels, all atoms of a rank in one "
+                         "call: r_c, a2, E_KB and the norm residual per channel (LDA / GGA only): Scf.pseudopotentials()")
     ap.add_argument("--lsda", action="store_true", help="spin-polarised (LSDA) instead of LDA")
     ap.add_argument("--ionization", action="store_true",
                     help="first ionization energies: the neutral atom and the +1 cation of every Z of a rank's shard advance in one batch; "
@@ -225,6 +228,18 @@ def main():
             parts = [None] * world
             dist.all_gather_object(parts, photo)
             photo = {z: v for p in parts for z, v in p.items()}
+    pseudo = {}
+    if args.pseudo and not args.lsda and args.exchange == "functional":      # every channel of this rank's batch in one call
+        ps = scf.pseudopotentials()
+        for k in range(len(ps["atom"])):
+            lv = scf.levels(int(ps["atom"][k]), 0)
+            pseudo.setdefault(int(mine[ps["atom"][k]]), []).append(
+                {"n": int(lv["n"][ps["level"][k]]) + 1, "l": int(ps["l"][k]), "status": int(ps["status"][k]), "rc": float(ps["rc"][k]),
+                 "a2": float(ps["coef"][k][1]), "E_KB": float(ps["kb"][k][2]), "norm_residual": float(ps["match"][k][7])})
+        if world > 1:
+            parts = [None] * world
+            dist.all_gather_object(parts, pseudo)
+            pseudo = {z: v for p in parts for z, v in p.items()}
     block = torch.zeros((cap, D.RECORD_DOUBLES), dtype=torch.float64, device="cuda")
     scf.records_into(block.data_ptr())          # rows beyond len(mine) stay zero (Z = 0: no atom)
     ctx.synchronize()
@@ -253,6 +268,10 @@ def main():
             if t:
                 for om, sg in zip(t["omega"], t["sigma_Mb"]):
                     print("Z %3d  Photo %d%s omega = %.6f sigma = %.6f Mb" % (r["Z"], t["n"], "spdf"[t["l"]], om, sg))
+        for r in rows:                          # the pseudopotential of every default valence level, per atom
+            for t in pseudo.get(r["Z"], []):
+                print("Z %3d  Pseudo %d%s status = %d rc = %.6f a2 = %.6f EKB = %.6f norm = %.2e"
+                      % (r["Z"], t["n"], "spdfg"[t["l"]], t["status"], t["rc"], t["a2"], t["E_KB"], t["norm_residual"]))
         print("%d atoms, %d GPU(s), %d SCF steps of the longest-running atom of rank 0, %d atom-steps in all, %d finished, %.1f s"
               % (len(rows), world, steps, sum(r["steps"] for r in rows), sum(r["finished"] for r in rows), elapsed))
         if args.out:
@@ -263,7 +282,8 @@ def main():
                                           **({"exx": exx[r["Z"]]} if r["Z"] in exx else {}),
                                           **({"kli": kli[r["Z"]]} if r["Z"] in kli else {}),
                                           **({"form_factor": ff[r["Z"]]} if r["Z"] in ff else {}),
-                                          **({"photoionization": photo[r["Z"]]} if r["Z"] in photo else {})) for r in rows]},
+                                          **({"photoionization": photo[r["Z"]]} if r["Z"] in photo else {}),
+                                          **({"pseudopotential": pseudo[r["Z"]]} if r["Z"] in pseudo else {})) for r in rows]},
                           f, indent=1)
     scf.close()
     grid.close()

@@ -804,6 +804,102 @@ int  dfta_scf_continuum(dfta_scf* s, int norm_mode, int ntrials, const int* atom
  * S_{l+1} term for l = 4.  omega_out, sigma_out: njobs_of_the_atom x neps.  A trial with a status bit makes its sigma NaN. */
 int  dfta_scf_photoionization(dfta_scf* s, int atom, int neps, const double* eps, int norm_mode, double* omega_out, double* sigma_out);
 
+/* ---- Troullier-Martins pseudization of valence orbitals (beyond the reference) ------------------------------------------------------------
+ * N. Troullier and J. L. Martins, Phys. Rev. B 43, 1993 (1991).  One channel = a valence level (l, eps, u = r R of N doubles) in a
+ * screened all-electron potential V (N doubles, Hartree: -u''/2 + [l(l+1)/2r^2 + V] u = eps u) and a core node ic, 3 <= ic <= N-4,
+ * r_c = r_ic; 0 <= l <= 4.  Tables s_i = dr/di and lam of the continuum block.  sigma = 1 if u_ic > 0, else -1.
+ *   outside, i >= ic:  u_ps,i = sigma u_i,  V_ps,i = V_i                                   (copies: bit for bit)
+ *   inside,  i <  ic:  x_i = r_i rinv, rinv = 1 / r_c;  t = x_i x_i;
+ *                      p = a0 + t (a2 + t (a4 + t (a6 + t (a8 + t (a10 + t a12)))));
+ *                      u_ps,i = rp_i exp(p), rp_i = r_i^(l+1) by l products from r_i       (u_ps,0 = 0)
+ *                      q = cq_1 + t (cq_2 + t (.. + t cq_6)), cq_k = (2k) a_2k;   w likewise with cw_k = (2k (2k-1)) a_2k;
+ *                      V_ps,i = eps + (((l + 1) q) + ((w + t (q q)) 0.5)) / (r_c r_c)      (q = (p'/r) r_c^2, w = p'' r_c^2: no division
+ *                      by r; node 0: eps + (2l + 3) a2 / r_c^2)
+ * Matching values at r_c, with su_k = sigma u_{ic+k} and the five-point differences in the index
+ *   D1[f] = (8 (f_1 - f_-1) - (f_2 - f_-2)) / 12,   D2[f] = ((16 (f_1 + f_-1) - (f_2 + f_-2)) - 30 f_0) / 12,   s = s_ic:
+ *   u' = D1[su] / s;  V' = D1[V] / s;  V'' = (D2[V] - lam D1[V]) / (s s);  L = l + 1;  rcp = r_c^(l+1) by l products;
+ *   p0 = log(su_0 / rcp);  p1 = u' / su_0 - L / r_c;
+ *   p2 = ((2 (V_ic - eps)) - ((2 L) p1) / r_c) - p1 p1;
+ *   p3 = (((2 V') + ((2 L) p1) / rc2) - ((2 L) p2) / r_c) - (2 p1) p2;
+ *   p4 = ((((2 V'') - ((4 L) p1) / rc3) + ((4 L) p2) / rc2) - ((2 L) p3) / r_c) - (2 (p2 p2) + (2 p1) p3);
+ *   rc2 = r_c r_c, rc3 = rc2 r_c, rc4 = rc2 rc2;   P0 = p0, P1 = p1 r_c, P2 = p2 rc2, P3 = p3 rc3, P4 = p4 rc4    (derivatives in x).
+ * Coefficients of a trial a2:  a4 = -((a2 a2) / (2l + 5))        (zero curvature of V_ps at the origin: a2^2 + (2l+5) a4 = 0)
+ *   b = (P0 - (a2 + a4), P1 - (2 a2 + 4 a4), P2 - (2 a2 + 12 a4), P3 - 24 a4, P4 - 24 a4); the unknowns (a0, a6, a8, a10, a12) solve
+ *   the rows (1 1 1 1 1), (0 6 8 10 12), (0 30 56 90 132), (0 120 336 720 1320), (0 360 1680 5040 11880) = b by Gaussian elimination
+ *   on the augmented matrix: for column k = 0 .. 4, each row i = k+1 .. 4 in turn changes places with row k if |A_ik| > |A_kk|; then
+ *   m = A_ik / A_kk, A_ij = A_ij - m A_kj for j = k+1 .. 5; back substitution x_k = (A_k5 - A_k,k+1 x_k+1 - .. ) / A_kk, the products
+ *   subtracted in ascending j.
+ * Norm: f_i = (u_i u_i) s_i with u the all-electron orbital (I_AE) or u_ps below ic and u from ic on (I_ps); d_i the increment of the
+ *   cumulative integral of the screening block (1 <= i <= ic: it reads f_{i-2} .. f_{i+1}; i = 1: f_0 .. f_3); lane t of 256 adds d_i of
+ *   the nodes i = t, t + 256, .. in order from 0.0, then the tree of the orbital block (xor shuffles 32 .. 1, (w0 + w1) + (w2 + w3)).
+ *   g(a2) = log(I_ps(a2)) - log(I_AE).
+ * Root search, sgn(g) in {-1, 0, 1}, a NaN g is no sign:  g(0) NaN: DFTA_PS_NOBRACKET.  sgn g(0) = 0: a2 = 0.  Otherwise bracket: for
+ *   h = 1/4, 1/2, 1, .. (24 values) evaluate g(h), then g(-h); the first value that is not NaN and whose sign differs from g(0)'s closes
+ *   the bracket: hi = that a2, lo = the last a2 of the same side whose g was not NaN (0 at the start).  None: DFTA_PS_NOBRACKET.
+ *   Bisection while g(hi) != 0: mid = lo + (hi - lo) 0.5; stop if mid == lo or mid == hi (no double between the ends); stop with
+ *   DFTA_PS_CAP if 200 evaluations were made; a NaN g(mid): DFTA_PS_NOBRACKET; mid replaces lo if sgn g(mid) = sgn g(0), else hi.  The
+ *   end of smaller |g| is kept (lo on a tie); one more evaluation there gives the coefficients, I_ps and g that are returned.  iters
+ *   counts every evaluation.
+ * status (0: fine): DFTA_PS_NOBRACKET, DFTA_PS_CAP; DFTA_PS_NODES -- ic is not beyond the last i >= 2 where u_i and b are of strictly
+ *   opposite sign, b = u_{i-1}, or u_{i-2} where u_{i-1} is exactly zero; or u_ic = 0; DFTA_PS_NONFINITE -- eps or a node of u or V is not finite (the only bit then); DFTA_PS_NOTPOSITIVE --
+ *   u_ps,i > 0 and finite failed for an i in 1 .. ic-1.  With any bit set every floating-point output of the channel is NaN.
+ * match (DFTA_PS_MATCH doubles per channel): P0 .. P4, I_AE, I_ps, g.  coef: a0, a2, .., a12.
+ * One workgroup of 256 lanes per channel, one launch per call, no atomics: a channel's bits depend on its own rows, l, eps, ic and
+ * the grid -- not on the other channels, their number or order, or the run.  DFTA_ERR_INVALID: a NULL input, an l outside 0 .. 4, an ic
+ * outside 3 .. N-4, N < 8.  nch == 0: DFTA_OK, nothing is written.  Records the launch's time for dfta_ctx_last_kernel_ms. */
+#define DFTA_PS_COEF  7
+#define DFTA_PS_MATCH 8
+#define DFTA_PS_NOBRACKET   1
+#define DFTA_PS_CAP         2
+#define DFTA_PS_NODES       4
+#define DFTA_PS_NONFINITE   8
+#define DFTA_PS_NOTPOSITIVE 16
+/* host pointers.  V, u: nch x N (a row of each per channel); l, eps, ic: nch.  Outputs, any of which may be NULL: u_ps, V_ps nch x N;
+ * coef nch x 7; rc nch; match nch x 8; iters, status nch. */
+int  dfta_pseudize(dfta_ctx* ctx, const dfta_grid* g, int nch, const double* V, const double* u, const int* l, const double* eps,
+                   const int* ic, double* u_ps, double* V_ps, double* coef, double* rc, double* match, int* iters, int* status);
+/* Unscreening and Kleinman-Bylander quantities of pseudized channels; host pointers.  Channel k belongs to atom[k] (0 .. natoms-1) with
+ * occupation occ[k] > 0; u_ps, V_ps: nch x N (the rows of dfta_pseudize); a0: its first coefficient per channel.  K the double nearest
+ * 4 pi; sums over the channels of an atom in the order of the call, one accumulator from 0.0, every product rounded on its own:
+ *   rho_v,i = Sum occ ((u u) / ((K r_i) r_i)) for i >= 1;  node 0: the term is exp(2 a0) / K for l = 0 and 0.0 otherwise
+ *   y_k     = y^0_kk: the row of job (k, k, 0) of dfta_screening_yk on the pseudo-orbitals, bit for bit;  vH,i = Sum occ y_k,i
+ *   vxc     = Vexc of the functional's own launcher on rho_v (natoms x N): DFTA_XC_VWN, DFTA_XC_PW92, or DFTA_XC_PBE (logarithmic grid)
+ *   V_ion,k = (V_ps,k - vH) - vxc              no nonlinear core correction
+ *   local channel of an atom: the first channel with l = l_loc[atom]; l_loc NULL or negative: the first channel of its highest l
+ *   beta_k  = (V_ion,k - V_ion,loc) u_ps,k     (V_ion,loc formed again from the local channel's V_ps: the same bits)
+ *   q1 = <u|dV|u> = Q[(beta u) s], q2 = <u|dV^2|u> = Q[(beta beta) s] with the weights and the fixed 256-lane tree of the orbital block;
+ *   kb (3 doubles per channel): q1, q2, E_KB = q2 / q1 (the local channel: 0, 0, NaN).  The normalised projector is beta / sqrt(q2).
+ * Outputs, any of which may be NULL: rho_v, vH, vxc natoms x N; V_ion, beta nch x N; kb nch x 3.  Launches: the y jobs, the density, the
+ * functional, the pointwise pass, the quadratures; no atomics, shapes depend on N alone.  An atom's bits do not depend on the other
+ * atoms of the call.  DFTA_ERR_INVALID: a NULL input, an atom index out of range, an l outside 0 .. 4, an occupation that is not
+ * positive (an unoccupied level), an atom without channels or without a channel of its l_loc, another functional, N < 8. */
+int  dfta_pseudo_ionic(dfta_ctx* ctx, const dfta_grid* g, int functional, int natoms, int nch, const int* atom, const int* l, const double* occ,
+                       const double* a0, const double* u_ps, const double* V_ps, const int* l_loc, double* rho_v, double* vH, double* vxc,
+                       double* V_ion, double* beta, double* kb);
+/* ... of levels of the batch, orbitals and potentials read in place on the device: channel k is level level[k] (the index within
+ * dfta_scf_get_levels(atom[k], 0)) of atom[k]; l, eps and the occupation are the level's.  WHICH POTENTIAL: the resident one, the array
+ * dfta_scf_get_array(.., 3) returns at the time of the call -- after a step that is the NEXT step's input, while the orbitals are
+ * eigenfunctions of the last step's input potential (the orbital block's warning), which the SCF does not keep; at convergence the two
+ * agree to the SCF's tolerance, and the mismatch enters V_ps inside r_c through p''.  The result is bit for bit dfta_pseudize on
+ * dfta_scf_get_orbitals and dfta_scf_get_array(.., 3), then dfta_pseudo_ionic with the SCF's functional.  A frozen atom keeps its
+ * orbitals and its potential, hence every bit of its channels.  ic NULL: the core nodes of dfta_pseudo_default_ic(factor); ic_used
+ * (may be NULL): the core nodes used.  The atoms in use are numbered in the order of their first channel: l_loc (NULL: the highest l)
+ * and the rows of rho_v, vH, vxc follow that numbering.  Any output may be NULL; without an output of dfta_pseudo_ionic only the
+ * pseudization runs.  DFTA_ERR_INVALID: an LSDA batch, an exchange mode other than DFTA_EXCHANGE_FUNCTIONAL, a functional other than
+ * VWN, PW92, PBE, a call before the first dfta_scf_step, an atom or level out of range, an unoccupied level, and what dfta_pseudize and
+ * dfta_pseudo_ionic refuse (l > 4, ic closer than 3 nodes to an end). */
+int  dfta_scf_pseudopotentials(dfta_scf* s, int nch, const int* atom, const int* level, const int* ic, double factor, const int* l_loc,
+                               int* ic_used, double* u_ps, double* V_ps, double* coef, double* rc, double* match, int* iters, int* status,
+                               double* rho_v, double* vH, double* vxc, double* V_ion, double* beta, double* kb);
+/* the valence levels of a configuration (host integers only): for each l the level with occ > 0 of largest n, kept if
+ * n >= n_max - max(0, l - 1), n_max the largest n with occ > 0 (Fe: 3d 4s; Ar: 3s 3p).  pick: the kept indices into the list, ascending
+ * in l; npick: their number.  DFTA_ERR_INVALID: a NULL pointer, a negative l, more than cap levels kept. */
+int  dfta_pseudo_default_valence(int nlev, const int* n, const int* l, const int* occ, int cap, int* pick, int* npick);
+/* the default core node of each of nch orbitals u (nch x N, host): the node whose r is nearest to factor x r_peak (r_peak: DFTA_ORB_RPEAK's
+ * definition, the lower node on a tie), moved outwards until it lies beyond the last sign change of u and u is non-zero there, clamped
+ * to 3 .. N-4.  Host only.  DFTA_ERR_INVALID: a NULL pointer, a factor that is not finite and positive, N < 8. */
+int  dfta_pseudo_default_ic(const dfta_grid* g, int nch, const double* u, double factor, int* ic);
+
 /* ---- Aufbau -------------------------------------------------------------------------------------------------
  * AufbauPrinciple::GetSubshells + sort (AufbauPrinciple.h:36-75, DFTAtom.cpp:367); integer-only host code. */
 int dfta_get_subshells(int Z, int* n, int* l, int* occ, int cap);
