@@ -46,6 +46,8 @@ CONT_MAX_PARTNERS = 16                 # DFTA_CONT_MAX_PARTNERS: partners of one
 CONT_NONFINITE, CONT_STEP, CONT_WKB_TAIL = 1, 2, 4      # status bits of a continuum trial
 PS_COEF, PS_MATCH = 7, 8               # DFTA_PS_*: a0, a2 .. a12 of a pseudized channel; P0 .. P4, I_AE, I_ps, g
 PS_NOBRACKET, PS_CAP, PS_NODES, PS_NONFINITE, PS_NOTPOSITIVE = 1, 2, 4, 8, 16      # status bits of a pseudized channel
+KB_MAX_STATES, KB_REPORT = 8, 10       # DFTA_KB_*: bound states of a channel; doubles of a channel's ghost report
+KB_SEARCH_NONFINITE, KB_SEARCH_FULL, KB_SEARCH_CAP = 1, 2, 4      # status bits of kb_bound_states
 
 c_dp = C.POINTER(C.c_double)
 c_ip = C.POINTER(C.c_int)
@@ -203,6 +205,11 @@ SIGNATURES = {
                                   + [c_dp] * 6),
     "dfta_pseudo_default_valence": (C.c_int, [C.c_int, c_ip, c_ip, c_ip, C.c_int, c_ip, c_ip]),
     "dfta_pseudo_default_ic": (C.c_int, [vp, C.c_int, c_dp, C.c_double, c_ip]),
+    "dfta_kb_sweep": (C.c_int, [vp, vp, C.c_int, c_dp, C.c_int, c_ip, c_ip, c_dp, c_dp, C.c_int, c_ip, c_dp, c_ip] + [c_dp] * 6 + [c_ip, c_dp]),
+    "dfta_kb_bound_states": (C.c_int, [vp, vp, C.c_int, c_dp, C.c_int, c_ip, c_ip, c_dp, c_dp, c_ip, c_dp, c_dp, C.c_int, c_ip, c_dp, c_ip,
+                                       c_ip]),
+    "dfta_kb_ghost_report": (C.c_int, [vp, vp, C.c_int, C.c_int, c_ip, c_ip, c_dp, c_dp, c_dp, c_dp, c_ip, C.c_int, C.c_double, C.c_double,
+                                       C.c_int, C.c_double, c_dp, c_dp]),
 }
 
 _lib = None
@@ -886,6 +893,80 @@ def default_ic(grid, u, factor=1.5):
     return ic
 
 
+def _kb_channels(grid, V, l, beta, q1, vidx):
+    V = _f64(V).reshape(-1, grid.N)
+    beta = _f64(beta).reshape(-1, grid.N)
+    l, q1 = _i32(np.atleast_1d(l)), _f64(np.atleast_1d(q1))
+    nch = beta.shape[0]
+    if not (len(l) == len(q1) == nch):
+        raise ValueError("kb: %d projectors, %d l, %d q1" % (nch, len(l), len(q1)))
+    vidx = None if vidx is None else _i32(np.broadcast_to(vidx, (nch,)))
+    return V, l, beta, q1, vidx, nch
+
+
+def kb_sweep(ctx, grid, V, l, beta, q1, E, m=None, chan=None, vidx=None, want_rows=False):
+    """dfta_kb_sweep: outward solves of (H_loc + |beta><beta| / q1 - E) u = 0.  V: (nV, N) local potentials; per channel l, a row of beta
+    (nch, N), q1 and vidx (None: 0); per trial E, the end node m (None: N-2; at or beyond the last non-zero node of beta) and chan
+    (None: 0).  Returns "u" and "du" (u~ and u~' at r_m), "logderiv", "Bh", "Bp", "D", "status" (CONT_NONFINITE, CONT_STEP) and, on
+    request, "rows" (ntrials, N)."""
+    V, l, beta, q1, vidx, nch = _kb_channels(grid, V, l, beta, q1, vidx)
+    E = _f64(np.atleast_1d(E))
+    nt = len(E)
+    m = np.full(nt, grid.N - 2, np.int32) if m is None else _i32(np.broadcast_to(m, (nt,)))
+    chan = None if chan is None else _i32(np.broadcast_to(chan, (nt,)))
+    out = {k: np.zeros(nt) for k in ("u", "du", "logderiv", "Bh", "Bp", "D")}
+    out["status"] = np.zeros(nt, np.int32)
+    if want_rows:
+        out["rows"] = np.zeros((nt, grid.N))
+    ptr = lambda a, f: None if a is None else f(a)       # noqa: E731
+    ctx.check(ctx.lib.dfta_kb_sweep(ctx.h, grid.h, V.shape[0], _dp(V), nch, ptr(vidx, _ip), _ip(l), _dp(beta), _dp(q1), nt, ptr(chan, _ip),
+                                    _dp(E), _ip(m), _dp(out["u"]), _dp(out["du"]), _dp(out["logderiv"]), _dp(out["Bh"]), _dp(out["Bp"]),
+                                    _dp(out["D"]), _ip(out["status"]), ptr(out.get("rows"), _dp)))
+    return out
+
+
+def kb_bound_states(ctx, grid, V, l, beta, q1, E_lo, E_hi, m=None, vidx=None, nscan=256):
+    """dfta_kb_bound_states: the bound states of H_KB of every channel between E_lo and E_hi (per channel or one for all) in the box that
+    ends at node m (None: N-2), by the sign of u~_m(E).  Returns "count", "energies" (nch, 8; NaN beyond count), "rounds", "status"
+    (KB_SEARCH_* bits)."""
+    V, l, beta, q1, vidx, nch = _kb_channels(grid, V, l, beta, q1, vidx)
+    m = np.full(nch, grid.N - 2, np.int32) if m is None else _i32(np.broadcast_to(m, (nch,)))
+    lo, hi = _f64(np.broadcast_to(E_lo, (nch,))), _f64(np.broadcast_to(E_hi, (nch,)))
+    out = {"count": np.zeros(nch, np.int32), "energies": np.zeros((nch, KB_MAX_STATES)), "rounds": np.zeros(nch, np.int32),
+           "status": np.zeros(nch, np.int32)}
+    ctx.check(ctx.lib.dfta_kb_bound_states(ctx.h, grid.h, V.shape[0], _dp(V), nch, None if vidx is None else _ip(vidx), _ip(l), _dp(beta),
+                                           _dp(q1), _ip(m), _dp(lo), _dp(hi), int(nscan), _ip(out["count"]), _dp(out["energies"]),
+                                           _ip(out["rounds"]), _ip(out["status"])))
+    return out
+
+
+def kb_ghost_report(ctx, grid, ps, l=None, eps=None, atom=None, l_loc=None, m=None, E_lo=None, E_hi=0.0, nscan=512, tol=1e-5):
+    """dfta_kb_ghost_report on the output `ps` of Scf.pseudopotentials(), or of pseudize() merged with pseudo_ionic() (then l, eps and
+    atom per channel are given here; atom None: one atom).  l_loc as it was given to them.  Per channel (NaN for the local one):
+    "eps_ref", "E_KB", "bound" (the states of H_KB in [E_lo, min(0, E_hi)] with the box at node m, None: N-2; E_lo None: per channel
+    the bound below which H_KB has no state), "ghosts" (how many lie
+    below eps_ref - tol), "e_loc" (nch, 2: the two lowest levels of the local potential at l), "gks" and "direct" (the two verdicts:
+    1 ghost, 0 clean, -1 none), "status", "rounds"."""
+    V, beta, kb = (_f64(ps[k]) for k in ("V_ps", "beta", "kb"))
+    V, beta, kb = V.reshape(-1, grid.N), beta.reshape(-1, grid.N), kb.reshape(-1, 3)
+    nch = V.shape[0]
+    l = _i32(np.atleast_1d(ps["l"] if l is None else l))
+    eps = _f64(np.atleast_1d(ps["eps"] if eps is None else eps))
+    if atom is None:
+        atom = ps["atom"] if "atom" in ps else np.zeros(nch, np.int32)
+    seen = {}
+    atom = _i32([seen.setdefault(int(a), len(seen)) for a in np.atleast_1d(atom)])      # numbered by first channel, as l_loc's rows
+    natoms = int(atom.max()) + 1 if nch else 0
+    ll = None if l_loc is None else _i32(np.broadcast_to(l_loc, (natoms,)))
+    rep, st = np.zeros((nch, KB_REPORT)), np.zeros((nch, KB_MAX_STATES))
+    ctx.check(ctx.lib.dfta_kb_ghost_report(ctx.h, grid.h, natoms, nch, _ip(atom), _ip(l), _dp(eps), _dp(V), _dp(beta), _dp(kb),
+                                           None if ll is None else _ip(ll), int(grid.N - 2 if m is None else m), float("nan" if E_lo is None else E_lo),
+                                           float(E_hi), int(nscan), float(tol), _dp(rep), _dp(st)))
+    flag = lambda x: np.where(np.isnan(x), -1, np.nan_to_num(x)).astype(np.int32)      # noqa: E731
+    return {"eps_ref": rep[:, 0], "E_KB": rep[:, 1], "bound": [row[~np.isnan(row)] for row in st], "ghosts": flag(rep[:, 3]),
+            "e_loc": rep[:, 4:6], "gks": flag(rep[:, 6]), "direct": flag(rep[:, 7]), "status": flag(rep[:, 8]), "rounds": flag(rep[:, 9])}
+
+
 class Mixer:
     """The SCF's density-mixing stage on its own (dfta_mixer): the launches dfta_scf_step issues for `mixing`, on the caller's arrays."""
 
@@ -1171,6 +1252,11 @@ class Scf:
             _dp(out["u_ps"]), _dp(out["V_ps"]), _dp(out["coef"]), _dp(out["rc"]), _dp(out["match"]), _ip(out["iters"]), _ip(out["status"]),
             _dp(out["rho_v"]), _dp(out["vH"]), _dp(out["vxc"]), _dp(out["V_ion"]), _dp(out["beta"]), _dp(out["kb"])))
         return out
+
+    def kb_ghost_report(self, atoms=None, levels=None, ic=None, factor=1.5, l_loc=None, **search):
+        """pseudopotentials(...) and then kb_ghost_report() on them (search: m, E_lo, E_hi, nscan, tol).  Returns (report, ps)."""
+        ps = self.pseudopotentials(atoms, levels, ic, factor, l_loc)
+        return kb_ghost_report(self.ctx, self.grid, ps, l_loc=l_loc, **search), ps
 
     def photoionization(self, eps, atom=0, norm="auto"):
         """dfta_scf_photoionization: {"omega", "sigma"} (subshells of the atom, neps) -- photon energies eps - E_nl (Ha) and cross

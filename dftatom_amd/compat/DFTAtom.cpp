@@ -33,6 +33,10 @@ double DFTAtom::phaseShiftEmax = 2.0;
 int DFTAtom::phaseShiftPoints = 8;
 bool DFTAtom::pseudoTable = false;         // --pseudo-table[=factor]
 double DFTAtom::pseudoFactor = 1.5;
+bool DFTAtom::kbTable = false;             // --kb-table[=elo:ehi:ne]
+double DFTAtom::kbElo = -2.0;
+double DFTAtom::kbEhi = 1.0;
+int DFTAtom::kbPoints = 7;
 bool DFTAtom::photoTable = false;          // --photo-table[=emax:ne]
 double DFTAtom::photoEmax = 4.0;
 int DFTAtom::photoPoints = 8;
@@ -315,6 +319,73 @@ void print_pseudo_table(dfta_scf* scf, dfta_ctx* ctx, const dfta_grid* grid, boo
     std::cout << std::endl;
 }
 
+// --kb-table: the Kleinman-Bylander form of the default valence levels' pseudopotentials (the highest l local): per channel E_KB, the
+// bound states of H_KB below 0 in the box that ends at the last node but one, the two ghost verdicts (dfta_kb_ghost_report), then u'/u
+// at the atom's largest core radius in the all-electron potential, in V_ps,l and in H_KB at kbPoints energies in kbElo .. kbEhi
+void print_kb_table(dfta_scf* scf, dfta_ctx* ctx, const dfta_grid* grid, bool lsda, int N)
+{
+    if (lsda) {
+        std::cout << "KB: spin-polarised atoms are out of scope" << std::endl << std::endl;
+        return;
+    }
+    const std::vector<LevelLine> levels = fetch_levels(scf, 0);
+    const int nlev = (int)levels.size();
+    std::vector<int> n(nlev), l(nlev), occ(nlev), pick(nlev);
+    for (int k = 0; k < nlev; ++k) { n[k] = levels[k].n; l[k] = levels[k].l; occ[k] = levels[k].occ > 0. ? 1 : 0; }
+    int nch = 0;
+    if (dfta_pseudo_default_valence(nlev, n.data(), l.data(), occ.data(), nlev, pick.data(), &nch) != DFTA_OK)
+        throw std::runtime_error("dfta_pseudo_default_valence");
+    std::vector<int> atom(nch, 0), ic(nch), status(nch), lch(nch);
+    std::vector<double> Vps((size_t)nch * N), beta((size_t)nch * N), kb((size_t)nch * 3), eps(nch);
+    if (dfta_scf_pseudopotentials(scf, nch, atom.data(), pick.data(), nullptr, DFTAtom::pseudoFactor, nullptr, ic.data(), nullptr, Vps.data(), nullptr,
+                                  nullptr, nullptr, nullptr, status.data(), nullptr, nullptr, nullptr, nullptr, beta.data(), kb.data()) != DFTA_OK)
+        throw std::runtime_error(std::string("dfta_scf_pseudopotentials: ") + dfta_last_error(ctx));
+    int loc = 0, icmax = 0;
+    for (int k = 0; k < nch; ++k) {
+        lch[k] = levels[pick[k]].l; eps[k] = levels[pick[k]].E;
+        if (status[k]) { std::cout << "KB: the pseudization of a channel failed (status " << status[k] << ")" << std::endl << std::endl; return; }
+        if (lch[k] > lch[loc]) loc = k;
+        icmax = std::max(icmax, ic[k]);
+    }
+    std::vector<double> report((size_t)nch * DFTA_KB_REPORT), states((size_t)nch * DFTA_KB_MAX_STATES);
+    if (dfta_kb_ghost_report(ctx, grid, 1, nch, atom.data(), lch.data(), eps.data(), Vps.data(), beta.data(), kb.data(), nullptr, N - 2, std::nan(""), 0., 512,
+                             1e-5, report.data(), states.data()) != DFTA_OK)
+        throw std::runtime_error(std::string("dfta_kb_ghost_report: ") + dfta_last_error(ctx));
+    std::vector<double> r(N);
+    dfta_grid_get_r(grid, r.data());
+    const int ne = DFTAtom::kbPoints;
+    std::vector<double> E(ne), ae(ne), sl(ne), nl(ne);
+    for (int j = 0; j < ne; ++j) E[j] = DFTAtom::kbElo + (DFTAtom::kbEhi - DFTAtom::kbElo) * j / (ne > 1 ? ne - 1 : 1);
+    for (int k = 0; k < nch; ++k) {
+        const LevelLine& lv = levels[pick[k]];
+        const double* rp = &report[(size_t)k * DFTA_KB_REPORT];
+        std::cout << "KB " << lv.n + 1 << DFTAtom::orb[lv.l] << std::fixed << std::setprecision(6);
+        if (k == loc) {
+            std::cout << " local" << std::endl;
+        } else {
+            std::cout << " EKB = " << rp[1] << " states =";
+            for (int q = 0; q < (int)rp[2]; ++q) std::cout << " " << states[(size_t)k * DFTA_KB_MAX_STATES + q];
+            std::cout << " eps = " << rp[0] << " local levels = " << rp[4] << " " << rp[5] << " GKS = " << (rp[6] != rp[6] ? -1 : (int)rp[6])
+                      << " direct = " << (int)rp[7] << " ghosts = " << (int)rp[3] << std::endl;
+        }
+        std::vector<int> zero(ne, 0), ll(ne, lv.l), mm(ne, icmax);
+        const double one = 1.;
+        std::vector<double> nobeta(N, 0.);
+        if (dfta_scf_continuum(scf, continuum_norm(), ne, zero.data(), zero.data(), ll.data(), E.data(), mm.data(), -1, ae.data(), nullptr, nullptr, nullptr,
+                               nullptr, nullptr, nullptr, nullptr) != DFTA_OK
+            || dfta_kb_sweep(ctx, grid, 1, Vps.data() + (size_t)k * N, 1, nullptr, &lv.l, nobeta.data(), &one, ne, nullptr, E.data(), mm.data(), nullptr,
+                             nullptr, sl.data(), nullptr, nullptr, nullptr, nullptr, nullptr) != DFTA_OK
+            || dfta_kb_sweep(ctx, grid, 1, Vps.data() + (size_t)loc * N, 1, nullptr, &lv.l, k == loc ? nobeta.data() : beta.data() + (size_t)k * N,
+                             k == loc ? &one : &kb[(size_t)k * 3], ne, nullptr, E.data(), mm.data(), nullptr, nullptr, nl.data(), nullptr, nullptr, nullptr,
+                             nullptr, nullptr) != DFTA_OK)
+            throw std::runtime_error(std::string("KB table: ") + dfta_last_error(ctx));
+        for (int j = 0; j < ne; ++j)
+            std::cout << "KB " << lv.n + 1 << DFTAtom::orb[lv.l] << " r = " << r[icmax] << " E = " << E[j] << " AE = " << ae[j] << " semilocal = " << sl[j]
+                      << " KB = " << nl[j] << std::endl;
+    }
+    std::cout << std::endl;
+}
+
 void print_configuration(std::vector<LevelLine> levels)
 {
     // levels sorted by energy for the final configuration line (DFTAtom.cpp:487-490)
@@ -381,6 +452,7 @@ void DFTAtom::Run(bool lsda, bool uniform, int Z, int MultigridLevels, double al
             if (phaseShiftTable) print_phase_shift_table(scf, grid, lsda);
             if (photoTable) print_photo_table(scf, lsda);
             if (pseudoTable) print_pseudo_table(scf, rt.ctx(), grid, lsda, dfta_num_nodes(MultigridLevels));
+            if (kbTable) print_kb_table(scf, rt.ctx(), grid, lsda, dfta_num_nodes(MultigridLevels));
             break;
         }
         std::cout << "********************************************************************************" << std::endl;

@@ -70,6 +70,9 @@ public:
     // factor x the radius of the orbital's largest |u| (dfta_scf_pseudopotentials): r_c, the coefficients, E_KB and two checks
     static bool pseudoTable;
     static double pseudoFactor;
+    static bool kbTable;
+    static double kbElo, kbEhi;
+    static int kbPoints;
     static double phaseShiftEmax, photoEmax;
     static int phaseShiftPoints, photoPoints;
 

@@ -29,6 +29,9 @@
 //                (Ha; default 2:8): the scattering phase shift delta_l(E) of the converged potential, u'/u at the last node but one and the
 //                node count of the outward solution (include/dftatom_hip.h: dfta_scf_continuum, one launch for the table).  With
 //                --charge, --config or --exchange=kli|sic the potential has a Coulomb tail: the column is the WKB phase instead.
+// --kb-table[=elo:ehi:ne]: after "Finished!" (and the other tables), the Kleinman-Bylander form of the default valence levels' pseudopotentials
+//                (the highest l local): per channel E_KB, the bound states of H_KB, both ghost verdicts (dfta_kb_ghost_report), then u'/u at
+//                the largest core radius in the all-electron potential, in V_ps,l and in H_KB at ne energies in elo .. ehi Ha (default -2:1:7).
 // --photo-table[=emax:ne]: then one line per subshell and photoelectron energy eps = emax k / ne (default 4:8): the photon energy
 //                omega = eps - E_nl and the photoionization cross section sigma_nl(omega) in a_0^2 and megabarn (dfta_scf_photoionization).
 //                Without them the output is unchanged.
@@ -147,6 +150,20 @@ int main(int argc, char** argv)
             }
             DFT::DFTAtom::pseudoTable = true;
             DFT::DFTAtom::pseudoFactor = f;
+        } else if (a == "--kb-table") {
+            DFT::DFTAtom::kbTable = true;
+        } else if (a.rfind("--kb-table=", 0) == 0) {
+            double elo = 0, ehi = 0;
+            int ne = 0;
+            char tail = 0;
+            if (std::sscanf(a.c_str() + 11, "%lf:%lf:%d%c", &elo, &ehi, &ne, &tail) != 3 || !(elo < ehi && elo >= -1e4 && ehi <= 1e4) || ne < 2 || ne > 100000) {
+                std::cerr << "bad KB table " << a.substr(11) << " (elo:ehi:ne, energies in Ha, ne >= 2 of them)" << std::endl;
+                return 2;
+            }
+            DFT::DFTAtom::kbTable = true;
+            DFT::DFTAtom::kbElo = elo;
+            DFT::DFTAtom::kbEhi = ehi;
+            DFT::DFTAtom::kbPoints = ne;
         } else if (a.rfind("--phase-shift-table=", 0) == 0 || a.rfind("--photo-table=", 0) == 0) {
             const bool photo = a.rfind("--photo-table=", 0) == 0;
             const std::string v = a.substr(a.find('=') + 1);
@@ -227,6 +244,7 @@ int main(int argc, char** argv)
                   << "       --form-factor-table[=smax:ns]: after Finished!, the X-ray form factor f(q) at ns values of s = sin(theta)/lambda in 0 .. smax 1/Angstrom (default 2:41)\n"
                   << "       --phase-shift-table[=emax:ne]: after Finished!, the scattering phase shifts delta_l(E), l = 0 .. 4, at ne energies in (0, emax] Ha (default 2:8), with u'/u and the node count\n"
                   << "       --pseudo-table[=factor]: after Finished!, the Troullier-Martins pseudopotentials of the default valence levels (LDA / GGA), r_c at factor x the radius of the orbital's largest |u| (default 1.5): r_c, coefficients, E_KB, eigenvalue and norm checks\n"
+                  << "       --kb-table[=elo:ehi:ne]: after Finished!, the Kleinman-Bylander form of those pseudopotentials: E_KB, the bound states of H_KB, the two ghost verdicts, and u'/u at r_c in the all-electron potential, in V_ps and in H_KB at ne energies in elo .. ehi Ha (default -2:1:7)\n"
                   << "       --photo-table[=emax:ne]: after Finished!, the photoionization cross section of every subshell at ne photoelectron energies in (0, emax] Ha (default 4:8)\n"
                   << "       --charge=q: the cation (q > 0); --config: an electron configuration, fractional occupations allowed\n";
         return 2;

@@ -74,6 +74,9 @@ def main():
     ap.add_argument("--pseudo", action="store_true",
                     help="after the table, the Troullier-Martins pseudopotentials of every atom's default valence levels, all atoms of a rank in one "
                          "call: r_c, a2, E_KB and the norm residual per channel (LDA / GGA only): Scf.pseudopotentials()")
+    ap.add_argument("--ghosts", action="store_true",
+                    help="after the table, the Kleinman-Bylander ghost report of those pseudopotentials (the highest l local): E_KB, the bound "
+                         "states of H_KB and both verdicts per non-local channel: Scf.kb_ghost_report()")
     ap.add_argument("--lsda", action="store_true", help="spin-polarised (LSDA) instead of LDA")
     ap.add_argument("--ionization", action="store_true",
                     help="first ionization energies: the neutral atom and the +1 cation of every Z of a rank's shard advance in one batch; "
@@ -240,6 +243,20 @@ def main():
             parts = [None] * world
             dist.all_gather_object(parts, pseudo)
             pseudo = {z: v for p in parts for z, v in p.items()}
+    ghosts = {}
+    if args.ghosts and not args.lsda and args.exchange == "functional":      # every non-local channel of this rank's batch: one search
+        rep, ps = scf.kb_ghost_report()
+        for k in range(len(ps["atom"])):
+            if rep["direct"][k] < 0 or ps["status"][k]:
+                continue                            # the local channel; a channel that was not pseudized
+            lv = scf.levels(int(ps["atom"][k]), 0)
+            ghosts.setdefault(int(mine[ps["atom"][k]]), []).append(
+                {"n": int(lv["n"][ps["level"][k]]) + 1, "l": int(ps["l"][k]), "eps": float(rep["eps_ref"][k]), "E_KB": float(rep["E_KB"][k]),
+                 "bound": [float(e) for e in rep["bound"][k]], "gks": int(rep["gks"][k]), "direct": int(rep["direct"][k])})
+        if world > 1:
+            parts = [None] * world
+            dist.all_gather_object(parts, ghosts)
+            ghosts = {z: v for p in parts for z, v in p.items()}
     block = torch.zeros((cap, D.RECORD_DOUBLES), dtype=torch.float64, device="cuda")
     scf.records_into(block.data_ptr())          # rows beyond len(mine) stay zero (Z = 0: no atom)
     ctx.synchronize()
@@ -272,6 +289,11 @@ def main():
             for t in pseudo.get(r["Z"], []):
                 print("Z %3d  Pseudo %d%s status = %d rc = %.6f a2 = %.6f EKB = %.6f norm = %.2e"
                       % (r["Z"], t["n"], "spdfg"[t["l"]], t["status"], t["rc"], t["a2"], t["E_KB"], t["norm_residual"]))
+        for r in rows:                          # the ghost report of every non-local channel, per atom
+            for t in ghosts.get(r["Z"], []):
+                print("Z %3d  Ghost %d%s eps = %.6f EKB = %.6f states = %s GKS = %d direct = %d%s"
+                      % (r["Z"], t["n"], "spdfg"[t["l"]], t["eps"], t["E_KB"], " ".join("%.6f" % e for e in t["bound"]), t["gks"], t["direct"],
+                         "  DISAGREE" if t["gks"] != t["direct"] else ""))
         print("%d atoms, %d GPU(s), %d SCF steps of the longest-running atom of rank 0, %d atom-steps in all, %d finished, %.1f s"
               % (len(rows), world, steps, sum(r["steps"] for r in rows), sum(r["finished"] for r in rows), elapsed))
         if args.out:
@@ -283,7 +305,8 @@ def main():
                                           **({"kli": kli[r["Z"]]} if r["Z"] in kli else {}),
                                           **({"form_factor": ff[r["Z"]]} if r["Z"] in ff else {}),
                                           **({"photoionization": photo[r["Z"]]} if r["Z"] in photo else {}),
-                                          **({"pseudopotential": pseudo[r["Z"]]} if r["Z"] in pseudo else {})) for r in rows]},
+                                          **({"pseudopotential": pseudo[r["Z"]]} if r["Z"] in pseudo else {}),
+                                          **({"ghosts": ghosts[r["Z"]]} if r["Z"] in ghosts else {})) for r in rows]},
                           f, indent=1)
     scf.close()
     grid.close()

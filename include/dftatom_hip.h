@@ -900,6 +900,84 @@ int  dfta_pseudo_default_valence(int nlev, const int* n, const int* l, const int
  * to 3 .. N-4.  Host only.  DFTA_ERR_INVALID: a NULL pointer, a factor that is not finite and positive, N < 8. */
 int  dfta_pseudo_default_ic(const dfta_grid* g, int nch, const double* u, double factor, int* ic);
 
+/* ---- Kleinman-Bylander form: nonlocal radial solves, bound states of H_KB, ghost states (beyond the reference) -------------------------
+ * L. Kleinman and D. M. Bylander, Phys. Rev. Lett. 48, 1425 (1982); X. Gonze, P. Kaeckell and M. Scheffler, Phys. Rev. B 41, 12264 (1990).
+ * One channel = a local potential Vloc (N doubles), 0 <= l <= 4, a projector row beta (N doubles) and q1 != 0:
+ *   H = -1/2 d^2/dr^2 + l(l+1)/2r^2 + Vloc + |beta><beta| / q1.
+ * One trial = (channel, E, end node m), 3 <= m <= N-2 and m at or beyond the last node where beta is not 0.0 (so that the sums below
+ * are complete; a NaN is not 0.0).  One lane per trial marches TWO solutions of the local equation outwards, both regular at the nucleus:
+ *   u_h: (H_loc - E) u_h = 0       every operation of the continuum block on (Vloc, l, E): s2_i, q_i, vl_i, f_i, d_i, the start, the
+ *                                  recurrence; written yh_i = u_h,i / q_i, wh_i here;
+ *   u_p: (H_loc - E) u_p = -beta   in the index variable yp'' = f yp + G with G_i = ((2 beta_i) s_i) q_i and G12_i = G_i / 12:
+ *     Numerov's form is wp_i = d_i yp_i - G12_i with wp_{i+1} - 2 wp_i + wp_{i-1} = f_i yp_i + G_i.
+ *     Start, nodes i = 1 and 2, from the leading term of the series, u_p = 2 B r^(l+3) / (4l + 6) where beta = B r^(l+1):
+ *       B = beta_1 / p_1;  u_p,i = (((2 B) p_i) (r_i r_i)) / (4l + 6)   (p_i = r_i^(l+1) by l products from r_i, the divisor exact);
+ *       yp_i = u_p,i / q_i;  wp_i = d_i yp_i - G12_i.
+ *     Recurrence, i = 3 .. m+1:  wp_i = ((2 wp_{i-1}) - wp_{i-2}) + (f_{i-1} yp_{i-1} + G_{i-1});  yp_i = (wp_i + G12_i) / d_i.
+ *     (Any regular particular solution serves: two of them differ by a multiple of u_h, which the combination below removes.)
+ * Projector sums, in the partner-sum shape of the continuum block at power 0: gb_i = w_i ((beta_i 1.) s_i), w_i the weight of node i
+ * without 3/8;  B_h = (Sum_{1 <= i <= m} gb_i (q_i yh_i)) (3/8), B_p likewise with yp: sequential inside blocks of 256 nodes
+ * (256 k .. 256 k + 255), the blocks' sums added in order.  (B_h is bit for bit the sum of dfta_continuum with the partner beta at E <= 0.)
+ * End node m, per chain as the continuum block, the source's term kept:
+ *   yh'_m = (((1 - f_{m+1} / 6) yh_{m+1}) - ((1 - f_{m-1} / 6) yh_{m-1})) 0.5
+ *   yp'_m = ((((1 - f_{m+1} / 6) yp_{m+1}) - G_{m+1} / 6) - (((1 - f_{m-1} / 6) yp_{m-1}) - G_{m-1} / 6)) 0.5
+ *   u_x,m = q_m yx_m;  u_x'_m = (yx'_m + (lam 0.5) yx_m) / q_m     for x = h, p.
+ * The combination, continuous in E (the solution u_h + c u_p with c = B_h / D of (H - E) u = 0, multiplied through by D):
+ *   D = q1 - B_p;   u~_m = (D u_h,m) + (B_h u_p,m);   u~'_m = (D u_h'_m) + (B_h u_p'_m);   logderiv = u~'_m / u~_m.
+ * Rows: u~_i = (D (q_i yh_i)) + (B_h (q_i yp_i)) for 1 <= i <= m+1, 0.0 at node 0 and beyond m+1.
+ * With beta == 0 and q1 = 1: B_h = B_p = 0, D = 1, every yp_i = 0 and G_i = 0 -- the additions of 0.0 change no bit, so logderiv and the
+ * rows are those of dfta_continuum (its rows before the normalisation) wherever u_h,i is not -0.0.
+ * status (0: fine): DFTA_CONT_NONFINITE -- a yh_i or yp_i, 1 <= i <= m+1, was not finite; DFTA_CONT_STEP as in the continuum block.  With
+ * either bit every floating-point output of the trial is NaN.
+ * A trial's bits depend on its channel, E, m and the grid -- not on the other trials of the call, their number or order, whether rows
+ * were asked for, the chunking of the rows (DFTA_DEBUG KB_CHUNK_WAVES) or the run.  No atomics.
+ * DFTA_ERR_INVALID: a NULL input, an l outside 0 .. 4, a q1 that is 0 or not finite, an m outside 3 .. N-2 or below the last non-zero
+ * node of the channel's beta, a non-finite E, an index out of range, N < 5.  ntrials == 0: DFTA_OK, nothing is written.  Records the
+ * launches' time for dfta_ctx_last_kernel_ms. */
+#define DFTA_KB_MAX_STATES 8
+#define DFTA_KB_SEARCH_NONFINITE 1
+#define DFTA_KB_SEARCH_FULL      2
+#define DFTA_KB_SEARCH_CAP       4
+#define DFTA_KB_REPORT 10
+/* host pointers.  V: nV x N; per channel vidx (NULL: 0), l, q1 and a row of beta (nch x N); per trial chan (NULL: 0), E, m.  Outputs per
+ * trial, any of which may be NULL: u = u~_m, du = u~'_m, logderiv, Bh, Bp, D, status; rows ntrials x N. */
+int  dfta_kb_sweep(dfta_ctx* ctx, const dfta_grid* g, int nV, const double* V, int nch, const int* vidx, const int* l, const double* beta,
+                   const double* q1, int ntrials, const int* chan, const double* E, const int* m, double* u, double* du, double* logderiv,
+                   double* Bh, double* Bp, double* D, int* status, double* rows);
+/* Bound states of H_KB in a box that ends at node m[k] (u(r_m) = 0), E_lo[k] < E < E_hi[k], per channel: the zeros of u~_m(E).  The
+ * nonlocal operator breaks the node theorem, so the search walks the sign of u~_m: a value is negative if u~_m < 0 and finite if the
+ * trial has no status bit and u~_m is finite.  A host loop whose only device work is launches of the sweep:
+ *   round 0: E_k = E_lo + ((E_hi - E_lo) k) / (nscan - 1), k = 0 .. nscan-1 (nscan a multiple of 64, 64 .. 65536); neighbours k, k+1 that
+ *     are both finite and of opposite sign open a bracket (a, b) = (E_k, E_k+1), in ascending E, at most DFTA_KB_MAX_STATES per channel
+ *     (more sign changes: status DFTA_KB_SEARCH_FULL);
+ *   every further round cuts every open bracket of every channel in ONE launch, a wave per bracket: e_j = a + ((b - a) (j + 1)) / 65,
+ *     j = 0 .. 63, moved to a or b if rounding left [a, b]; among p_0 = a, p_1 = e_0, .., p_64 = e_63, p_65 = b the first pair of
+ *     neighbours of opposite sign is the new bracket; a value that is not finite takes the sign of a and sets DFTA_KB_SEARCH_NONFINITE
+ *     (an outward sweep far below a state overflows at a large box: the caller's choice of m);
+ *   a bracket is closed when no double lies between its ends (about 9 rounds); its state is a, the lower end.  32 rounds at most
+ *     (DFTA_KB_SEARCH_CAP).
+ * Outputs per channel, any of which may be NULL: count; energies nch x 8, ascending, NaN beyond count; rounds (round 0 included);
+ * status.  The events of dfta_ctx_last_kernel_ms bracket the whole search, the host's work between the launches included. */
+int  dfta_kb_bound_states(dfta_ctx* ctx, const dfta_grid* g, int nV, const double* V, int nch, const int* vidx, const int* l,
+                          const double* beta, const double* q1, const int* m, const double* E_lo, const double* E_hi, int nscan, int* count,
+                          double* energies, int* rounds, int* status);
+/* Ghost-state report of Kleinman-Bylander channels; host code that composes dfta_kb_bound_states and dfta_solve_levels.  Inputs as
+ * dfta_pseudo_ionic / dfta_scf_pseudopotentials return them: per channel atom, l, eps (the reference eigenvalue), the SCREENED V_ps
+ * (nch x N), beta (nch x N) and kb (nch x 3); l_loc as dfta_pseudo_ionic (the same rule finds the local channel of each atom).  A
+ * non-local channel k runs with Vloc = V_ps of its atom's local channel, beta_k and q1 = kb[3k].  report, DFTA_KB_REPORT doubles per
+ * channel (the local channel: eps, NaN, then NaN):
+ *   0 eps_ref;  1 E_KB;  2 the number of bound states of H_KB in [E_lo, min(0, E_hi)] with the box at node m (E_lo NaN: per channel
+ *   min_{i >= 1} vl_i - max(0, -E_KB), below which H_KB has no state: H_loc >= min vl and the projector's norm is |E_KB|);  3 how many of them lie
+ *   below eps_ref - tol: each is a ghost;  4, 5 the two lowest eigenvalues e~_0, e~_1 of the local potential at the channel's l from
+ *   dfta_solve_levels (levels n = l, l + 1; a level that is not found -- not converged, or not below 0 -- is absent: NaN; l = 4: NaN, the
+ *   level search ends at l = 3);  6 the verdict of Gonze, Kaeckell and Scheffler, 1 ghost / 0 clean: E_KB > 0: e~_1 < eps_ref, E_KB < 0:
+ *   e~_0 < eps_ref (an absent level is not below; NaN where E_KB is 0 or NaN or l = 4);  7 the direct verdict: 1 if entry 3 is not 0;
+ *   8 the search's status bits;  9 its rounds.
+ * Both verdicts are returned as they come out; the report never reconciles them.  states (may be NULL): nch x 8, the bound states. */
+int  dfta_kb_ghost_report(dfta_ctx* ctx, const dfta_grid* g, int natoms, int nch, const int* atom, const int* l, const double* eps,
+                          const double* V_ps, const double* beta, const double* kb, const int* l_loc, int m, double E_lo, double E_hi,
+                          int nscan, double tol, double* report, double* states);
+
 /* ---- Aufbau -------------------------------------------------------------------------------------------------
  * AufbauPrinciple::GetSubshells + sort (AufbauPrinciple.h:36-75, DFTAtom.cpp:367); integer-only host code. */
 int dfta_get_subshells(int Z, int* n, int* l, int* occ, int cap);
