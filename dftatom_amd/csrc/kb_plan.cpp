@@ -107,14 +107,12 @@ std::vector<Bracket> open_brackets(int nscan, const double* E, const unsigned ch
 bool cut_bracket(Bracket* br, const double* E, const unsigned char* finite, const unsigned char* neg)
 {
     bool bad = false;
+    for (int j = 0; j < kCuts; ++j) bad = bad || !finite[j];       // any of the 64 cuts, also those above the pair picked below
     double pa = br->a;
     for (int j = 0; j <= kCuts; ++j) {               // the pair (p_j, p_j+1) of a, the cuts, b
         const bool last = j == kCuts;
         bool ng = !br->neg_a;                        // b's
-        if (!last) {
-            if (!finite[j]) bad = true;
-            ng = finite[j] ? neg[j] != 0 : br->neg_a;
-        }
+        if (!last) ng = finite[j] ? neg[j] != 0 : br->neg_a;
         const double pb = last ? br->b : E[j];
         if (ng != br->neg_a) {
             br->a = pa; br->b = pb;

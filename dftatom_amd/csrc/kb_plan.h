@@ -60,7 +60,7 @@ struct Bracket { double a, b; bool neg_a; };
 // round 0 of a channel: neighbouring finite values of opposite sign, ascending, at most kMaxStates
 std::vector<Bracket> open_brackets(int nscan, const double* E, const unsigned char* finite, const unsigned char* neg);
 // a further round: the 64 cuts of br and their values; br becomes the first pair of neighbours of opposite sign among a, cuts, b.  A
-// non-finite value takes the sign of a; returns whether one was met
+// non-finite value takes the sign of a; returns whether any of the 64 cuts had one (below, at or above the new bracket)
 bool cut_bracket(Bracket* br, const double* E, const unsigned char* finite, const unsigned char* neg);
 
 struct SearchChannel { int m; double lo, hi; };

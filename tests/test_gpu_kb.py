@@ -8,8 +8,20 @@ a. continuum   beta == 0, q1 = 1: logderiv and rows are continuum()'s on the sam
                ==: the combination adds 0.0, which turns a -0.0 into 0.0 and changes nothing else).
 b. model       hydrogen-like and smooth-well channels on log12 (4097), uni11 (2049) and uni3 (9 nodes): m = 255, 256, 257, N-2; beta cut
                at 255, 256, 257, N-2 and all zero; E < 0, = 0, > 0; l = 0 .. 4; a NaN node in Vloc and one in beta.
-c. bits        a trial alone == among 63, 64, 65, 200 others at any position == with rows == a repeated call == one wave per chunk.
-d. search      kb_bound_states == _kb_ref.search fed with the device's own signs, bit for bit.
+b'. exits      the status words born mid-sweep from finite inputs: DFTA_CONT_STEP alone (uni3, E = -146), DFTA_CONT_NONFINITE by overflow
+               (uni11, E = -1e4 and +1e6), both (E = -40 315): every output and the rows equal the model; flagged trials at lanes 0, 31, 32
+               and 63 of a wave between clean ones, some of which end before a node whose step test would fail; a flagged row is NaN on
+               1 .. m+1 and 0.0 elsewhere.
+c. bits        a trial alone == among 63, 64, 65, 200 others at any position == with rows == a repeated call == rows in chunks of one, two
+               and three waves (the last chunk shorter than the others).
+d. search      kb_bound_states == _kb_ref.search fed with the device's own signs, bit for bit; DFTA_KB_SEARCH_FULL (nine sign changes and
+               more on uni11); scan points that are not finite in round 0 (uni3, also against the model's search); four channels with their
+               own potential, l, m, range and closing round in one call == each alone, one of them without a state.
+d'. report     kb_ghost_report on a synthetic ps of five atoms held to its composition -- the bound of E_lo = NaN restated, the states of
+               kb_bound_states, the ghosts below eps_ref - tol (at the state, one double above it, tol = 0), e_loc of dfta_solve_levels,
+               both verdicts, status, rounds, the rows that stay NaN --: l = 3 non-local, l = 4 local and non-local, E_KB of both signs, a
+               channel that was not pseudized, l_loc by default and given, two channels of the local l; a given range, E_hi below and
+               above 0 and a shorter box; local channels only; every refusal.
 e. physics     Ne, Ar, Fe after convergence: the eigenstate identity (gated by the model on the same channel), the lowest bound state, the
                planted ghost, continuity through D = 0.
 f. edges       the DFTA_ERR_INVALID cases, zero trials.
@@ -172,6 +184,95 @@ def test_nan_nodes_poison_their_own_trials(ctx, grids):
     assert np.all(np.isnan(got["logderiv"][hit])) and np.all(np.isfinite(got["logderiv"][~hit]))
 
 
+# ---- b'. the status exits of k_kb -------------------------------------------------------------------------------------------------------------
+# Ordinary arithmetic that the kernel answers with a status word: a step so long that d_i = 1 - f_i / 12 is not positive (STEP), a chain
+# that overflows on the way out (NONFINITE), both.  (grid) -> the channels (V, l, beta, q1), the flagged energies with the bits the float64
+# model gives them at m = N - 2, a range of clean energies.
+def _status_case(name, r):
+    """channels, [(flagged E, its bits at m = N - 2)], the clean energies' range, the channel of the shared wave, end nodes of its clean trials"""
+    N = len(r)
+    if name == "uni3":
+        Vh, bh, qh = K.hydrogen_like(r, 3.0, 0, 4)
+        Vw, bw, qw = K.smooth_well(r, 40.0, 1, N - 2)
+        Vc, bc, qc = K.smooth_well(r, 40.0, 1, 4)
+        # the third channel: between E = -122 and -118.4 d_i is positive up to node 5 and not at node 6: a trial that ends at m = 3 is clean
+        # and shares its wave with lanes that march on through node 6
+        return [(Vh, 0, bh, qh), (Vw, 1, bw, qw), (Vc, 1, bc, qc)], [(-146.0, K.STEP)], (-122.0, 1.0), 2, lambda e, j: 3 if e < -95.0 else (3, 5, N - 2)[j % 3]
+    Vh, bh, qh = K.hydrogen_like(r, 3.0, 0, 257)
+    return ([(Vh, 0, bh, qh)], [(-1e4, K.NONFINITE), (1e6, K.NONFINITE), (-40315.0, K.STEP | K.NONFINITE)], (-2.0, 1.0), 0,
+            lambda e, j: (257, 1000, N - 2)[j % 3])
+
+
+def _flagged_row_is_nan_inside(row, m):
+    return np.all(np.isnan(row[1:m + 2])) and row[0] == 0 and not np.signbit(row[0]) and np.all(row[m + 2:] == 0) and not np.signbit(row[m + 2:]).any()
+
+
+@pytest.mark.parametrize("name", ["uni3", "uni11"])
+def test_status_exits_are_the_models(ctx, grids, name):
+    """DFTA_CONT_STEP, DFTA_CONT_NONFINITE by overflow and both together, born mid-sweep from finite inputs: every output, rows included,
+    is the float64 model's bit for bit, the model gives exactly the expected bits, and a flagged trial's row is NaN on 1 .. m+1"""
+    grid, tab = grids(name)
+    N = grid.N
+    chans, flagged, _, _, _ = _status_case(name, tab[0])
+    energies = [e for e, _ in flagged] + [-95.0 if name == "uni3" else -2.0]
+    want = [bits for _, bits in flagged] + [0]
+    chan = np.repeat(np.arange(len(chans)), len(energies)).astype(np.int32)
+    E = np.tile(energies, len(chans))
+    m = np.full(len(E), N - 2, np.int32)
+    got = _call(ctx, grid, chans, chan, E, m, want_rows=True)
+    ref = _model(chans, chan, E, m, tab, want_rows=True)
+    print("   %s: E %s -> status %s (model %s)" % (name, E, got["status"], ref["status"].astype(int)))
+    assert np.array_equal(ref["status"], np.tile(want, len(chans))), "the model does not take the exits this test is about"
+    _same(got, ref, name)
+    for t in range(len(E)):
+        if got["status"][t]:
+            assert all(np.isnan(got[q][t]) for q in OUTS[:-1]) and _flagged_row_is_nan_inside(got["rows"][t], m[t]), t
+        else:
+            assert all(np.isfinite(got[q][t]) for q in OUTS[:-1]) and np.all(np.isfinite(got["rows"][t])), t
+
+
+@pytest.mark.parametrize("name", ["uni3", "uni11"])
+def test_flagged_and_clean_trials_share_a_wave(ctx, grids, name):
+    """one wave of 64 trials of one channel, flagged ones at lanes 0, 31, 32 and 63 between clean ones of other end nodes: the clean trials
+    keep the bits they have in a call without the flagged ones, and alone; the whole wave is the model's"""
+    grid, tab = grids(name)
+    N = grid.N
+    chans, flagged, clean, which, end_of = _status_case(name, tab[0])
+    chans = chans[which:which + 1]
+    lanes = (0, 31, 32, 63)
+    E = np.zeros(64)
+    m = np.zeros(64, np.int32)
+    bits = np.zeros(64, np.int64)
+    others = [t for t in range(64) if t not in lanes]
+    E[others] = np.linspace(clean[0], clean[1], len(others))
+    m[others] = [end_of(E[t], j) for j, t in enumerate(others)]
+    for j, t in enumerate(lanes):
+        E[t], bits[t] = flagged[j % len(flagged)]
+        m[t] = N - 2
+    chan = np.zeros(64, np.int32)
+    got = _call(ctx, grid, chans, chan, E, m, want_rows=True)
+    ref = _model(chans, chan, E, m, tab, want_rows=True)
+    print("   %s: status by lane %s" % (name, got["status"]))
+    assert np.array_equal(ref["status"], bits), "the model does not take the exits this test is about"
+    if name == "uni3":                               # clean trials whose step test would fail beyond their own last node
+        r, s, c, lam = tab
+        V, l, beta, q1 = chans[0]
+        beyond = K.sweep(V, l, beta, q1, E[others], N - 2, r, s, c, lam)["status"]
+        print("   uni3: %d clean trials end before a node where d_i <= 0" % np.count_nonzero(beyond & K.STEP))
+        assert np.count_nonzero(beyond & K.STEP) >= 2
+    _same(got, ref, name)
+    apart = _call(ctx, grid, chans, chan[others], E[others], m[others], want_rows=True)
+    for q in OUTS + ("rows",):
+        assert np.array_equal(got[q][others], apart[q], equal_nan=True), q
+    for t in (1, 30, 33, 62):
+        alone = _call(ctx, grid, chans, chan[t:t + 1], E[t:t + 1], m[t:t + 1], want_rows=True)
+        for q in OUTS + ("rows",):
+            assert np.array_equal(got[q][t], alone[q][0], equal_nan=True), (t, q)
+    assert not got["status"][others].any() and all(np.all(np.isfinite(got[q][others])) for q in OUTS[:-1])
+    for t in lanes:
+        assert all(np.isnan(got[q][t]) for q in OUTS[:-1]) and _flagged_row_is_nan_inside(got["rows"][t], m[t]), t
+
+
 # ---- c. a trial's bits are its own ------------------------------------------------------------------------------------------------------------
 def test_a_trial_does_not_depend_on_the_call(ctx, grids, monkeypatch):
     grid, tab = grids("uni11")
@@ -192,11 +293,17 @@ def test_a_trial_does_not_depend_on_the_call(ctx, grids, monkeypatch):
                 for q in OUTS + (("rows",) if rows else ()):
                     assert np.array_equal(got[q][at], alone[q][0], equal_nan=True), (others, at, rows, q)
     again = _call(ctx, grid, chans, ch.astype(np.int32), E, m.astype(np.int32), want_rows=True)
-    monkeypatch.setenv("DFTA_DEBUG", "KB_CHUNK_WAVES=1")                  # read by every call
-    chunked = _call(ctx, grid, chans, ch.astype(np.int32), E, m.astype(np.int32), want_rows=True)
-    monkeypatch.delenv("DFTA_DEBUG")
     for q in OUTS + ("rows",):
-        assert np.array_equal(again[q], got[q], equal_nan=True) and np.array_equal(chunked[q], got[q], equal_nan=True), q
+        assert np.array_equal(again[q], got[q], equal_nan=True), q
+    # the rows in chunks of 1, 2 and 3 waves: the call has four waves (one per channel), so chunks of 3 leave a last chunk of one
+    waves_of_call = sum(-(-int(n) // 64) for n in np.bincount(ch.astype(np.int64)))
+    assert waves_of_call % 3 != 0, waves_of_call
+    for waves in (1, 2, 3):
+        monkeypatch.setenv("DFTA_DEBUG", "KB_CHUNK_WAVES=%d" % waves)     # read by every call
+        chunked = _call(ctx, grid, chans, ch.astype(np.int32), E, m.astype(np.int32), want_rows=True)
+        monkeypatch.delenv("DFTA_DEBUG")
+        for q in OUTS + ("rows",):
+            assert np.array_equal(chunked[q], got[q], equal_nan=True), (waves, q)
 
 
 # ---- d. the search ------------------------------------------------------------------------------------------------------------------------------
@@ -221,6 +328,303 @@ def test_bound_states_are_the_restated_search(ctx, grids, name):
         assert np.all(np.isnan(got["energies"][k][len(en):])) and got["rounds"][k] == rounds and got["status"][k] == status
     assert got["count"].sum() >= 4 and np.all(got["rounds"] <= 12)
     print("   %s: %s states, %s rounds" % (name, got["count"], got["rounds"]))
+
+
+def _device_signs(ctx, grid, V, ls, beta, q1, ms, seen=None):
+    """signs() for _kb_ref.search from the device's own sweep, a channel at a time; seen[k] counts the scan points (the first call per
+    channel) that were not finite"""
+    def signs(k, E):
+        res = D.kb_sweep(ctx, grid, V[k], [ls[k]], beta[k], [q1[k]], E, ms[k])
+        fin = (res["status"] == 0) & np.isfinite(res["u"])
+        if seen is not None and k not in seen:
+            seen[k] = int(np.count_nonzero(~fin))
+        return fin, res["u"] < 0
+    return signs
+
+
+def _same_search(got, ref, k, j=None):
+    """channel k of kb_bound_states' output against entry j (default k) of _kb_ref.search's"""
+    en, rounds, status = ref[k if j is None else j]
+    assert got["count"][k] == len(en) and np.array_equal(got["energies"][k][:len(en)], en), (k, got["energies"][k], en)
+    assert np.all(np.isnan(got["energies"][k][len(en):])) and got["rounds"][k] == rounds and got["status"][k] == status, (k, got, ref)
+
+
+def test_search_reports_more_sign_changes_than_states(ctx, grids):
+    """DFTA_KB_SEARCH_FULL: the box at N - 2 of uni11 and a range that reaches up to E = 3 hold more than eight sign changes; the lowest
+    eight are kept and closed, the bit is set"""
+    grid, tab = grids("uni11")
+    r, N = tab[0], grid.N
+    V, beta, q1 = K.hydrogen_like(r, 3.0, 0, 257)
+    got = D.kb_bound_states(ctx, grid, V, [0], beta, [q1], -6.0, 3.0, m=N - 2, nscan=128)
+    ref = K.search(_device_signs(ctx, grid, [V], [0], [beta], [q1], [N - 2]), [(-6.0, 3.0)], 128)
+    print("   uni11: %d states %s, %d rounds, status %d" % (got["count"][0], got["energies"][0], got["rounds"][0], got["status"][0]))
+    _same_search(got, ref, 0)
+    assert got["count"][0] == K.MAX_STATES and got["status"][0] & K.SEARCH_FULL and not got["status"][0] & K.SEARCH_CAP
+    assert np.all(np.diff(got["energies"][0]) > 0)
+
+
+def test_search_steps_over_scan_points_that_are_not_finite(ctx, grids):
+    """round 0 with points that are not finite (the low end of the range has DFTA_CONT_STEP on nine nodes): they open nothing and set
+    nothing; the states above them are found.  Held to the restated search on the device's signs AND on the float64 model's."""
+    grid, tab = grids("uni3")
+    r, s, c, lam = tab
+    N = grid.N
+    chans, _, _, _, _ = _status_case("uni3", r)
+    chans = chans[:2]
+    V, ls, beta, q1 = [ch[0] for ch in chans], [ch[1] for ch in chans], [ch[2] for ch in chans], [ch[3] for ch in chans]
+    got = D.kb_bound_states(ctx, grid, np.array(V), ls, np.array(beta), q1, -200.0, 0.0, m=N - 2, vidx=[0, 1], nscan=64)
+    seen = {}
+    ref = K.search(_device_signs(ctx, grid, V, ls, beta, q1, [N - 2] * 2, seen), [(-200.0, 0.0)] * 2, 64)
+    print("   uni3: scan points that are not finite %s, states %s, rounds %s, status %s" % (seen, got["count"], got["rounds"], got["status"]))
+    for k in range(2):
+        _same_search(got, ref, k)
+        model = K.search(K.model_signs(V[k], ls[k], beta[k], q1[k], N - 2, r, s, c, lam), [(-200.0, 0.0)], 64)
+        _same_search(got, model, k, 0)
+        assert 0 < seen[k] < 64
+    assert got["count"].sum() >= 2
+
+
+def test_four_channels_search_as_each_alone(ctx, grids):
+    """one call with four channels that differ in potential, l, end node, range and closing round, one of them without a state: every
+    channel's count, energies, rounds and status are those of the channel searched alone"""
+    grid, tab = grids("log12")
+    r, N = tab[0], grid.N
+    chans = [K.hydrogen_like(r, 3.0, 0, 257), K.smooth_well(r, 4.0, 2, 0), K.hydrogen_like(r, 3.0, 1, 256), K.smooth_well(r, 4.0, 0, 255)]
+    ls = [0, 2, 1, 0]
+    V = np.array([chans[2][0], chans[1][0]])                              # the potentials, each once
+    vidx = [0, 1, 0, 1]
+    beta, q1 = np.array([c[1] for c in chans]), [c[2] for c in chans]
+    ms = [int(np.searchsorted(r, 12.0)), N - 2, int(np.searchsorted(r, 8.0)), int(np.searchsorted(r, 5.0))]
+    lo, hi = [-6.0, -4.0, -1.126, -4.5], [0.0, -3.5, -1.124, 0.5]          # (the third: a narrow range round the 2p-like state closes sooner)
+    got = D.kb_bound_states(ctx, grid, V, ls, beta, q1, lo, hi, m=ms, vidx=vidx, nscan=128)
+    print("   log12: states %s, rounds %s, status %s" % (got["count"], got["rounds"], got["status"]))
+    for k in range(4):
+        print("      channel %d: m = %d, (%g, %g): %s" % (k, ms[k], lo[k], hi[k], got["energies"][k][:got["count"][k]]))
+        alone = D.kb_bound_states(ctx, grid, V[vidx[k]], [ls[k]], beta[k], [q1[k]], lo[k], hi[k], m=ms[k], nscan=128)
+        for q in ("count", "rounds", "status"):
+            assert got[q][k] == alone[q][0], (k, q, got[q], alone[q])
+        assert np.array_equal(got["energies"][k], alone["energies"][0], equal_nan=True), k
+    assert got["count"][1] == 0 and got["rounds"][1] == 1 and min(got["count"][k] for k in (0, 2, 3)) >= 1
+    assert len(set(got["rounds"].tolist())) >= 3, got["rounds"]
+
+
+# ---- d'. the ghost report is its own composition ----------------------------------------------------------------------------------------------------
+REPORT_CUT = 3400                       # the projectors of the synthetic report end here (r = 6.2 on log12) ...
+REPORT_M = 3600                         # ... and this is the shorter box (r = 9.3)
+#              atom, l, maker ("h": hydrogen_like, Z; "w": smooth_well, depth), pseudized
+REPORT_CHANNELS = [(0, 0, "h", 3.0, True), (0, 1, "w", 5.0, True), (0, 2, "h", 3.0, True), (0, 3, "w", 7.0, True), (0, 4, "w", 40.0, True),
+                   (1, 0, "w", 30.0, True), (1, 4, "h", 3.0, True),
+                   (2, 0, "h", 3.0, True), (2, 1, "w", 1.0, True), (2, 2, "w", 6.0, False),
+                   (3, 2, "w", 10.0, True),
+                   (4, 0, "h", 3.0, True), (4, 1, "w", 20.0, True), (4, 1, "w", 8.0, True)]
+REPORT_L_LOC = [-1, 0, 1, -1, -1]       # atom 0: l = 4 is local and l = 3 is not; 1: l = 4 is NOT local; 2: l = 1; 3: its one channel; 4: the
+#                                         first of its two l = 1 channels
+
+
+def _report_ps(r, s):
+    """a synthetic `ps`: V_ps and beta of the makers, kb = (q1, q2, q2 / q1) with q2 = <beta|beta>: E_KB > 0 for "h", < 0 for "w"; the
+    channel that was not pseudized has kb = NaN; a local channel has kb = NaN as well (what pseudo_ionic leaves)"""
+    V, beta, kb = [], [], []
+    for atom, l, kind, par, pseudized in REPORT_CHANNELS:
+        v, b, q1 = K.hydrogen_like(r, par, l, REPORT_CUT) if kind == "h" else K.smooth_well(r, par, l, REPORT_CUT)
+        V.append(v); beta.append(b)
+        kb.append((q1, K.q1_of(b, b, s), K.q1_of(b, b, s) / q1) if pseudized else (np.nan,) * 3)
+    ps = {"V_ps": np.array(V), "beta": np.array(beta), "kb": np.array(kb), "l": np.array([c[1] for c in REPORT_CHANNELS], np.int32),
+          "atom": np.array([c[0] for c in REPORT_CHANNELS], np.int32), "eps": np.full(len(V), -0.5)}
+    for k in _report_local(ps, REPORT_L_LOC).values():
+        ps["kb"][k] = np.nan
+    return ps
+
+
+def _report_atoms(ps):
+    """the atoms numbered by their first channel, as the binding numbers them (and the rows of l_loc)"""
+    seen = {}
+    return np.array([seen.setdefault(int(a), len(seen)) for a in ps["atom"]])
+
+
+def _report_local(ps, l_loc):
+    """the header's rule: per atom the first channel of l_loc, or (l_loc < 0) the first channel of the atom's highest l"""
+    atom, loc = _report_atoms(ps), {}
+    for a in range(int(atom.max()) + 1):
+        ks = [k for k in range(len(atom)) if atom[k] == a]
+        want = l_loc[a] if l_loc[a] >= 0 else max(ps["l"][k] for k in ks)
+        loc[a] = [k for k in ks if ps["l"][k] == want][0]
+    return loc
+
+
+def _levels_as_the_report(ctx, grid, V, levels, vidx):
+    """dfta_solve_levels as the report calls it: LEVELS_BATCHED on every potential of `ps` with bottom min_{i >= 1} V - 1, no hints, no
+    density, no orbitals; a level that did not converge is not an error here.  Returns E per level, NaN for an absent one."""
+    V = D._f64(V)
+    n, l, occ = (D._i32([lv[q] for lv in levels]) for q in range(3))
+    vi, bottom = D._i32(vidx), D._f64(V[:, 1:].min(axis=1) - 1.0)
+    res = (D.LevelResult * len(levels))()
+    issued = D.C.c_long(0)
+    rc = ctx.lib.dfta_solve_levels(ctx.h, grid.h, D.LEVELS_BATCHED, 0, V.shape[0], D._dp(V), D._dp(bottom), None, len(levels), D._ip(vi),
+                                   D._ip(n), D._ip(l), D._ip(occ), res, None, None, None, D.C.byref(issued))
+    assert rc in (D.OK, 5), rc                                            # (5: DFTA_ERR_NOT_CONVERGED, soft)
+    return np.array([x.E if x.converged and np.isfinite(x.E) and x.E < 0 else np.nan for x in res])
+
+
+def _report_expected(ctx, grid, ps, l_loc, m=None, E_lo=None, E_hi=0.0, nscan=512, tol=1e-5):
+    """what include/dftatom_hip.h says dfta_kb_ghost_report returns, composed from kb_bound_states and dfta_solve_levels called directly"""
+    r, N = grid.r(), grid.N
+    nch = len(ps["l"])
+    loc, atom = _report_local(ps, l_loc), _report_atoms(ps)
+    nl = [k for k in range(nch) if k != loc[atom[k]] and np.isfinite(ps["kb"][k, 0]) and ps["kb"][k, 0] != 0]
+    exp = {"eps_ref": ps["eps"].copy(), "E_KB": ps["kb"][:, 2].copy(), "bound": [np.zeros(0)] * nch, "ghosts": np.full(nch, -1),
+           "e_loc": np.full((nch, 2), np.nan), "gks": np.full(nch, -1), "direct": np.full(nch, -1), "status": np.full(nch, -1),
+           "rounds": np.full(nch, -1), "lo": np.full(nch, np.nan), "nl": nl, "loc": loc}
+    if not nl:
+        return exp
+    vidx = [loc[atom[k]] for k in nl]
+    for k, v in zip(nl, vidx):
+        if E_lo is None:                             # min_{i >= 1} vl_i - max(0, -E_KB), the header's operations in its order
+            L = float(ps["l"][k]) * (float(ps["l"][k]) + 1.0)
+            exp["lo"][k] = np.min(ps["V_ps"][v][1:] + (L / (r[1:] * r[1:])) * 0.5) - max(0.0, -ps["kb"][k, 2])
+        else:
+            exp["lo"][k] = E_lo
+    st = D.kb_bound_states(ctx, grid, ps["V_ps"], ps["l"][nl], ps["beta"][nl], ps["kb"][nl, 0], exp["lo"][nl], min(0.0, E_hi),
+                           m=N - 2 if m is None else m, vidx=vidx, nscan=nscan)
+    has = [j for j, k in enumerate(nl) if ps["l"][k] <= 3]
+    levels = [(int(ps["l"][nl[j]]) + q, int(ps["l"][nl[j]]), 1) for j in has for q in range(2)]
+    e = _levels_as_the_report(ctx, grid, ps["V_ps"], levels, [vidx[j] for j in has for q in range(2)])
+    for at, j in enumerate(has):
+        exp["e_loc"][nl[j]] = e[2 * at:2 * at + 2]
+    for j, k in enumerate(nl):
+        states = st["energies"][j][:st["count"][j]]
+        exp["bound"][k] = states
+        exp["ghosts"][k] = np.count_nonzero(states < ps["eps"][k] - tol)
+        exp["direct"][k] = int(exp["ghosts"][k] > 0)
+        exp["status"][k], exp["rounds"][k] = st["status"][j], st["rounds"][j]
+        if ps["l"][k] <= 3 and ps["kb"][k, 2] != 0 and not np.isnan(ps["kb"][k, 2]):
+            exp["gks"][k] = K.gks_verdict(ps["kb"][k, 2], exp["e_loc"][k, 0], exp["e_loc"][k, 1], ps["eps"][k])
+    return exp
+
+
+def _same_report(rep, exp, what):
+    for k in range(len(exp["eps_ref"])):
+        row = "%s channel %d: eps_ref %.17g E_KB %.6g lo %.6g states %s ghosts %d e_loc %s gks %d direct %d status %d rounds %d" % (
+            what, k, rep["eps_ref"][k], rep["E_KB"][k], exp["lo"][k], rep["bound"][k], rep["ghosts"][k], rep["e_loc"][k], rep["gks"][k],
+            rep["direct"][k], rep["status"][k], rep["rounds"][k])
+        print("   " + row)
+        for q in ("eps_ref", "E_KB", "e_loc"):
+            assert np.array_equal(rep[q][k], exp[q][k], equal_nan=True), (row, q, exp[q][k])
+        assert np.array_equal(rep["bound"][k], exp["bound"][k]), (row, exp["bound"][k])
+        for q in ("ghosts", "gks", "direct", "status", "rounds"):
+            assert rep[q][k] == exp[q][k], (row, q, exp[q][k])
+
+
+@pytest.fixture(scope="module")
+def report(ctx, grids):
+    """the synthetic ps on log12, its first report (eps_ref = -0.5 everywhere) and what that report must be"""
+    grid, tab = grids("log12")
+    ps = _report_ps(tab[0], tab[1])
+    rep = D.kb_ghost_report(ctx, grid, ps, l_loc=REPORT_L_LOC)
+    return ps, rep, _report_expected(ctx, grid, ps, REPORT_L_LOC)
+
+
+def test_ghost_report_is_its_composition(ctx, grids, report):
+    """the bound of E_lo = NaN (E_KB of both signs), the states, the count of ghosts, e_loc, both verdicts, status and rounds of every
+    channel of five atoms: l = 3 non-local, l = 4 local and non-local, a channel that was not pseudized, l_loc by default and given,
+    two channels of the local l; the rows that stay NaN"""
+    ps, rep, exp = report
+    _same_report(rep, exp, "first")
+    nl, loc = exp["nl"], exp["loc"]
+    assert [loc[a] for a in range(5)] == [4, 5, 8, 10, 12] and nl == [0, 1, 2, 3, 6, 7, 11, 13]
+    assert np.all(ps["kb"][nl, 2][[0, 2, 4, 5, 6]] > 0) and np.all(ps["kb"][nl, 2][[1, 3, 7]] < 0)      # E_KB of both signs
+    for k in range(len(ps["l"])):
+        if k not in nl:                              # local, or not pseudized: (eps, E_KB, NaN ...)
+            assert len(rep["bound"][k]) == 0 and np.all(np.isnan(rep["e_loc"][k])), k
+            assert (rep["ghosts"][k], rep["gks"][k], rep["direct"][k], rep["status"][k], rep["rounds"][k]) == (-1,) * 5, k
+            assert np.isnan(rep["E_KB"][k]) and rep["eps_ref"][k] == ps["eps"][k]
+    assert np.all(np.isnan(rep["e_loc"][6])) and rep["gks"][6] == -1 and rep["direct"][6] in (0, 1) and rep["rounds"][6] >= 1      # l = 4, non-local
+    assert set(rep["gks"][[0, 1, 2, 3, 7, 11, 13]].tolist()) <= {0, 1} and len(rep["bound"][3]) >= 1                              # l = 3 has levels
+    assert sum(len(rep["bound"][k]) >= 1 for k in nl) >= 4
+    assert np.isfinite(rep["e_loc"][7, 0]) and np.isnan(rep["e_loc"][7, 1])      # atom 2's shallow local well has one s level: the second is absent
+    assert np.all(np.isfinite(rep["e_loc"][[0, 1, 2, 3, 11, 13]]))
+
+
+def test_ghost_report_at_the_edge_of_tol(ctx, grids, report):
+    """eps_ref placed from the first report's states, tol = 1e-5: 1e-3 above the lowest state (a ghost), below every state (none),
+    eps_ref - tol EQUAL to the lowest state (not a ghost: the count is of states BELOW it) and the next double above that (a ghost)"""
+    grid, _ = grids("log12")
+    ps, rep, exp = report
+    tol = 1e-5
+    with_states = [k for k in exp["nl"] if len(rep["bound"][k]) >= 1][:4]
+    assert len(with_states) == 4
+    ps2 = dict(ps, eps=ps["eps"].copy())
+    lowest = [rep["bound"][k][0] for k in with_states]
+    def at_the_state(e):                             # the largest double x with x - tol == e in float64
+        x = e + tol
+        for _ in range(8):
+            x = np.nextafter(x, np.inf) if x - tol < e else (np.nextafter(x, -np.inf) if x - tol > e else x)
+        while np.nextafter(x, np.inf) - tol == e:
+            x = np.nextafter(x, np.inf)
+        assert x - tol == e
+        return x
+    equal, above = at_the_state(lowest[2]), np.nextafter(at_the_state(lowest[3]), np.inf)
+    assert equal - tol == lowest[2] and above - tol > lowest[3] and np.nextafter(above, -np.inf) - tol == lowest[3]
+    ps2["eps"][with_states] = [lowest[0] + 1e-3, lowest[1] - 1.0, equal, above]
+    rep2 = D.kb_ghost_report(ctx, grid, ps2, l_loc=REPORT_L_LOC, tol=tol)
+    _same_report(rep2, _report_expected(ctx, grid, ps2, REPORT_L_LOC, tol=tol), "edge")
+    print("   ghosts of channels %s: %s" % (with_states, rep2["ghosts"][with_states]))
+    assert rep2["ghosts"][with_states[0]] >= 1 and rep2["direct"][with_states[0]] == 1
+    assert rep2["ghosts"][with_states[1]] == 0 and rep2["direct"][with_states[1]] == 0
+    assert rep2["ghosts"][with_states[2]] == 0 and rep2["direct"][with_states[2]] == 0
+    assert rep2["ghosts"][with_states[3]] == 1 and rep2["direct"][with_states[3]] == 1
+    for k in exp["nl"]:                              # the states do not depend on eps_ref
+        assert np.array_equal(rep2["bound"][k], rep["bound"][k])
+    # tol = 0: a state at eps_ref itself is not below it
+    ps3 = dict(ps, eps=ps["eps"].copy())
+    ps3["eps"][with_states] = lowest
+    rep3 = D.kb_ghost_report(ctx, grid, ps3, l_loc=REPORT_L_LOC, tol=0.0)
+    assert np.all(rep3["ghosts"][with_states] == 0) and np.all(rep3["direct"][with_states] == 0)
+
+
+def test_ghost_report_with_a_given_range_and_box(ctx, grids, report):
+    """E_lo given, E_hi = -0.5 below 0 and the box at a node below N - 2; a ps without a non-local channel returns its heads"""
+    grid, _ = grids("log12")
+    ps, _, _ = report
+    kw = dict(m=REPORT_M, E_lo=-30.0, E_hi=-0.5, nscan=256)
+    rep = D.kb_ghost_report(ctx, grid, ps, l_loc=REPORT_L_LOC, **kw)
+    exp = _report_expected(ctx, grid, ps, REPORT_L_LOC, **kw)
+    _same_report(rep, exp, "given")
+    assert all(np.all((b > -30.0) & (b < -0.5)) for b in rep["bound"]) and sum(len(b) for b in rep["bound"]) >= 4
+    # E_hi above 0: the range ends at 0
+    rep0 = D.kb_ghost_report(ctx, grid, ps, l_loc=REPORT_L_LOC, m=REPORT_M, E_lo=-30.0, E_hi=2.0, nscan=256)
+    _same_report(rep0, _report_expected(ctx, grid, ps, REPORT_L_LOC, m=REPORT_M, E_lo=-30.0, E_hi=2.0, nscan=256), "E_hi = 2")
+    # local channels only: atom 3 alone, and the local channels of atoms 0 and 1 together
+    for keep, l_loc in (([10], [-1]), ([4, 5], [-1, 0])):
+        only = {q: ps[q][keep] for q in ps}
+        rep1 = D.kb_ghost_report(ctx, grid, only, l_loc=l_loc)
+        exp1 = _report_expected(ctx, grid, only, l_loc)
+        assert not exp1["nl"]
+        _same_report(rep1, exp1, "local only")
+        assert np.array_equal(rep1["eps_ref"], only["eps"]) and np.all(rep1["rounds"] == -1)
+
+
+def test_ghost_report_refusals(ctx, grids, report):
+    grid, _ = grids("log12")
+    ps, _, _ = report
+    ok = dict(l_loc=REPORT_L_LOC, m=REPORT_M, E_lo=-30.0, nscan=64)
+    for bad in (dict(tol=-1e-9), dict(tol=np.nan), dict(E_hi=np.inf), dict(E_hi=np.nan), dict(E_lo=-np.inf), dict(E_lo=np.inf),
+                dict(l_loc=[-1, 0, 3, -1, -1]),                           # atom 2 has no l = 3 channel
+                dict(E_lo=0.0), dict(E_lo=-0.5, E_hi=-0.5), dict(E_lo=-0.25, E_hi=-0.5), dict(E_lo=1.0, E_hi=2.0),      # E_lo >= min(0, E_hi)
+                dict(l=np.where(np.arange(len(ps["l"])) == 6, 5, ps["l"])), dict(l=np.where(np.arange(len(ps["l"])) == 0, -1, ps["l"]))):
+        with pytest.raises(D.DftaError):
+            D.kb_ghost_report(ctx, grid, ps, **dict(ok, **bad))
+    # an atom index out of range: the binding renumbers the atoms, so the entry is called as the binding calls it
+    nch = len(ps["l"])
+    rep, st = np.zeros((nch, D.KB_REPORT)), np.zeros((nch, D.KB_MAX_STATES))
+    for atoms, natoms in ((ps["atom"], 4), (np.where(np.arange(nch) == 3, -1, ps["atom"]), 5)):
+        atoms = D._i32(atoms)
+        rc = ctx.lib.dfta_kb_ghost_report(ctx.h, grid.h, natoms, nch, D._ip(atoms), D._ip(D._i32(ps["l"])), D._dp(D._f64(ps["eps"])),
+                                          D._dp(D._f64(ps["V_ps"])), D._dp(D._f64(ps["beta"])), D._dp(D._f64(ps["kb"])),
+                                          D._ip(D._i32(REPORT_L_LOC)), REPORT_M, -30.0, 0.0, 64, 1e-5, D._dp(rep), D._dp(st))
+        with pytest.raises(D.DftaError):
+            ctx.check(rc)
+    assert D.kb_ghost_report(ctx, grid, ps, **ok)["rounds"][0] >= 1       # the call the refusals were cut from is accepted
 
 
 # ---- e. physics -----------------------------------------------------------------------------------------------------------------------------------
