@@ -43,7 +43,7 @@ BT_DENSITY, BT_ORBITAL = 0, 1         # DFTA_BT_*: kinds of bessel_transform
 BESSEL_LMAX = 4                        # DFTA_BESSEL_LMAX: largest order of sph_bessel / bessel_transform
 CONT_FREE, CONT_WKB = 0, 1             # DFTA_CONT_*: normalisation of continuum(): Riccati matching (short range) / WKB amplitude (any tail)
 CONT_MAX_PARTNERS = 16                 # DFTA_CONT_MAX_PARTNERS: partners of one list
-CONT_NONFINITE, CONT_STEP, CONT_WKB_TAIL = 1, 2, 4      # status bits of a continuum trial
+CONT_NONFINITE, CONT_STEP, CONT_WKB_TAIL, CONT_NORM = 1, 2, 4, 8      # status bits of a continuum trial
 PS_COEF, PS_MATCH = 7, 8               # DFTA_PS_*: a0, a2 .. a12 of a pseudized channel; P0 .. P4, I_AE, I_ps, g
 PS_NOBRACKET, PS_CAP, PS_NODES, PS_NONFINITE, PS_NOTPOSITIVE = 1, 2, 4, 8, 16      # status bits of a pseudized channel
 KB_MAX_STATES, KB_REPORT = 8, 10       # DFTA_KB_*: bound states of a channel; doubles of a channel's ghost report

@@ -229,7 +229,8 @@ void print_form_factor_table(dfta_scf* scf, bool lsda)
 // the normalisation of the continuum tables: the Riccati matching needs a short-range potential
 int continuum_norm() { return DFTAtom::charge != 0 || !DFTAtom::config.empty() || DFTAtom::exchange != DFTA_EXCHANGE_FUNCTIONAL ? DFTA_CONT_WKB : DFTA_CONT_FREE; }
 
-// --phase-shift-table: every (spin, l = 0 .. 4, E_k = Emax (k + 1) / ne) in one launch, end node N - 2
+// --phase-shift-table: every (spin, l = 0 .. 4, E_k = Emax (k + 1) / ne) in one launch, end node N - 2; "status =" prints the trial's
+// DFTA_CONT_* bits as they come (NONFINITE 1, STEP 2, WKB_TAIL 4, NORM 8)
 void print_phase_shift_table(dfta_scf* scf, const dfta_grid* grid, bool lsda)
 {
     const int ne = DFTAtom::phaseShiftPoints, nspin = lsda ? 2 : 1, nt = nspin * 5 * ne, norm = continuum_norm();

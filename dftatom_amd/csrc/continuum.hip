@@ -81,6 +81,31 @@ __device__ __forceinline__ void riccati_y(int l, double x, double s, double co, 
     *yhp = ym - (((double)l) / x) * y;
 }
 
+// atan2 of the header: the library's atan2 only in the octant 0 <= min / max <= 1, the quadrant put back with both halves of pi / 2 and
+// of pi.  (The library's own reconstruction subtracts from the ONE double nearest pi, 0.28 ulp short before its rounding: one ulp off in
+// a phase near pi.)  s and e: the exact sum of the constant's head and -hi (the head is at least twice hi).
+__device__ __forceinline__ double atan2_quadrants(double y, double x)
+{
+    const double kHalfPiHi = 1.5707963267948966, kHalfPiLo = 6.123233995736766e-17, kPiLo = 1.2246467991473532e-16;
+    const double ay = fabs(y), ax = fabs(x);
+    double hi = atan2(ay > ax ? ax : ay, ay > ax ? ay : ax), lo = 0.;      // (a NaN stays in place and comes out of the library)
+    if (ay > ax) {
+        const double s = kHalfPiHi - hi, e = (kHalfPiHi - s) - hi;
+        lo = (e + kHalfPiLo) - lo;
+        hi = s;
+    }
+    if (signbit(x)) {
+        const double s = kPi - hi, e = (kPi - s) - hi;
+        lo = (e + kPiLo) - lo;
+        hi = s;
+    }
+    return copysign(hi + lo, y);
+}
+
+// DFTA_CONT_NORM: the normalisation left double range -- an operand of the hypot is NaN (inf - inf in the matching) or the factor is
+// not finite.  (An infinite operand alone gives factor 0.0 and no bit: the header counts that as an underflow.)
+__device__ __forceinline__ bool norm_finite(double a, double b, double factor) { return a == a && b == b && fabs(factor) <= DBL_MAX; }
+
 template <int NP, bool ROWS>
 __global__ __launch_bounds__(64) void k_continuum(ContArgs a, int block0)
 {
@@ -212,9 +237,10 @@ __global__ __launch_bounds__(64) void k_continuum(ContArgs a, int block0)
             jhp = l == 0 ? co : x * sph_bessel(l - 1, x) - (((double)l) / x) * jh;
             riccati_y(l, x, s, co, &yh, &yhp);
             const double ca = um * yhp - U * yh, cb = U * jh - um * jhp;
-            dop = atan2(-cb, ca);
+            dop = atan2_quadrants(-cb, ca);
             factor = sqrt(2. / (kPi * k)) / hypot(ca, cb);
             scale = factor;
+            if (!norm_finite(ca, cb, factor)) { status |= DFTA_CONT_NORM; dop = nan; scale = nan; factor = nan; }
         } else {
             double kap[3];
             bool ok = true;
@@ -233,8 +259,9 @@ __global__ __launch_bounds__(64) void k_continuum(ContArgs a, int block0)
                 const double alp = -kp / ((2. * kap[1]) * sk);
                 const double A = um / al, B = al * dum - alp * um;
                 factor = kSqrtTwoOverPi / hypot(A, B);
-                dop = atan2(A, B);
+                dop = atan2_quadrants(A, B);
                 scale = factor;
+                if (!norm_finite(A, B, factor)) { status |= DFTA_CONT_NORM; dop = nan; scale = nan; factor = nan; }
             } else {
                 status |= DFTA_CONT_WKB_TAIL;
             }

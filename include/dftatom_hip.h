@@ -756,6 +756,15 @@ int  dfta_scf_momentum_orbitals(dfta_scf* s, int nq, const double* q, double* ou
  *     kp = (kap_{m+1} - kap_{m-1}) / (r_{m+1} - r_{m-1});  al = 1 / sqrt(kap_m);  alp = -kp / ((2 kap_m) kap_m^(1/2));
  *     A = u_m / al;  B = al u'_m - alp u_m;  factor = sqrt(2 / pi) / hypot(A, B);  phase = atan2(A, B): the phase of the WKB form
  *     u = C al sin(phase) at r_m -- no phase shift (that needs Coulomb functions), but the amplitude is the energy-normalised one.
+ *   atan2(y, x) in both modes: t = the device's atan2(min(|y|, |x|), max(|y|, |x|)), the first octant only; |y| > |x|: t <- pi/2 - t;
+ *     the sign bit of x set: t <- pi - t; the result takes the sign of y.  Both subtractions carry the constant as two doubles
+ *     (s = hi - t and its exact error, then the tails), so the reconstruction adds one rounding: a phase near pi/2 or pi is not off
+ *     by the 0.28 ulp that the one double nearest pi is short.
+ *   DFTA_CONT_NORM (E > 0, either mode): an operand of the hypot (a or b, A or B) is NaN, or the computed factor is not finite.  Then
+ *     delta_or_phase, scale, the sums and the rows are NaN; logderiv and nodes stand.  The floor: for l >= 3 the free normalisation
+ *     leaves double range below roughly E ~ 1e-150 .. 1e-200 (yh_l ~ x^-l overflows and a = inf - inf).  Before that yh'_l alone
+ *     overflows (l = 4, r_m = 25: from E ~ 4e-126 on), hypot is inf and factor = scale = 0.0 WITHOUT a bit: an underflow, although the
+ *     true factor is a normal double (1e-286 .. 1e-307) down to E ~ 1e-135.  Treat scale == 0.0 at E > 0 as "below double range".
  * Normalised, u_E(r) -> sqrt(2 / (pi k)) sin(k r - l pi / 2 + delta_l): Int u_E u_E' dr = delta(E - E').
  *
  * Partner sums (overlap and dipole integrals with bound orbitals), fused into the sweep.  Partner rows P_b (N doubles each), a power
@@ -778,6 +787,7 @@ int  dfta_scf_momentum_orbitals(dfta_scf* s, int nq, const double* q, double* ou
 #define DFTA_CONT_NONFINITE 1
 #define DFTA_CONT_STEP      2
 #define DFTA_CONT_WKB_TAIL  4
+#define DFTA_CONT_NORM      8
 /* on caller-supplied potentials and partner rows; host pointers.  V: nV x N; vidx (NULL: 0), l, E, m: ntrials; P: npartner_rows x N
  * (NULL with 0 rows); list k holds the rows list_rows[list_off[k] .. list_off[k+1] - 1], trial_list[t] (NULL: none) is the list of trial
  * t or -1.  Outputs per trial, any of which may be NULL: logderiv, nodes, delta_or_phase, scale, status; sums ntrials x 16 (entries

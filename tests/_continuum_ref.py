@@ -7,7 +7,9 @@ two wrong models that the gates are calibrated with.  No GPU, no library.
 The gate of a GPU quantity against the longdouble replay is 8 E + floor: E the float64 model's own distance from the replay (a running
 maximum over the +-8 neighbouring energies of a ladder: the error of a single energy can sit in a zero crossing), floor the largest change
 of the float64 model when every division result is moved by +-1 ulp, over 8 seeds (the device's division, sqrt and the table s are
-correctly rounded; its sin, cos, atan2 and hypot are not -- 1 ulp on every division moves the result by more than they do).
+correctly rounded; its sin, cos, atan2 and hypot are not -- 1 ulp on every division moves the result by more than they do.  Where no seed
+moves a phase shift the gate is 0.0 and asks for the correctly rounded value: Coulomb Z = 10, l = 1 on uni10 at E <= 1e-4, which is why
+the kernel puts the quadrant of its atan2 back with pi as two doubles, atan2_quadrants below).
 """
 import math
 
@@ -19,7 +21,7 @@ from _orb_ref import GRIDS as _ORB_GRIDS, hydrogenic_u, weights      # noqa: F40
 LD = np.longdouble
 EPS = 2.0 ** -52
 FREE, WKB = 0, 1
-NONFINITE, STEP, WKB_TAIL = 1, 2, 4
+NONFINITE, STEP, WKB_TAIL, NORM = 1, 2, 4, 8
 MAX_PARTNERS = 16
 TILE = 256
 ALPHA_FS = 1 / 137.035999084
@@ -28,7 +30,7 @@ PI_LD = LD("3.14159265358979323846264338327950288419716939937510")
 
 # (levels, delta, Rmax); delta None: uniform
 GRIDS = {"uni3": (3, None, 2.0), "uni10": (10, None, 25.0), "uni11": (11, None, 25.0), "log12": (12, 2e-3, 25.0),
-         "log13": (13, 1e-3, 25.0), "uni13": (13, None, 25.0)}
+         "log13": (13, 1e-3, 25.0), "uni13": (13, None, 25.0), "uni14": (14, None, 25.0)}
 
 
 def tables(levels, delta, Rmax):
@@ -54,6 +56,27 @@ class Perturb:
         return np.where(up, np.nextafter(q, np.inf), np.nextafter(q, -np.inf))
 
 
+def atan2_quadrants(y, x, tails=True):
+    """the header's atan2 in float64 on top of np.arctan2 in the first octant: the quadrant put back with pi / 2 and pi as two doubles
+    each (tails=False: with the one nearest double, the usual reconstruction) -- the operations of continuum.hip's atan2_quadrants"""
+    h_hi, h_lo, p_hi, p_lo = np.float64(1.5707963267948966), np.float64(6.123233995736766e-17), np.float64(math.pi), np.float64(1.2246467991473532e-16)
+    if not tails:
+        h_lo = p_lo = np.float64(0.0)
+    y, x = np.asarray(y, dtype=np.float64), np.asarray(x, dtype=np.float64)
+    with np.errstate(all="ignore"):
+        ay, ax = np.abs(y), np.abs(x)
+        swap, neg = ay > ax, np.signbit(x)
+        hi = np.arctan2(np.where(swap, ax, ay), np.where(swap, ay, ax))
+        lo = np.zeros_like(hi)
+        s = h_hi - hi
+        e = (h_hi - s) - hi
+        hi, lo = np.where(swap, s, hi), np.where(swap, (e + h_lo) - lo, lo)
+        s = p_hi - hi
+        e = (p_hi - s) - hi
+        hi, lo = np.where(neg, s, hi), np.where(neg, (e + p_lo) - lo, lo)
+        return np.copysign(hi + lo, y)
+
+
 def _riccati(l, x, dtype):
     """(jh, jh', yh, yh') of the header at x > 0 (arrays)"""
     s, co = np.sin(x), np.cos(x)
@@ -76,7 +99,9 @@ def sweep(V, l, E, m, r, s, c, lam, mode=FREE, P=None, power=0, dtype=np.float64
     """The header's arithmetic for the trials (E[t], m[t]) of ONE potential V and one l, vectorised over the trials; r, s: float64
     tables; P: (nb, N) partner rows.  dtype np.float64: the kernel's model; LD: the replay (inputs are converted, nothing else changes).
     perturb: a Perturb (float64 only); wrong: "noc" drops the delta^2 / 4 term, "tenth" uses 1/10 in place of 1/12.
-    Returns logderiv, nodes, delta (phase shift or WKB phase), scale, status, sums (nt, nb) and, on request, rows (nt, N)."""
+    Returns logderiv, nodes, delta (phase shift or WKB phase), scale, status, sums (nt, nb) and, on request, rows (nt, N); sums_raw and
+    rows_raw are the two before their one multiplication by the factor.  NORM is set
+    by the header's rule in the sweep's own format; gate() marks the replay's trials where the float64 model carries it."""
     T = dtype
     div = (lambda a, b: perturb(a / b)) if perturb is not None else (lambda a, b: a / b)      # noqa: E731
     V, r, s = (np.asarray(x, dtype=np.float64).astype(T) for x in (V, r, s))
@@ -157,6 +182,7 @@ def sweep(V, l, E, m, r, s, c, lam, mode=FREE, P=None, power=0, dtype=np.float64
             ca, cb = um * yhp - U * yh, U * jh - um * jhp
             pi = PI_LD if T is LD else T(math.pi)
             dl, fc = np.arctan2(-cb, ca), div(np.sqrt(div(T(2), pi * k)), np.hypot(ca, cb))
+            formed, opa, opb = np.ones(nt, dtype=bool), ca, cb
         else:
             kap2 = [(T(2) * (Ep - V[m + q])) - div(L, r[m + q] * r[m + q]) for q in (-1, 0, 1)]
             ok = (kap2[0] > 0) & (kap2[1] > 0) & (kap2[2] > 0)
@@ -169,25 +195,32 @@ def sweep(V, l, E, m, r, s, c, lam, mode=FREE, P=None, power=0, dtype=np.float64
             A, B = div(um, al), al * dum - alp * um
             c2 = np.sqrt(T(2) / PI_LD) if T is LD else T(0.7978845608028654)
             dl, fc = np.arctan2(A, B), div(c2, np.hypot(A, B))
+            formed, opa, opb = ok, A, B
             dl, fc = np.where(ok, dl, T(np.nan)), np.where(ok, fc, T(np.nan))
         delta, scale, factor = np.where(pos, dl, delta), np.where(pos, fc, scale), np.where(pos, fc, factor)
         bad = (status & (NONFINITE | STEP)) != 0
         nan = T(np.nan)
+        # NORM: the factor was formed (E > 0, no other exit) from a NaN operand of the hypot, or is not finite
+        lost = pos & formed & ~bad & (np.isnan(opa) | np.isnan(opb) | ~np.isfinite(fc))
+        status[lost] |= NORM
+        delta, scale, factor = (np.where(lost, nan, x) for x in (delta, scale, factor))
         logderiv, delta, scale, factor = (np.where(bad, nan, x) for x in (logderiv, delta, scale, factor))
         nodes[bad] = -1
         out = {"logderiv": logderiv, "nodes": nodes, "delta": delta, "scale": scale, "status": status,
-               "sums": ((tot * T(0.375)) * factor[None, :]).T}
+               "sums": ((tot * T(0.375)) * factor[None, :]).T, "sums_raw": (tot * T(0.375)).T}
         if want_rows:
-            rows = np.zeros((nt, N), dtype=T)
+            rows, raw = np.zeros((nt, N), dtype=T), np.zeros((nt, N), dtype=T)
             for tt in range(nt):
-                rows[tt, 1:mend[tt] + 1] = (sq[1:mend[tt] + 1] * y_all[1:mend[tt] + 1, tt]) * factor[tt]
-            out["rows"] = rows
+                raw[tt, 1:mend[tt] + 1] = sq[1:mend[tt] + 1] * y_all[1:mend[tt] + 1, tt]
+                rows[tt, 1:mend[tt] + 1] = raw[tt, 1:mend[tt] + 1] * factor[tt]
+            out["rows"], out["rows_raw"] = rows, raw
     return out
 
 
 # ---- gates ------------------------------------------------------------------------------------------------------------------------------
 SEEDS = tuple(range(8))
 NEIGHBOURS = 8
+LADDER_E = (1e-100, 1e-40, 1e-12, 1e-8, 1e-4)      # small positive energies: sincos, j_l and yh_l at tiny x = k r (FREE)
 
 
 def running_max(x, half=NEIGHBOURS):
@@ -240,6 +273,14 @@ def gate(V, l, E, m, r, s, c, lam, mode, P=None, power=0, seeds=SEEDS, want_rows
     nt, ns = len(E), len(seeds)
     ld = sweep(V, l, E, m, r, s, c, lam, mode, P, power, dtype=LD, want_rows=want_rows)
     f64 = sweep(V, l, E, m, r, s, c, lam, mode, P, power, want_rows=want_rows)
+    lost = (f64["status"] & NORM) != 0               # the float64 normalisation left double range: the trial's normalised outputs are NaN,
+    if lost.any():                                   # and the replay (whose range is wider) has no say on them
+        ld["status"] = np.where(lost, ld["status"] | NORM, ld["status"])
+        for q in ("delta", "scale"):
+            ld[q] = np.where(lost, LD(np.nan), ld[q])
+        for q in ("sums", "rows"):
+            if q in ld:
+                ld[q] = np.where(lost[:, None], LD(np.nan), ld[q])
     own = distances(f64, ld)
     pert = sweep(V, l, np.tile(E, ns), np.tile(m, ns), r, s, c, lam, mode, P, power, perturb=Perturb(seeds), want_rows=want_rows)
     gates = {}

@@ -70,19 +70,24 @@ int main()
     bad += instance_for(0) != 0 || instance_for(1) != 4 || instance_for(4) != 4 || instance_for(5) != 8 || instance_for(9) != 16 || instance_for(16) != 16;
 
     // plans: (trials per group ...) -> blocks, padded positions, instance, chunk
-    struct Shape { int N; std::vector<int> groups; int partners; bool rows; };
-    const Shape shapes[] = {{4097, {1}, 0, false}, {4097, {63, 64, 65}, 5, true}, {4097, {129}, 16, false}, {131073, {256, 256, 256, 256, 256}, 11, true},
-                            {9, {70000}, 0, true}};
+    // a group is an l of potential 0, or (by_potential) a potential of its own with l = group % 5: more than five groups
+    struct Shape { int N; std::vector<int> groups; int partners; bool rows; bool by_potential; };
+    const Shape shapes[] = {{4097, {1}, 0, false, false}, {4097, {63, 64, 65}, 5, true, false}, {4097, {129}, 16, false, false},
+                            {131073, {256, 256, 256, 256, 256}, 11, true, false}, {9, {70000}, 0, true, false},
+                            {9, std::vector<int>(1100, 1), 3, true, true}, {1025, std::vector<int>(520, 1), 3, true, true}};
     for (const Shape& sh : shapes) {
         std::vector<int> vv, ll, mm, tl, off = {0}, rows;
         std::vector<double> EE;
         for (size_t gi = 0; gi < sh.groups.size(); ++gi)
-            for (int t = 0; t < sh.groups[gi]; ++t) { vv.push_back(0); ll.push_back((int)gi); mm.push_back(3); EE.push_back(1.); tl.push_back(0); }
+            for (int t = 0; t < sh.groups[gi]; ++t) {
+                vv.push_back(sh.by_potential ? (int)gi : 0); ll.push_back(sh.by_potential ? (int)gi % 5 : (int)gi);
+                mm.push_back(3); EE.push_back(1.); tl.push_back(0);
+            }
         // interleave: the trials of a group need not be adjacent in the call
         if (vv.size() > 2) { std::swap(ll[0], ll[vv.size() - 1]); }
         for (int j = 0; j < sh.partners; ++j) rows.push_back(j);
         off.push_back(sh.partners);
-        Call w = base(sh.N, 1, vv, ll, EE, mm);
+        Call w = base(sh.N, sh.by_potential ? (int)sh.groups.size() : 1, vv, ll, EE, mm);
         if (sh.partners) { w.npartner_rows = sh.partners; w.nlists = 1; w.list_off = off.data(); w.list_rows = rows.data(); w.trial_list = tl.data(); }
         bad += check(w) != nullptr;
         const Plan p = plan(w, sh.rows);
@@ -91,7 +96,7 @@ int main()
         for (const Block& b : p.blocks)
             for (int j = 0; j < kWave; ++j) {
                 const int t = p.order[b.first + j];
-                if (j < b.cnt) { bad += t < 0 || ll[t] != b.l || b.first % kWave != 0; if (t >= 0) ++seen[t]; }
+                if (j < b.cnt) { bad += t < 0 || ll[t] != b.l || vv[t] != b.v || b.first % kWave != 0; if (t >= 0) ++seen[t]; }
                 else bad += t != -1;
             }
         for (int sgn : seen) bad += sgn != 1;

@@ -151,6 +151,69 @@ def test_status_bits_and_unnormalised_trials():
     Vb[N - 4:] = 5.0
     out = R.sweep(Vb, 0, [0.5], [N - 2], r, s, c, lam, R.WKB)
     assert out["status"][0] == R.WKB_TAIL and np.isnan(out["scale"][0]) and np.isfinite(out["logderiv"][0]) and out["nodes"][0] >= 0
+    # the free normalisation below double range, l = 4: at E = 1e-300 yh_4 ~ x^-4 overflows and a = inf - inf -- the NORM bit, u'/u and
+    # nodes stand; at E = 1e-150 only yh'_4 overflows, hypot is inf and the scale is 0.0 (the replay's: 1.3e-340) without a bit
+    P = np.array([r * np.exp(-r)])
+    out = R.sweep(V, 4, [1e-300, 1e-150], [N - 2] * 2, r, s, c, lam, R.FREE, P, 1, want_rows=True)
+    assert list(out["status"]) == [R.NORM, 0] and np.isnan(out["scale"][0]) and out["scale"][1] == 0.0
+    assert np.all(np.isfinite(out["logderiv"])) and np.all(out["nodes"] >= 0)
+    assert np.isnan(out["delta"][0]) and np.isnan(out["sums"][0, 0]) and np.all(np.isnan(out["rows"][0, 1:])) and out["rows"][0, 0] == 0
+    assert not out["rows"][1].any() and out["sums"][1, 0] == 0
+    ld = R.sweep(V, 4, [1e-300, 1e-150], [N - 2] * 2, r, s, c, lam, R.FREE, dtype=LD)
+    assert not ld["status"].any() and np.all(np.isfinite(ld["scale"])) and 0 < ld["scale"][1] < 5e-324
+    # gate() marks the replay where the float64 model carries the bit: the trial counts as one without a normalisation
+    ld, f64, gates = R.gate(V, 4, [1e-300, 1e-150], N - 2, r, s, c, lam, R.FREE, P, 1, seeds=(0,), want_rows=True)
+    assert list(ld["status"]) == [R.NORM, 0] and np.isnan(ld["scale"][0]) and np.all(np.isnan(ld["rows"][0])) and np.isfinite(ld["scale"][1])
+    assert all(np.all(np.isfinite(gates[q])) for q in R.QUANTITIES)
+
+
+def test_atan2_reconstruction_with_both_halves_of_pi():
+    """the kernel's atan2 takes the library's value in the first octant only and puts the quadrant back with pi / 2 and pi as two doubles:
+    against mpmath that is as good as a correctly rounded first octant allows (within 1 ulp, wrong in under 3 % of 4000 draws), where
+    the reconstruction from the one nearest double is wrong in more than 10 %; the special values are np.arctan2's, sign included"""
+    import mpmath as mp
+    mp.mp.dps = 40
+    rng = np.random.default_rng(2)
+    n = 4000
+    x = rng.standard_normal(n) * 10.0 ** rng.integers(-3, 3, n)
+    y = rng.standard_normal(n) * 10.0 ** rng.integers(-6, 3, n)
+    ref = np.array([float(mp.atan2(mp.mpf(float(a)), mp.mpf(float(b)))) for a, b in zip(y, x)])
+    two, one = R.atan2_quadrants(y, x), R.atan2_quadrants(y, x, tails=False)
+    assert np.all(np.abs(two - ref) <= np.spacing(np.abs(ref))) and np.mean(two != ref) < 0.03 and np.mean(one != ref) > 0.10
+    # the case that showed it: Coulomb Z = 10, l = 1, uni10, E = 1e-4 -- the exact phase shift lies 0.38 ulp below the double nearest it,
+    # the one-double pi is another 0.28 ulp short: 0.66 ulp, the neighbour below
+    r, s, c, lam = R.tables(*R.GRIDS["uni10"])
+    V = np.zeros(len(r))
+    V[1:] = -10.0 / r[1:]
+    ld = R.sweep(V, 1, [1e-4], [len(r) - 2], r, s, c, lam, R.FREE, dtype=LD)["delta"][0]
+    f64 = R.sweep(V, 1, [1e-4], [len(r) - 2], r, s, c, lam, R.FREE)["delta"][0]
+    assert f64 == np.float64(ld) and 0.3 < float((LD(f64) - ld) / LD(2.0 ** -51)) < 0.45
+    inf, nan = np.inf, np.nan
+    for yy, xx in ((0.0, -1.0), (-0.0, -1.0), (0.0, -0.0), (-0.0, -0.0), (0.0, 0.0), (-0.0, 0.0), (1.0, -0.0), (1.0, 0.0), (inf, -inf), (inf, inf),
+                   (-1.0, -inf), (1.0, inf), (inf, 1.0), (-inf, -1.0), (1e-300, -1e300), (5e-324, -1.0), (nan, 1.0), (1.0, nan), (nan, -1.0)):
+        got, want = R.atan2_quadrants(yy, xx), np.arctan2(yy, xx)
+        assert (np.isnan(got) and np.isnan(want)) or (got == want and np.signbit(got) == np.signbit(want)), (yy, xx, got, want)
+
+
+def test_energy_ladder_model_against_its_gate():
+    """the premise of the GPU suite's energy ladder, E = 1e-100 .. 1e-4 (uni10, free particle and Coulomb Z = 10, l = 1 .. 4, FREE): no
+    status bit in either format, a positive scale, finite gates.  Prints the model's own distance over its gate (at most 1/8 by the
+    gate's construction; close to it when the floor adds little, i.e. the gate is about eight times the model's own error)"""
+    r, s, c, lam = R.tables(*R.GRIDS["uni10"])
+    N = len(r)
+    V = np.zeros((2, N))
+    V[1, 1:] = -10.0 / r[1:]
+    worst = 0.0
+    for v in range(2):
+        for l in range(1, 5):
+            ld, f64, gates = R.gate(V[v], l, R.LADDER_E, N - 2, r, s, c, lam, R.FREE)
+            assert not f64["status"].any() and not ld["status"].any() and np.all(f64["scale"] > 0)
+            own = R.distances(f64, ld)
+            for q in ("logderiv", "delta", "scale"):
+                assert np.all(own[q] <= gates[q]), (v, l, q)
+                worst = max(worst, float(np.max(own[q] / np.where(gates[q] > 0, gates[q], 1))))
+    print("ladder: the model's largest ratio to its gate %.3f" % worst)
+    assert 0 < worst <= 0.125
 
 
 # ---- the header, the binding, the planner ---------------------------------------------------------------------------------------------------
@@ -167,8 +230,8 @@ def test_new_symbols_are_declared_and_bound():
     assert int(defines["DFTA_ABI_VERSION"]) == D.ABI_VERSION          # entries were added, no struct grew
     assert (int(defines["DFTA_CONT_FREE"]), int(defines["DFTA_CONT_WKB"])) == (D.CONT_FREE, D.CONT_WKB) == (R.FREE, R.WKB)
     assert int(defines["DFTA_CONT_MAX_PARTNERS"]) == D.CONT_MAX_PARTNERS == R.MAX_PARTNERS
-    assert tuple(int(defines["DFTA_CONT_" + n]) for n in ("NONFINITE", "STEP", "WKB_TAIL")) == (R.NONFINITE, R.STEP, R.WKB_TAIL) \
-        == (D.CONT_NONFINITE, D.CONT_STEP, D.CONT_WKB_TAIL)
+    assert tuple(int(defines["DFTA_CONT_" + n]) for n in ("NONFINITE", "STEP", "WKB_TAIL", "NORM")) == (R.NONFINITE, R.STEP, R.WKB_TAIL, R.NORM) \
+        == (D.CONT_NONFINITE, D.CONT_STEP, D.CONT_WKB_TAIL, D.CONT_NORM) == (1, 2, 4, 8)
     lib = D.load()
     assert all(hasattr(lib, n) for n in NEW_SYMBOLS)
     for f in (D.continuum, D.Scf.continuum, D.Scf.photoionization):
@@ -191,13 +254,19 @@ def test_host_planner_stand_alone_under_sanitizers(tmp_path):
                     os.path.join(here, "continuum_plan_main.cpp"), os.path.join(csrc, "continuum_plan.cpp")], check=True, timeout=300)
     run = subprocess.run([exe], capture_output=True, text=True, timeout=120)
     assert run.returncode == 0, (run.stdout, run.stderr)
-    plans = {(int(a), int(b)): (int(c), int(d), int(e), int(f)) for tag, a, b, c, d, e, f in (ln.split() for ln in run.stdout.strip().split("\n"))}
+    lines = [ln.split() for ln in run.stdout.strip().split("\n")]
+    plans = {(int(a), int(b)): (int(c), int(d), int(e), int(f)) for tag, a, b, c, d, e, f in lines}
+    assert len(plans) == len(lines) == 7
     # (N, trials) -> (waves, padded positions, instance, waves per chunk of rows)
     assert plans[(4097, 1)] == (1, 64, 0, 0)
     assert plans[(4097, 192)] == (4, 256, 8, 4)             # groups of 63, 64 and 65 trials: 1 + 1 + 2 waves; 5 partners: instance 8
     assert plans[(4097, 129)] == (3, 192, 16, 0)
     assert plans[(131073, 1280)] == (20, 1280, 16, 3)       # 64 rows of 131 073 doubles: 64 MiB a wave, three fit 256 MiB
     assert plans[(9, 70000)] == (1094, 70016, 0, 1023)      # the scaling launch's grid caps a chunk
+    # the two-chunk calls of tests/test_gpu_continuum.py, one trial per potential (every trial its own wave): 1023 + 77 waves by the
+    # wave cap, 511 + 9 waves by the 256 MiB budget (64 rows of 1025 doubles: 524 800 bytes a wave)
+    assert plans[(9, 1100)] == (1100, 70400, 4, 1023)
+    assert plans[(1025, 520)] == (520, 33280, 4, 511)
 
 
 def test_front_end_usage_names_the_continuum_tables():
